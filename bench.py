@@ -11,12 +11,17 @@ sweep`, the default) is the north-star decomposition of the same job: the rotati
 N / teams ranks; a team's first rank sweeps its rotation(s), and when a team has partners (N = 8: 4 rotations x 2 beam
 shards) it broadcasts the boundary MPS of every row to them over RCCL inside the timed step (what the beam shards need
 before the search can start).  Same total work for every N => "scaling": "strong".  `--mode replicas` keeps the round-1
-form (every rank its own instance, no collective, "weak").  After the timed steps one full 4-rotation ground-state
-search (solve_rotations: sweeps + M=1024 beam + RCCL gather at merge time) is timed once as `full_solve`.
+form (every rank its own instance, no collective, "weak").  With `--full`, after the timed steps one full 4-rotation
+ground-state search (solve_rotations: sweeps + M=1024 beam + RCCL gather at merge time) is timed once as `full_solve`.
 
-Prints ONE JSON line on rank 0.  `roofline` describes the kernel family with the largest summed duration, timed with
-HIP events on its launch stream inside the timed region; `cpu_baseline` times the CPU oracle on a bounded sample of the
-same sweep (bulk sites of the middle row) on this box's host cores.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the line (`metric`,
+`value`, `unit`, `ms_per_step`, ...).  `--full` adds everything else, outside the timed steps unless stated: the
+single-chain sweeps with events on every launch (kernel and phase tables, launch census), `roofline` (the kernel family
+with the largest summed duration, timed with HIP events on its launch stream inside the timed region), `full_solve`, and
+`cpu_baseline` (the CPU oracle on a bounded sample of the same sweep, whole bulk rows, on the host cores).
+
+`--dump-outputs DIR` writes what the last timed step computed (the boundary MPS of every row of rank 0's rotations) as
+float64 .npy files; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -126,6 +131,44 @@ def load_pmc():
     return None
 
 
+DUMP_SAMPLE_BYTES = 48 << 20       # the sampled site-tensor elements; with the small arrays the dump stays under 64 MB
+
+
+def dump_outputs(out_dir, solvers, rots):
+    """What the timed path hands its caller, for each lattice rotation r swept on this rank: the boundary MPS rhoT[ny] of
+    every row ny (site tensors A[nx] of shape (D[nx], d, D[nx + 1]), the accumulated power-of-two norm factor normC, the bond
+    dimensions D) and the sweep's rhoT_overlap / rhoT_discarded.  The site tensors (up to 8 MB each at L = 2048) enter as a
+    fixed sample: K elements of each at indices drawn by a generator seeded with (r, ny, nx), K set by the arguments alone.
+    Files, float64, Ny rows each:
+        rot<r>_sites.npy      (Ny, Nx, K)     sampled elements of A[nx] of rhoT[ny]
+        rot<r>_bond_dims.npy  (Ny, Nx + 1)    D of rhoT[ny]
+        rot<r>_log2_normC.npy (Ny,)           log2 normC of rhoT[ny]
+        rot<r>_overlap.npy, rot<r>_discarded.npy (Ny,)"""
+    os.makedirs(out_dir, exist_ok=True)
+    if not solvers:
+        return
+    K = max(1, min(2048, DUMP_SAMPLE_BYTES // (8 * sum(s.Ny * s.Nx for s in solvers))))
+    for r, s in zip(rots, solvers):
+        Ny, Nx = s.Ny, s.Nx
+        dev = s.rhoT[0].A[0].device
+        sites = torch.empty((Ny, Nx, K), dtype=torch.float64, device=dev)
+        log2_normC = np.zeros(Ny)
+        for ny in range(Ny):
+            psi = s.rhoT[ny]
+            for nx, A in enumerate(psi.A):
+                idx = np.random.default_rng([r, ny, nx]).integers(0, A.numel(), K)
+                sites[ny, nx] = A.reshape(-1)[torch.from_numpy(idx).to(dev)]
+            if psi._nfs:
+                log2_normC[ny] = float(torch.stack([f[0] for f in psi._nfs]).log2().sum())
+        out = {'sites': sites.cpu().numpy(),
+               'bond_dims': np.array([s.rhoT[ny].D for ny in range(Ny)], dtype=np.float64),
+               'log2_normC': log2_normC,
+               'overlap': np.array([float(s.rhoT_overlap[ny]) for ny in range(Ny)]),
+               'discarded': np.array([float(s.rhoT_discarded[ny]) for ny in range(Ny)])}
+        for name, a in out.items():
+            np.save(os.path.join(out_dir, 'rot%d_%s.npy' % (r, name)), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -155,7 +198,16 @@ def main():
                     help='multi-rank rehearsal on a single GPU: every rank uses cuda:0 and the exchange runs over gloo')
     ap.add_argument('--force-dist', action='store_true',
                     help='initialise the RCCL process group even with one rank (rehearses the multi-GPU code path on one GPU)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: kernel / phase tables and roofline (--no-profile drops them), '
+                         'the full ground-state search (--no-search) and the CPU baseline (--cpu-rows)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed to DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
+    if not args.full:
+        args.no_profile, args.no_search, args.cpu_rows = True, True, 0
     if args.L:
         args.workload = 'chimera%d' % args.L
     kind, n, seed, beta = WORKLOADS[args.workload]
@@ -188,7 +240,7 @@ def main():
     from tnac4o_amd import _lib, parallel
     from tnac4o_amd.auxx import synthetic_chimera, synthetic_rmf
     lib = _lib.lib()
-    pmc = load_pmc()
+    pmc = load_pmc() if args.full else None
     replicas = args.mode == 'replicas'
     inst_seed = seed + (rank if replicas else 0)
     J = synthetic_chimera(n, n, inst_seed) if kind == 'Ising' else synthetic_rmf(n, n, 8, inst_seed)
@@ -336,6 +388,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = 1e3 * dt / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solvers, my_rots)
 
     # second headline, outside the timed region: one full ground-state search of the 4 rotations
     # (sweeps + beam M=1024, merge of the rotations; with N > 1 sharded exactly like the timed step, one RCCL all-gather)
@@ -555,6 +609,11 @@ def cpu_baseline(n, args, solver, kw, single_ms):
     except ImportError:
         threadpoolctl = None
     phys, logical = physical_cores(), os.cpu_count() or 1
+    # OpenBLAS cannot grow its thread pool beyond the size it started with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else the CPU
+    # count): a higher limit crashes it in its worker threads.  That start-up size bounds every thread count tried below.
+    usable = logical
+    if threadpoolctl is not None:
+        usable = min([p['num_threads'] for p in threadpoolctl.threadpool_info() if p.get('user_api') == 'blas'] or [logical])
 
     def limited(nt, fn):
         if threadpoolctl is None:
@@ -571,7 +630,7 @@ def cpu_baseline(n, args, solver, kw, single_ms):
         t0 = time.perf_counter()
         mr.qr_pos(Tp @ Cp)
         return 1e3 * (time.perf_counter() - t0)
-    counts = [1] if threadpoolctl is None else sorted({c for c in (1, 8, 16, 32, 64, phys) if c <= logical})
+    counts = [1] if threadpoolctl is None else sorted({c for c in (1, 8, 16, 32, 64, phys, usable) if c <= usable})
     proxy_ms = {}
     for nt in counts:
         limited(nt, proxy)                                 # (first touch: thread pool start-up)
@@ -584,7 +643,7 @@ def cpu_baseline(n, args, solver, kw, single_ms):
     rows = [n // 2 - i for i in range(max(1, args.cpu_rows))]
     per_row = []
     row_ms_by_threads = {}
-    cand = [threads] if threadpoolctl is None else sorted({c for c in (8, 16, 32, threads) if c <= logical})
+    cand = [threads] if threadpoolctl is None else sorted({c for c in (8, 16, 32, threads) if c <= usable})
     for ny in rows:
         psi = solver.rhoT[ny + 1]
         mpo = solver._row_mpo(ny)
@@ -652,7 +711,7 @@ def cpu_baseline(n, args, solver, kw, single_ms):
     except Exception as e:                                 # noqa: BLE001 -- a sub-field must not take the bench line down
         first_pass = {'error': repr(e)}
     return {'value': cpu_row_ms, 'unit': 'ms per bulk row (apply_mpo + compress_mps)', 'cores': threads, 'kind': 'port', 'cpu_model': cpu_model(),
-            'physical_cores': phys, 'logical_cores': logical, 'proxy_ms_by_blas_threads': proxy_ms, 'row_ms_by_blas_threads': row_ms_by_threads,
+            'physical_cores': phys, 'logical_cores': logical, 'usable_blas_threads': usable, 'proxy_ms_by_blas_threads': proxy_ms, 'row_ms_by_blas_threads': row_ms_by_threads,
             'sample': 'whole bulk rows %s of the %d-row sweep (chi = %d): MPS.apply_mpo + MPS.compress_mps of the reference algorithm (oracle/, '
                       'numpy + scipy LAPACK) from the boundary MPS the GPU sweep fed into each row; %d BLAS threads = the fastest of %s on the first of '
                       'these rows (row_ms_by_blas_threads)' % (rows, n, kw['Dmax'], threads, sorted(int(k) for k in row_ms_by_threads) or [threads]),

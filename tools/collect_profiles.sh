@@ -11,10 +11,10 @@ echo "== counters" > $OUT/log.txt
 rocprofv3 -L 2>/dev/null | grep -i -E "mfma|FETCH_SIZE|WRITE_SIZE|SQ_BUSY_CYCLES|GRBM_GUI_ACTIVE" | head -60 > $OUT/counters_available.txt
 if [ -z "$PMC_ONLY" ]; then
 echo "== kernel trace of the bench command (4 interleaved chains)" >> $OUT/log.txt
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-search --cpu-rows 0 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-search --cpu-rows 0 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 echo "rc=$?" >> $OUT/log.txt
 echo "== kernel trace of the single-chain form" >> $OUT/log.txt
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt1 -o bench -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-search --cpu-rows 0 --concurrent 1 > $OUT/bench_c1_under_rocprof.json 2> $OUT/bench_c1_under_rocprof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt1 -o bench -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-search --cpu-rows 0 --concurrent 1 > $OUT/bench_c1_under_rocprof.json 2> $OUT/bench_c1_under_rocprof.err
 echo "rc=$?" >> $OUT/log.txt
 fi
 python3 $ROOT/tools/pmc_probe.py 2>/dev/null | grep PROBE_TIMES > $OUT/probe_times.txt
