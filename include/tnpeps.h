@@ -290,6 +290,30 @@ int tn_apply_truncation(const double* Al, int64_t ml, int64_t k0, const double* 
                         const double* Vt, int64_t vrs, int64_t vcs, const double* Ar, int64_t k1, int64_t nr, const double* S,
                         double* Al_new, double* Ar_new, double* Cdiag, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- thermal cluster marginals (tnac4o.calculate_marginals; no counterpart in the reference, which only samples).
+ * One row ny of the lattice between its two boundaries: At (Dt, pd, Dt2) a site of rhoT[ny+1], W (bl, pd, br, pu) the row-MPO site
+ * W[l,d,r,u], Ab (Db, pu, Db2) a site of rhoB[ny]; all contiguous.  Environments keep the MPO bond outermost.
+ *   tn_env3 side 0 (left step):  out EL' (br, Dt2, Db2) = sum EL (bl, Dt, Db) . At . W . Ab
+ *           side 1 (right step): out ER (bl, Dt, Db)    = sum At . W . Ab . ER' (br, Dt2, Db2)
+ *   the result is divided by its nfactor (a power of two); *log2nf_out = *log2nf_in (0 when null) + log2(nfactor), a device scalar.
+ *   half_out (may be null): receives the step's first product, the half of the cell marginal this side contributes:
+ *           side 0: HL (bl, pd, Dt2, Db) = sum_t EL . At;   side 1: HR (pu, br, Dt2, Db) = sum_b' ER' . Ab.
+ * No counterpart in the reference. */
+int64_t tn_env3_ws_bytes(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2);
+int tn_env3(int side, const double* E, const double* At, const double* W, const double* Ab, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl,
+            int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out, double* log2nf_out, double* half_out,
+            void* ws, int64_t ws_bytes, void* stream);
+/* Marginal of one cell from the two half-products of tn_env3 at that cell (K = Dt2 Db):
+ *   X[l,d,u,r] = sum_K HL[(l,d),K] HR[(u,r),K];   P[s] prop. to sum_{l,u} F[s,l,u] X[l,dmap[s],u,rmap[s]]   (F (q, bl, pu); int32 maps)
+ * then the negative-probability rule of tn_calc_pn (minP: its relative magnitude, <= 0; -1 for an all-zero table, which comes back
+ * uniform) and the normalisation to sum 1.  *log2z = log2(sum of the raw table) + *log2L + *log2R (nulls count 0): the log2 of the
+ * row contraction <rhoB[ny]| row ny |rhoT[ny+1]> when log2L / log2R are the running totals of the environments.  q <= 16384.
+ * No counterpart in the reference. */
+int64_t tn_cluster_marginal_ws_bytes(int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K);
+int tn_cluster_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t bl,
+                        int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* P, double* minP,
+                        double* log2z, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- measurement: bracket every launch of the selected kernel families with HIP events on the launch stream.
  * family ids: 0-3 gemm_kernel<128,128> / <128,32> / <32,128> / <64,64> (all operand layouts), 4 splitk_reduce,
  * 5 absorb, 6 gram_partial, 7 eig_small, 8 rows_times_small, 9 small_t_times_vecs, 10 tsqr_factor/apply,

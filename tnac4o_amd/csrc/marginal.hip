@@ -1,0 +1,280 @@
+// Thermal cluster marginals: the three-layer contraction  rhoB[ny] . row ny . rhoT[ny+1]  with one cell left open
+// (tnac4o.calculate_marginals).  No counterpart in the reference, which only samples (gibbs_sampling).
+//
+// Operands of one cell (all contiguous, C order):
+//   At (Dt, pd, Dt2)   site of rhoT[ny+1]: top bond, the row's down leg, top bond
+//   W  (bl, pd, br, pu) row MPO site W[l,d,r,u] = sum_s T[s,l,d,r,u]  (tn_mpo_from_factor)
+//   Ab (Db, pu, Db2)   site of rhoB[ny]:   bottom bond, the row's up leg, bottom bond
+// Environments keep the MPO bond outermost: EL (bl, Dt, Db) left of the cell, ER (br, Dt2, Db2) right of it.
+//
+// env3, side 0 (left step, EL -> EL' (br, Dt2, Db2)), three strided GEMMs and no permutation of any operand:
+//   HL[l][d][t'][b] = sum_t  At[t,(d,t')] EL[l][t][b]                  batch l:  M = pd Dt2,  N = Db,  K = Dt
+//   Y [r][t'][b][u] = sum_{l,d} HL[(l,d),(t',b)] W[(l,d),r,u]          batch r:  M = Dt2 Db,  N = pu,  K = bl pd
+//   EL'[(r,t'),b']  = sum_{b,u} Y[(r,t'),(b,u)] Ab[(b,u),b']                      M = br Dt2, N = Db2, K = Db pu
+// env3, side 1 (right step, ER -> ER (bl, Dt, Db)); W is first permuted to W'[l][d][u][r] (bl pd pu br doubles, the only copy):
+//   HR[u][r][t'][b] = sum_b' ER[(r,t'),b'] Ab[b,u,b']                  batch u:  M = br Dt2,  N = Db,  K = Db2
+//   Y [(l,d),(t',b)] = sum_{u,r} W'[(l,d),(u,r)] HR[(u,r),(t',b)]                 M = bl pd,  N = Dt2 Db, K = pu br
+//   ER[l][t][b]     = sum_{d,t'} At[t,(d,t')] Y[l][(d,t')][b]          batch l:  M = Dt,  N = Db,  K = pd Dt2
+// Both end with the power-of-two normalisation of the result (exact); the log2 of the factor is added to a running total.
+//
+// cluster_marginal: the half-products HL (left step at the cell) and HR (right step at the cell) give
+//   X[(l,d),(u,r)] = sum_{t',b} HL[(l,d),(t',b)] HR[(u,r),(t',b)]                 M = bl pd,  N = pu br,  K = Dt2 Db
+// and one workgroup gathers P[s] = sum_{l,u} F[s,l,u] X[l,dmap[s],u,rmap[s]], applies the negative-probability rule of
+// tn_calc_pn and normalises.  log2 of the raw sum plus the two environments' running totals is the row contraction.
+#include "../../include/tnpeps.h"
+#include "common.h"
+
+namespace tn {
+
+int normalize_pow2(hipStream_t, double*, int64_t, double*, void*, int64_t);
+
+static inline int64_t up256m(int64_t b) { return align_up(b, 256); }
+constexpr int64_t NF_SCRATCH = 8192 + 256;          // normalize_pow2 scratch + the [nf, 1/nf] pair
+
+struct Env3Plan {
+    int64_t half, y, wp;                  // doubles: first product, second product, permuted W (side 1)
+    int64_t g1, g2, g3;                   // split-K scratch of the three GEMMs
+};
+
+static Env3Plan env3_plan(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2) {
+    Env3Plan p;
+    if (side == 0) {
+        p.half = bl * pd * Dt2 * Db;
+        p.y = br * Dt2 * Db * pu;
+        p.wp = 0;
+        p.g1 = gemm_ws_bytes(pd * Dt2, Db, Dt, bl);
+        p.g2 = gemm_ws_bytes(Dt2 * Db, pu, bl * pd, br);
+        p.g3 = gemm_ws_bytes(br * Dt2, Db2, Db * pu, 1);
+    } else {
+        p.half = pu * br * Dt2 * Db;
+        p.y = bl * pd * Dt2 * Db;
+        p.wp = bl * pd * pu * br;
+        p.g1 = gemm_ws_bytes(br * Dt2, Db, Db2, pu);
+        p.g2 = gemm_ws_bytes(bl * pd, Dt2 * Db, pu * br, 1);
+        p.g3 = gemm_ws_bytes(Dt, Db, pd * Dt2, bl);
+    }
+    return p;
+}
+
+static int64_t env3_ws(const Env3Plan& p) {
+    int64_t g = p.g1 > p.g2 ? p.g1 : p.g2;
+    g = g > p.g3 ? g : p.g3;
+    return up256m(p.half * 8) + up256m(p.y * 8) + up256m(p.wp * 8) + up256m(g) + NF_SCRATCH;
+}
+
+static bool dims_ok(int64_t a, int64_t b, int64_t c, int64_t d, int64_t e, int64_t f, int64_t g, int64_t h) {
+    return a >= 1 && b >= 1 && c >= 1 && d >= 1 && e >= 1 && f >= 1 && g >= 1 && h >= 1;
+}
+
+// W[l][d][r][u] -> Wp[l][d][u][r]
+__global__ __launch_bounds__(256) void mpo_swap_ru_kernel(const double* __restrict__ W, int64_t nld, int br, int pu, double* __restrict__ Wp) {
+    const int64_t n = nld * br * pu;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int64_t ld = e / (br * pu);
+        const int rem = (int)(e - ld * br * pu), r = rem / pu, u = rem - r * pu;
+        Wp[(ld * pu + u) * br + r] = W[e];
+    }
+}
+
+// acc_out = acc_in + log2(nf): nf is an exact power of two (2^-1023 stands for an all-zero input, as in tn_nfactor)
+__global__ void log2_acc_kernel(const double* __restrict__ nf2, const double* __restrict__ acc_in, double* __restrict__ acc_out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) acc_out[0] = (acc_in ? acc_in[0] : 0.0) + (double)ilogb(nf2[0]);
+}
+
+int64_t env3_ws_bytes(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2) {
+    if ((side != 0 && side != 1) || !dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2)) return 0;
+    return env3_ws(env3_plan(side, Dt, pd, Dt2, bl, br, pu, Db, Db2));
+}
+
+int env3(hipStream_t st, int side, const double* E, const double* At, const double* W, const double* Ab, int64_t Dt, int64_t pd, int64_t Dt2,
+         int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out, double* log2nf_out,
+         double* half_out, void* ws, int64_t ws_bytes) {
+    TN_CHECK_ARG(side == 0 || side == 1, "side must be 0 (left step) or 1 (right step)");
+    TN_CHECK_ARG(E && At && W && Ab && out && log2nf_out && ws, "null operand");
+    TN_CHECK_ARG(dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2), "non-positive dimension");
+    const Env3Plan p = env3_plan(side, Dt, pd, Dt2, bl, br, pu, Db, Db2);
+    TN_CHECK_ARG(ws_bytes >= env3_ws(p), "workspace too small");
+    char* w = (char*)ws;
+    double* H = (double*)w;
+    w += up256m(p.half * 8);
+    if (half_out) H = half_out;
+    double* Y = (double*)w;
+    w += up256m(p.y * 8);
+    double* Wp = (double*)w;
+    w += up256m(p.wp * 8);
+    double* g = (double*)w;
+    int64_t gb = p.g1 > p.g2 ? p.g1 : p.g2;
+    gb = gb > p.g3 ? gb : p.g3;
+    w += up256m(gb);
+    double* nf2 = (double*)w;
+    void* scratch = w + 256;
+    int rc;
+    if (side == 0) {
+        // HL_l[(d,t'), b] = At^T[(d,t'), t] . EL_l[t, b]
+        if ((rc = gemm(st, pd * Dt2, Db, Dt, 1.0, At, 1, pd * Dt2, E, Db, 1, 0.0, H, Db, 1, bl, 0, Dt * Db, pd * Dt2 * Db,
+                       p.g1 > 0 ? g : nullptr, p.g1))) return rc;
+        // Y_r[(t',b), u] = HL^T[(t',b), (l,d)] . W_r[(l,d), u]
+        if ((rc = gemm(st, Dt2 * Db, pu, bl * pd, 1.0, H, 1, Dt2 * Db, W, br * pu, 1, 0.0, Y, pu, 1, br, 0, pu, Dt2 * Db * pu,
+                       p.g2 > 0 ? g : nullptr, p.g2))) return rc;
+        // EL'[(r,t'), b'] = Y[(r,t'), (b,u)] . Ab[(b,u), b']
+        if ((rc = gemm(st, br * Dt2, Db2, Db * pu, 1.0, Y, Db * pu, 1, Ab, Db2, 1, 0.0, out, Db2, 1, 1, 0, 0, 0, p.g3 > 0 ? g : nullptr, p.g3)))
+            return rc;
+        if ((rc = normalize_pow2(st, out, br * Dt2 * Db2, nf2, scratch, 8192))) return rc;
+    } else {
+        // HR_u[(r,t'), b] = ER[(r,t'), b'] . Ab_u[b', b]     (Ab_u[b', b] = Ab[b, u, b'])
+        if ((rc = gemm(st, br * Dt2, Db, Db2, 1.0, E, Db2, 1, Ab, 1, pu * Db2, 0.0, H, Db, 1, pu, 0, Db2, br * Dt2 * Db,
+                       p.g1 > 0 ? g : nullptr, p.g1))) return rc;
+        const int64_t nw = bl * pd * pu * br;
+        int64_t nbk = cdiv(nw, 256);
+        if (nbk > 1024) nbk = 1024;
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(mpo_swap_ru_kernel, dim3((unsigned)nbk), dim3(256), 0, st, W, bl * pd, (int)br, (int)pu, Wp));
+        TN_CHECK_LAUNCH("mpo_swap_ru_kernel");
+        // Y[(l,d), (t',b)] = W'[(l,d), (u,r)] . HR[(u,r), (t',b)]
+        if ((rc = gemm(st, bl * pd, Dt2 * Db, pu * br, 1.0, Wp, pu * br, 1, H, Dt2 * Db, 1, 0.0, Y, Dt2 * Db, 1, 1, 0, 0, 0,
+                       p.g2 > 0 ? g : nullptr, p.g2))) return rc;
+        // ER_l[t, b] = At[t, (d,t')] . Y_l[(d,t'), b]
+        if ((rc = gemm(st, Dt, Db, pd * Dt2, 1.0, At, pd * Dt2, 1, Y, Db, 1, 0.0, out, Db, 1, bl, 0, pd * Dt2 * Db, Dt * Db,
+                       p.g3 > 0 ? g : nullptr, p.g3))) return rc;
+        if ((rc = normalize_pow2(st, out, bl * Dt * Db, nf2, scratch, 8192))) return rc;
+    }
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(log2_acc_kernel, dim3(1), dim3(64), 0, st, nf2, log2nf_in, log2nf_out));
+    TN_CHECK_LAUNCH("log2_acc_kernel");
+    return 0;
+}
+
+// ---- cell marginal -----------------------------------------------------------------------------------------------------
+constexpr int64_t CM_QMAX = 16384;       // LDS holds the q entries of the table
+
+__device__ __forceinline__ double cm_block_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (tid < k) red[tid] += red[tid + k];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ double cm_block_min(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (tid < k) red[tid] = fmin(red[tid], red[tid + k]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// one workgroup: wave w gathers the states s = w, w+4, ..., its lanes split the (l,u) sum
+__global__ __launch_bounds__(256) void cluster_marginal_kernel(const double* __restrict__ X, const double* __restrict__ F,
+                                                               const int32_t* __restrict__ dmap, const int32_t* __restrict__ rmap, int q,
+                                                               int nl, int pd, int br, int nu, const double* __restrict__ log2L,
+                                                               const double* __restrict__ log2R, double* __restrict__ P,
+                                                               double* __restrict__ minP, double* __restrict__ log2z) {
+    extern __shared__ double sP[];
+    __shared__ double red[256];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nlu = nl * nu;
+    for (int s = wv; s < q; s += 4) {
+        const int d = dmap[s], r = rmap[s];
+        double acc = 0.0;
+        if (d >= 0 && d < pd && r >= 0 && r < br) {
+            const double* f = F + (int64_t)s * nlu;
+            for (int e = lane; e < nlu; e += 64) {
+                const int l = e / nu, u = e - l * nu;
+                acc += f[e] * X[(((int64_t)l * pd + d) * nu + u) * br + r];
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (lane == 0) sP[s] = acc;
+    }
+    __syncthreads();
+    double mn = 1.7e308, part = 0.0;
+    for (int s = tid; s < q; s += 256) { mn = fmin(mn, sP[s]); part += sP[s]; }
+    const double raw = cm_block_sum(part, red);
+    double mPn = cm_block_min(mn, red);
+    if (mPn < 0.0) {                                   // the rule of tn_calc_pn (reference tnac4o.py:1796-1799)
+        const double a = fabs(mPn);
+        double cnt = 0.0;
+        for (int s = tid; s < q; s += 256)
+            if (sP[s] < a) { sP[s] = a; cnt += 1.0; }
+        mPn *= cm_block_sum(cnt, red);
+    }
+    part = 0.0;
+    for (int s = tid; s < q; s += 256) part += sP[s];
+    const double no = cm_block_sum(part, red);
+    if (no > 0.0) {
+        const double inv = 1.0 / no;
+        for (int s = tid; s < q; s += 256) P[s] = sP[s] * inv;
+        mPn *= inv;
+    } else {                                           // all zeros -> uniform, flag -1 (as tn_calc_pn)
+        for (int s = tid; s < q; s += 256) P[s] = sP[s] + 1.0 / (double)q;
+        mPn = -1.0;
+    }
+    if (tid == 0) {
+        minP[0] = mPn;
+        log2z[0] = log2(raw) + (log2L ? log2L[0] : 0.0) + (log2R ? log2R[0] : 0.0);
+    }
+}
+
+int64_t cluster_marginal_ws_bytes(int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
+    if (!dims_ok(bl, pd, br, pu, K, 1, 1, 1)) return 0;
+    return up256m(bl * pd * pu * br * 8) + up256m(gemm_ws_bytes(bl * pd, pu * br, K, 1));
+}
+
+int cluster_marginal(hipStream_t st, const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
+                     int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* P,
+                     double* minP, double* log2z, void* ws, int64_t ws_bytes) {
+    TN_CHECK_ARG(HL && HR && F && dmap && rmap && P && minP && log2z && ws, "null operand");
+    TN_CHECK_ARG(dims_ok(q, bl, pd, br, pu, K, 1, 1), "non-positive dimension");
+    TN_CHECK_ARG(q <= CM_QMAX, "more than 16384 cell states");
+    TN_CHECK_ARG(ws_bytes >= cluster_marginal_ws_bytes(bl, pd, br, pu, K), "workspace too small");
+    double* X = (double*)ws;
+    const int64_t gb = gemm_ws_bytes(bl * pd, pu * br, K, 1);
+    double* g = (double*)((char*)ws + up256m(bl * pd * pu * br * 8));
+    int rc;
+    // X[(l,d), (u,r)] = HL[(l,d), K] . HR[(u,r), K]^T
+    if ((rc = gemm(st, bl * pd, pu * br, K, 1.0, HL, K, 1, HR, 1, K, 0.0, X, pu * br, 1, 1, 0, 0, 0, gb > 0 ? g : nullptr, gb))) return rc;
+    const size_t lds = (size_t)q * 8;
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)cluster_marginal_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(cluster_marginal_kernel, dim3(1), dim3(256), lds, st, X, F, dmap, rmap, (int)q, (int)bl,
+                                                     (int)pd, (int)br, (int)pu, log2L, log2R, P, minP, log2z));
+    TN_CHECK_LAUNCH("cluster_marginal_kernel");
+    return 0;
+}
+
+}  // namespace tn
+
+using namespace tn;
+
+extern "C" {
+
+int64_t tn_env3_ws_bytes(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2) {
+    return env3_ws_bytes(side, Dt, pd, Dt2, bl, br, pu, Db, Db2);
+}
+
+int tn_env3(int side, const double* E, const double* At, const double* W, const double* Ab, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl,
+            int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out, double* log2nf_out, double* half_out,
+            void* ws, int64_t ws_bytes, void* stream) {
+    return env3((hipStream_t)stream, side, E, At, W, Ab, Dt, pd, Dt2, bl, br, pu, Db, Db2, log2nf_in, out, log2nf_out, half_out, ws, ws_bytes);
+}
+
+int64_t tn_cluster_marginal_ws_bytes(int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
+    return cluster_marginal_ws_bytes(bl, pd, br, pu, K);
+}
+
+int tn_cluster_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t bl,
+                        int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* P, double* minP,
+                        double* log2z, void* ws, int64_t ws_bytes, void* stream) {
+    return cluster_marginal((hipStream_t)stream, HL, HR, F, dmap, rmap, q, bl, pd, br, pu, K, log2L, log2R, P, minP, log2z, ws, ws_bytes);
+}
+
+}  // extern "C"

@@ -833,3 +833,56 @@ def mpo_from_factor(F, dmap, rmap, pd, br):
     W = torch.empty((nl, pd, br, nu), dtype=torch.float64, device=F.device)
     check(lib().tn_mpo_from_factor(F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, nl, nu, pd, br, W.data_ptr(), _stream()))
     return W
+
+
+# ---- thermal cluster marginals (csrc/marginal.hip) -----------------------------------------------------------------------
+def env3(side, E, At, W, Ab, log2nf_in=None, keep_half=False):
+    """One three-layer environment step of a row between its boundaries (tn_env3).  At (Dt, pd, Dt2) site of rhoT[ny+1],
+    W (bl, pd, br, pu) row-MPO site, Ab (Db, pu, Db2) site of rhoB[ny].  side 0: E = EL (bl, Dt, Db) -> EL' (br, Dt2, Db2);
+    side 1: E = ER (br, Dt2, Db2) -> ER (bl, Dt, Db).  The result is nfactor-normalised; returns (out, log2nf) with log2nf the
+    device scalar log2nf_in + log2(nfactor), and with keep_half also the step's first product (HL (bl, pd, Dt2, Db) for side 0,
+    HR (pu, br, Dt2, Db) for side 1), the half of the cell marginal that tn_cluster_marginal consumes."""
+    Dt, pd, Dt2 = At.shape
+    bl, pd2, br, pu = W.shape
+    Db, pu2, Db2 = Ab.shape
+    assert pd2 == pd and pu2 == pu, (At.shape, W.shape, Ab.shape)
+    assert tuple(E.shape) == ((bl, Dt, Db) if side == 0 else (br, Dt2, Db2)), (side, E.shape)
+    for t in (E, At, W, Ab):
+        _need_gpu(t)
+        assert t.is_contiguous()
+    dev = At.device
+    out = torch.empty((br, Dt2, Db2) if side == 0 else (bl, Dt, Db), dtype=torch.float64, device=dev)
+    lg = torch.empty(1, dtype=torch.float64, device=dev)
+    half = None
+    if keep_half:
+        half = torch.empty((bl, pd, Dt2, Db) if side == 0 else (pu, br, Dt2, Db), dtype=torch.float64, device=dev)
+    wsb = _ws_query('tn_env3_ws_bytes', side, Dt, pd, Dt2, bl, br, pu, Db, Db2)
+    ws = workspace(wsb, 1)
+    check(lib().tn_env3(side, E.data_ptr(), At.data_ptr(), W.data_ptr(), Ab.data_ptr(), Dt, pd, Dt2, bl, br, pu, Db, Db2,
+                        log2nf_in.data_ptr() if log2nf_in is not None else None, out.data_ptr(), lg.data_ptr(),
+                        half.data_ptr() if half is not None else None, ws.data_ptr(), wsb, _stream()))
+    return (out, lg, half) if keep_half else (out, lg)
+
+
+def cluster_marginal(HL, HR, F, dmap, rmap, log2L=None, log2R=None):
+    """Marginal of one cell from the half-products of env3 at that cell (tn_cluster_marginal).  Returns device tensors
+    (P (q,), minP (1,), log2z (1,)): P normalised after the negative-probability rule of calc_pn, minP its relative magnitude
+    (<= 0), log2z the log2 of the row contraction <rhoB|row|rhoT> when log2L / log2R are the environments' running log2 factors."""
+    bl, pd, Dt2, Db = HL.shape
+    pu, br, Dt2b, Dbb = HR.shape
+    q, nl, nu = F.shape
+    assert (Dt2b, Dbb) == (Dt2, Db) and (nl, nu) == (bl, pu), (HL.shape, HR.shape, F.shape)
+    for t in (HL, HR, F, dmap, rmap):
+        assert t.is_contiguous() and t.is_cuda
+    assert dmap.dtype == torch.int32 and rmap.dtype == torch.int32 and dmap.numel() == q and rmap.numel() == q
+    dev = HL.device
+    P = torch.empty(q, dtype=torch.float64, device=dev)
+    mP = torch.empty(1, dtype=torch.float64, device=dev)
+    lz = torch.empty(1, dtype=torch.float64, device=dev)
+    K = Dt2 * Db
+    wsb = _ws_query('tn_cluster_marginal_ws_bytes', bl, pd, br, pu, K)
+    ws = workspace(wsb, 1)
+    check(lib().tn_cluster_marginal(HL.data_ptr(), HR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, bl, pd, br, pu, K,
+                                    log2L.data_ptr() if log2L is not None else None, log2R.data_ptr() if log2R is not None else None,
+                                    P.data_ptr(), mP.data_ptr(), lz.data_ptr(), ws.data_ptr(), wsb, _stream()))
+    return P, mP, lz

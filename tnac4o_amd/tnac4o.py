@@ -110,6 +110,26 @@ def _merge_groups(inv, Eng, prob, deg, min_dEng, canonical=True):
     return indn, degn, probn, order, starts
 
 
+def model_marginals(P_rot, order, ind0=None, L=None):
+    """Cell marginals of a (possibly rotated) lattice in model order, and the magnetisations they imply (host side of
+    calculate_marginals).  P_rot[c] is the marginal of cell c of the rotated lattice (row-major); model cell k sits at rotated
+    cell order[k] and keeps its state encoding.  With ind0 (the model's active spins per cell, Ising) and L, also
+    m_i = sum_s P_k(s) sigma_i(s) with sigma = +1 where binary_states writes 1; inactive spins get 0.  Returns (marginals, m)
+    with m None when ind0 is None."""
+    marg = [np.asarray(P_rot[int(c)], dtype=np.float64) for c in order]
+    if ind0 is None:
+        return marg, None
+    m = np.zeros(L)
+    k = 0
+    for row in ind0:
+        for act in row:
+            act = np.asarray(act, dtype=np.int64)
+            if act.size:
+                m[act] = marg[k] @ _spins(act.size)
+            k += 1
+    return marg, m
+
+
 def load(file_name):
     """Load a solution written by `tnac4o.save` -- by this package or by the reference (same .npy pickle of a dict,
     tnac4o.py:31-75).  Couplings are not stored, so the returned instance only carries the results (energy, states, ...)
@@ -888,6 +908,68 @@ class tnac4o:
         self.discarded_probability = 0
         self.negative_probability = min(globalmin, 0)
         return Eng
+
+    # ------------------------------------------------------------------------------------ thermal marginals (GPU)
+    def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
+        """Boltzmann marginal of every cell and magnetisation of every spin at the solver's beta, from both boundary MPS.
+        Each row is contracted between rhoB[ny] and rhoT[ny+1] with one cell left open (tn_env3 / tn_cluster_marginal): exact
+        up to the truncation of the boundaries.  Stores and returns `marginals` (a list over model cells, k = ny*Nx + nx, of
+        float64 vectors over the cell's states in the encoding of `states[:, k]`); stores `magnetization` (L,) (Ising; None for
+        RMF), `marginals_negative` (<= 0, the negative-probability measure of search_ground_state) and `marginal_row_log2`
+        (Ny, Nx) in the rotated frame: log2 of each row's contraction, the same for every cell of a row.  Leaves the search
+        results, gauges and rotation alone; rebuilds rhoT and rhoB."""
+        kw = dict(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        self.logger.info('Marginals with beta = %.2f', self.beta)
+        self._setup_rhoT(**kw)
+        self._setup_rhoB(**kw)
+        P_rot, minP, log2z = self._marginal_pass()
+        self.marginal_row_log2 = log2z
+        self.marginals_negative = min(float(minP.min()), 0.0)
+        if self.mode == 'Ising':
+            self.marginals, self.magnetization = model_marginals(P_rot, self.order, self.ind0, self.L)
+        else:
+            self.marginals, self.magnetization = model_marginals(P_rot, self.order)[0], None
+        return self.marginals
+
+    def _marginal_pass(self):
+        """Cell marginals of the rotated lattice from rhoT / rhoB as they stand.  Per row: right environments (and their
+        half-products) from the right end, then the left sweep with each cell's marginal.  One read-back at the end.
+        Returns (list of per-cell vectors, row-major; minP (Ny*Nx,); log2 row contractions (Ny, Nx))."""
+        Nx, Ny = self.Nx, self.Ny
+        dev = self.rhoT[0].A[0].device
+        one = torch.ones((1, 1, 1), dtype=torch.float64, device=dev)
+        zero = torch.zeros(1, dtype=torch.float64, device=dev)
+        Ps, mPs, lzs = [], [], []
+        for ny in range(Ny):
+            top, bot = self.rhoT[ny + 1].A, self.rhoB[ny].A
+            fac = self._peps_factors_dev([(ny, nx) for nx in range(Nx)])
+            Ws = [ops.mpo_from_factor(F, dm, rm, pd, br) for (F, dm, rm, pd, br) in fac]
+            At = [a.contiguous() for a in top]
+            Ab = [a.contiguous() for a in bot]
+            ER, lgR, HR = one, zero, [None] * Nx
+            lgRs = [None] * (Nx + 1)
+            lgRs[Nx] = zero
+            for nx in range(Nx - 1, -1, -1):
+                ER, lgR, HR[nx] = ops.env3(1, ER, At[nx], Ws[nx], Ab[nx], lgR, keep_half=True)
+                lgRs[nx] = lgR
+            EL, lgL = one, zero
+            for nx in range(Nx):
+                F, dm, rm, _, _ = fac[nx]
+                ELn, lgLn, HL = ops.env3(0, EL, At[nx], Ws[nx], Ab[nx], lgL, keep_half=True)
+                P, mP, lz = ops.cluster_marginal(HL, HR[nx], F, dm, rm, lgL, lgRs[nx + 1])
+                HR[nx] = None
+                Ps.append(P)
+                mPs.append(mP)
+                lzs.append(lz)
+                EL, lgL = ELn, lgLn
+        flat = torch.cat(Ps + mPs + lzs).cpu().numpy()
+        sizes = [int(p.numel()) for p in Ps]
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        P_rot = [flat[offs[i]:offs[i + 1]].copy() for i in range(len(Ps))]
+        n = len(Ps)
+        minP = flat[offs[-1]:offs[-1] + n].copy()
+        log2z = flat[offs[-1] + n:offs[-1] + 2 * n].reshape(Ny, Nx).copy()
+        return P_rot, minP, log2z
 
     # ------------------------------------------------------------------------------------ output
     def binary_states(self, number=-1):
