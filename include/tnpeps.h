@@ -313,6 +313,16 @@ int64_t tn_cluster_marginal_ws_bytes(int64_t bl, int64_t pd, int64_t br, int64_t
 int tn_cluster_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t bl,
                         int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* P, double* minP,
                         double* log2z, void* ws, int64_t ws_bytes, void* stream);
+/* Nearest-neighbour bond marginals of one cell (tnac4o.calculate_correlations), same operands and X as tn_cluster_marginal:
+ *   Pl (q, bl)[s,l] = sum_u F[s,l,u] X[l,dmap[s],u,rmap[s]] / T,   Pu (q, pu)[s,u] = sum_l F[s,l,u] X[l,dmap[s],u,rmap[s]] / T
+ * row-major fp64, T = sum_{s,l,u} F X the raw total of both (no negative-probability rule: sums stay exact); l and u carry the
+ * left and the upper neighbour's bond index, so Pl / Pu are the joint laws of the cell with those neighbours.  minB =
+ * min(0, smallest entry of either table); an all-zero T gives uniform tables and minB = -1.  *log2z = log2(T) + *log2L + *log2R,
+ * as tn_cluster_marginal.  dmap / rmap entries out of range contribute 0.  q <= 16384.  No counterpart in the reference. */
+int64_t tn_cluster_bond_marginal_ws_bytes(int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K);
+int tn_cluster_bond_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
+                             int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* Pl,
+                             double* Pu, double* minB, double* log2z, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- measurement: bracket every launch of the selected kernel families with HIP events on the launch stream.
  * family ids: 0-3 gemm_kernel<128,128> / <128,32> / <32,128> / <64,64> (all operand layouts), 4 splitk_reduce,

@@ -85,6 +85,8 @@ SIGNATURES = {
     'tn_env3': (_int, [_int] + [_ptr] * 4 + [_i64] * 8 + [_ptr] * 5 + [_i64, _ptr]),
     'tn_cluster_marginal_ws_bytes': (_i64, [_i64] * 5),
     'tn_cluster_marginal': (_int, [_ptr] * 5 + [_i64] * 6 + [_ptr] * 6 + [_i64, _ptr]),
+    'tn_cluster_bond_marginal_ws_bytes': (_i64, [_i64] * 6),
+    'tn_cluster_bond_marginal': (_int, [_ptr] * 5 + [_i64] * 6 + [_ptr] * 7 + [_i64, _ptr]),
     'tn_profile_enable': (None, [C.c_uint]),
     'tn_profile_reset': (None, []),
     'tn_profile_sample': (None, [C.c_uint]),
@@ -180,9 +182,10 @@ SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes
                'tn_normalize_pow2', 'tn_scale_phys', 'tn_calc_pn', 'tn_nfactor_batched', 'tn_env_rr_batched', 'tn_env_rl_batched',
                'tn_balance', 'tn_merge_groups', 'tn_svdvals_async', 'tn_rar', 'tn_rar_ws_bytes', 'tn_env_mix', 'tn_env_mix_ws_bytes',
                'tn_apply_truncation', 'tn_apply_truncation_ws_bytes', 'tn_site_qr_ws_bytes', 'tn_gram_weights', 'tn_argsort_desc', 'tn_weighted_sum', 'tn_rows_norm2', 'tn_gather_scale_rows', 'tn_peps_factor', 'tn_mpo_from_factor', 'tn_env3', 'tn_env3_ws_bytes',
-               'tn_cluster_marginal', 'tn_cluster_marginal_ws_bytes', 'tn_last_error')
+               'tn_cluster_marginal', 'tn_cluster_marginal_ws_bytes', 'tn_cluster_bond_marginal', 'tn_cluster_bond_marginal_ws_bytes',
+               'tn_last_error')
 _lib = None
-ABI_VERSION = 10         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
+ABI_VERSION = 11         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
 
 
 def lib():

@@ -76,7 +76,7 @@ using namespace tn;
 
 extern "C" {
 
-int tn_version(void) { return 10; }
+int tn_version(void) { return 11; }
 
 #ifndef TN_SRC_HASH
 #define TN_SRC_HASH "unknown"

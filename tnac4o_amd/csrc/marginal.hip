@@ -21,6 +21,10 @@
 //   X[(l,d),(u,r)] = sum_{t',b} HL[(l,d),(t',b)] HR[(u,r),(t',b)]                 M = bl pd,  N = pu br,  K = Dt2 Db
 // and one workgroup gathers P[s] = sum_{l,u} F[s,l,u] X[l,dmap[s],u,rmap[s]], applies the negative-probability rule of
 // tn_calc_pn and normalises.  log2 of the raw sum plus the two environments' running totals is the row contraction.
+//
+// cluster_bond_marginal (tnac4o.calculate_correlations): the same X, and the same products left unsummed over one bond:
+//   Pl[s,l] = sum_u F[s,l,u] X[l,dmap[s],u,rmap[s]],   Pu[s,u] = sum_l F[s,l,u] X[l,dmap[s],u,rmap[s]]
+// one workgroup per state, then one workgroup divides both tables by T = sum Pl (no negativity rule: the sums stay exact).
 #include "../../include/tnpeps.h"
 #include "common.h"
 
@@ -251,6 +255,108 @@ int cluster_marginal(hipStream_t st, const double* HL, const double* HR, const d
     return 0;
 }
 
+// ---- nearest-neighbour bond marginals ----------------------------------------------------------------------------------
+// Pl[s,l] = sum_u F[s,l,u] X[l,dmap[s],u,rmap[s]] and Pu[s,u] = sum_l (the same products): the joint law of the cell's state
+// with its left and with its upper bond index.  Launch 1 spreads the states over the device (one workgroup per state); launch 2
+// is one workgroup that normalises both tables by the same total.
+
+// one workgroup per state s.  The (l,u) plane is walked in tiles of TL rows x TU columns, TU = min(pu, 256), one product per
+// lane; a tile goes through LDS, lanes t < TL add up its rows (the u sums of Pl) and lanes t < TU its columns (the l sums of
+// Pu).  Every table entry has one owning lane and a fixed summation order.
+__global__ __launch_bounds__(256) void bond_gather_kernel(const double* __restrict__ X, const double* __restrict__ F,
+                                                          const int32_t* __restrict__ dmap, const int32_t* __restrict__ rmap, int nl,
+                                                          int pd, int br, int nu, double* __restrict__ Pl, double* __restrict__ Pu) {
+    __shared__ double tile[256];
+    const int s = blockIdx.x, t = threadIdx.x;
+    const int d = dmap[s], r = rmap[s];
+    const bool ok = d >= 0 && d < pd && r >= 0 && r < br;
+    const int TU = nu < 256 ? nu : 256, TL = 256 / TU;
+    const int i = t / TU, j = t - i * TU;
+    const double* f = F + (int64_t)s * nl * nu;
+    double* pl = Pl + (int64_t)s * nl;
+    double* pu = Pu + (int64_t)s * nu;
+    for (int u0 = 0; u0 < nu; u0 += TU) {
+        const int u = u0 + j;
+        double cacc = 0.0;
+        for (int l0 = 0; l0 < nl; l0 += TL) {
+            const int l = l0 + i;
+            double v = 0.0;
+            if (ok && i < TL && l < nl && u < nu) v = f[(int64_t)l * nu + u] * X[(((int64_t)l * pd + d) * nu + u) * br + r];
+            tile[t] = v;
+            __syncthreads();
+            if (t < TL && l0 + t < nl) {
+                double racc = 0.0;
+                for (int c = 0; c < TU; ++c) racc += tile[t * TU + c];
+                pl[l0 + t] = u0 == 0 ? racc : pl[l0 + t] + racc;
+            }
+            if (t < TU)
+                for (int c = 0; c < TL; ++c) cacc += tile[c * TU + t];
+            __syncthreads();
+        }
+        if (t < TU && u < nu) pu[u] = cacc;
+    }
+}
+
+// one workgroup: T = sum of the raw Pl, both tables divided by it, the smallest entry, log2 of the row contraction
+__global__ __launch_bounds__(256) void bond_finish_kernel(const double* __restrict__ Rl, const double* __restrict__ Ru, int64_t nlq,
+                                                          int64_t nuq, const double* __restrict__ log2L, const double* __restrict__ log2R,
+                                                          double* __restrict__ Pl, double* __restrict__ Pu, double* __restrict__ minB,
+                                                          double* __restrict__ log2z) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double part = 0.0;
+    for (int64_t e = tid; e < nlq; e += 256) part += Rl[e];
+    const double raw = cm_block_sum(part, red);
+    double mn = 0.0;
+    if (raw > 0.0) {
+        const double inv = 1.0 / raw;
+        for (int64_t e = tid; e < nlq; e += 256) { const double v = Rl[e] * inv; Pl[e] = v; mn = fmin(mn, v); }
+        for (int64_t e = tid; e < nuq; e += 256) { const double v = Ru[e] * inv; Pu[e] = v; mn = fmin(mn, v); }
+        mn = cm_block_min(mn, red);
+    } else {                                           // all zeros -> uniform, flag -1 (as cluster_marginal_kernel)
+        for (int64_t e = tid; e < nlq; e += 256) Pl[e] = 1.0 / (double)nlq;
+        for (int64_t e = tid; e < nuq; e += 256) Pu[e] = 1.0 / (double)nuq;
+        mn = -1.0;
+    }
+    if (tid == 0) {
+        minB[0] = mn;
+        log2z[0] = log2(raw) + (log2L ? log2L[0] : 0.0) + (log2R ? log2R[0] : 0.0);
+    }
+}
+
+int64_t cluster_bond_marginal_ws_bytes(int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
+    if (!dims_ok(q, bl, pd, br, pu, K, 1, 1)) return 0;
+    return cluster_marginal_ws_bytes(bl, pd, br, pu, K) + up256m(q * bl * 8) + up256m(q * pu * 8);
+}
+
+int cluster_bond_marginal(hipStream_t st, const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap,
+                          int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R,
+                          double* Pl, double* Pu, double* minB, double* log2z, void* ws, int64_t ws_bytes) {
+    TN_CHECK_ARG(HL && HR && F && dmap && rmap && Pl && Pu && minB && log2z && ws, "null operand");
+    TN_CHECK_ARG(dims_ok(q, bl, pd, br, pu, K, 1, 1), "non-positive dimension");
+    TN_CHECK_ARG(q <= CM_QMAX, "more than 16384 cell states");
+    TN_CHECK_ARG(ws_bytes >= cluster_bond_marginal_ws_bytes(q, bl, pd, br, pu, K), "workspace too small");
+    char* w = (char*)ws;
+    double* X = (double*)w;
+    w += up256m(bl * pd * pu * br * 8);
+    const int64_t gb = gemm_ws_bytes(bl * pd, pu * br, K, 1);
+    double* g = (double*)w;
+    w += up256m(gb);
+    double* Rl = (double*)w;
+    w += up256m(q * bl * 8);
+    double* Ru = (double*)w;
+    int rc;
+    // X[(l,d), (u,r)] = HL[(l,d), K] . HR[(u,r), K]^T      (as cluster_marginal)
+    if ((rc = gemm(st, bl * pd, pu * br, K, 1.0, HL, K, 1, HR, 1, K, 0.0, X, pu * br, 1, 1, 0, 0, 0, gb > 0 ? g : nullptr, gb))) return rc;
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(bond_gather_kernel, dim3((unsigned)q), dim3(256), 0, st, X, F, dmap, rmap, (int)bl,
+                                                     (int)pd, (int)br, (int)pu, Rl, Ru));
+    TN_CHECK_LAUNCH("bond_gather_kernel");
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(bond_finish_kernel, dim3(1), dim3(256), 0, st, Rl, Ru, q * bl, q * pu, log2L, log2R,
+                                                     Pl, Pu, minB, log2z));
+    TN_CHECK_LAUNCH("bond_finish_kernel");
+    return 0;
+}
+
 }  // namespace tn
 
 using namespace tn;
@@ -275,6 +381,17 @@ int tn_cluster_marginal(const double* HL, const double* HR, const double* F, con
                         int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* P, double* minP,
                         double* log2z, void* ws, int64_t ws_bytes, void* stream) {
     return cluster_marginal((hipStream_t)stream, HL, HR, F, dmap, rmap, q, bl, pd, br, pu, K, log2L, log2R, P, minP, log2z, ws, ws_bytes);
+}
+
+int64_t tn_cluster_bond_marginal_ws_bytes(int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
+    return cluster_bond_marginal_ws_bytes(q, bl, pd, br, pu, K);
+}
+
+int tn_cluster_bond_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
+                             int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* Pl,
+                             double* Pu, double* minB, double* log2z, void* ws, int64_t ws_bytes, void* stream) {
+    return cluster_bond_marginal((hipStream_t)stream, HL, HR, F, dmap, rmap, q, bl, pd, br, pu, K, log2L, log2R, Pl, Pu, minB, log2z, ws,
+                                 ws_bytes);
 }
 
 }  // extern "C"

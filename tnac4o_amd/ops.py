@@ -886,3 +886,30 @@ def cluster_marginal(HL, HR, F, dmap, rmap, log2L=None, log2R=None):
                                     log2L.data_ptr() if log2L is not None else None, log2R.data_ptr() if log2R is not None else None,
                                     P.data_ptr(), mP.data_ptr(), lz.data_ptr(), ws.data_ptr(), wsb, _stream()))
     return P, mP, lz
+
+
+def cluster_bond_marginal(HL, HR, F, dmap, rmap, log2L=None, log2R=None):
+    """Nearest-neighbour bond marginals of one cell from the half-products of env3 at that cell (tn_cluster_bond_marginal).
+    Returns device tensors (Pl (q, bl), Pu (q, pu), minB (1,), log2z (1,)): Pl[s,l] / Pu[s,u] the joint law of the cell's state
+    with its left / upper bond index, both divided by the same raw total (no negative-probability rule), minB = min(0, smallest
+    entry), log2z the log2 of the row contraction as cluster_marginal."""
+    bl, pd, Dt2, Db = HL.shape
+    pu, br, Dt2b, Dbb = HR.shape
+    q, nl, nu = F.shape
+    assert (Dt2b, Dbb) == (Dt2, Db) and (nl, nu) == (bl, pu), (HL.shape, HR.shape, F.shape)
+    for t in (HL, HR, F, dmap, rmap):
+        assert t.is_contiguous() and t.is_cuda
+    assert dmap.dtype == torch.int32 and rmap.dtype == torch.int32 and dmap.numel() == q and rmap.numel() == q
+    dev = HL.device
+    Pl = torch.empty((q, bl), dtype=torch.float64, device=dev)
+    Pu = torch.empty((q, pu), dtype=torch.float64, device=dev)
+    mB = torch.empty(1, dtype=torch.float64, device=dev)
+    lz = torch.empty(1, dtype=torch.float64, device=dev)
+    K = Dt2 * Db
+    wsb = _ws_query('tn_cluster_bond_marginal_ws_bytes', q, bl, pd, br, pu, K)
+    ws = workspace(wsb, 1)
+    check(lib().tn_cluster_bond_marginal(HL.data_ptr(), HR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, bl, pd, br, pu,
+                                         K, log2L.data_ptr() if log2L is not None else None,
+                                         log2R.data_ptr() if log2R is not None else None, Pl.data_ptr(), Pu.data_ptr(), mB.data_ptr(),
+                                         lz.data_ptr(), ws.data_ptr(), wsb, _stream()))
+    return Pl, Pu, mB, lz

@@ -130,6 +130,76 @@ def model_marginals(P_rot, order, ind0=None, L=None):
     return marg, m
 
 
+def model_correlations(Pl_rot, Pu_rot, order, Nx, Ny, J0=None, ind=None, ir=None, idn=None, keys=None, Nx_model=None):
+    """Nearest-neighbour correlations in the model frame from the bond tables of a (possibly rotated) lattice (host side of
+    calculate_correlations).  Pl_rot[c] (q, bl) / Pu_rot[c] (q, pu) is the joint law of rotated cell c (row-major, Nx x Ny) with
+    its left / upper bond index; model cell k sits at rotated cell order[k] and keeps its state encoding, so rotated spin
+    c*Nc + a is model spin order_i[c]*Nc + a.
+      Ising (J0, the model's couplings, and the rotated frame's ind, ir, id): returns (bond_pairs (n, 2) int64, C (n,)) for every
+      off-diagonal J0[i, j] != 0, i < j, sorted; C = <sigma_i sigma_j> with sigma = +1 where binary_states writes 1.  Intra-cell
+      pairs come from the cell law p[s] = sum_l Pl[s, l].
+      RMF (keys, the rotated frame's two-cell factor keys, and Nx_model): returns {model key: P[s1, s2]} with s1 the state of the
+      key's first cell; the model key is the rotated key mapped back through order, i.e. the key as the model gave it."""
+    order = np.asarray(order, dtype=np.int64)
+    order_i = np.empty_like(order)
+    order_i[order] = np.arange(order.size)
+
+    def table(c1, c2):                  # P[s1, s2] of two neighbouring rotated cells, from the table at the right / lower one
+        (y1, x1), (y2, x2) = divmod(c1, Nx), divmod(c2, Nx)
+        if y1 == y2 and x2 == x1 + 1:
+            return Pl_rot[c2].T
+        if y1 == y2 and x1 == x2 + 1:
+            return Pl_rot[c1]
+        if x1 == x2 and y2 == y1 + 1:
+            return Pu_rot[c2].T
+        if x1 == x2 and y1 == y2 + 1:
+            return Pu_rot[c1]
+        raise ValueError('cells %d and %d of the rotated lattice are not nearest neighbours' % (c1, c2))
+
+    if J0 is None:
+        out = {}
+        for key in keys:
+            if len(key) != 4:
+                continue
+            c1, c2 = key[0] * Nx + key[1], key[2] * Nx + key[3]
+            k1, k2 = int(order_i[c1]), int(order_i[c2])
+            mkey = divmod(k1, Nx_model) + divmod(k2, Nx_model)
+            out[mkey] = np.ascontiguousarray(table(c1, c2), dtype=np.float64)
+        return out
+    Nc = J0.shape[0] // (Nx * Ny)
+
+    def model(x):
+        return int(order_i[x // Nc]) * Nc + x % Nc
+
+    C = {}
+
+    def put(spins_a, spins_b, M):
+        for a, i in enumerate(spins_a):
+            for b, j in enumerate(spins_b):
+                if i != j:
+                    C[tuple(sorted((model(int(i)), model(int(j)))))] = float(M[a, b])
+
+    for ny in range(Ny):
+        for nx in range(Nx):
+            c = ny * Nx + nx
+            here = np.asarray(ind[ny][nx], dtype=np.int64)
+            S = _spins(here.size)
+            Pl = np.asarray(Pl_rot[c])
+            p = Pl.sum(1)
+            put(here, here, S.T @ (p[:, None] * S))
+            if nx > 0 and len(ir[ny][nx - 1]):
+                left = np.asarray(ind[ny][nx - 1])[ir[ny][nx - 1]]
+                put(here, left, S.T @ Pl @ _spins(left.size))
+            if ny > 0 and len(idn[ny - 1][nx]):
+                up = np.asarray(ind[ny - 1][nx])[idn[ny - 1][nx]]
+                put(here, up, S.T @ np.asarray(Pu_rot[c]) @ _spins(up.size))
+    pairs = np.argwhere(np.triu(J0, 1) != 0).astype(np.int64)
+    missing = [tuple(p) for p in pairs if tuple(int(v) for v in p) not in C]
+    if missing:
+        raise ValueError('couplings between cells that are not nearest neighbours: %s' % missing[:4])
+    return pairs, np.array([C[(int(i), int(j))] for i, j in pairs], dtype=np.float64)
+
+
 def load(file_name):
     """Load a solution written by `tnac4o.save` -- by this package or by the reference (same .npy pickle of a dict,
     tnac4o.py:31-75).  Couplings are not stored, so the returned instance only carries the results (energy, states, ...)
@@ -970,6 +1040,88 @@ class tnac4o:
         minP = flat[offs[-1]:offs[-1] + n].copy()
         log2z = flat[offs[-1] + n:offs[-1] + 2 * n].reshape(Ny, Nx).copy()
         return P_rot, minP, log2z
+
+    # ------------------------------------------------------------------------------------ thermal correlations (GPU)
+    def calculate_correlations(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
+        """Nearest-neighbour correlations and the mean energy at the solver's beta, from both boundary MPS.  Each row is
+        contracted between rhoB[ny] and rhoT[ny+1] with one cell left open, keeping the cell's state jointly with its left and
+        upper bond index (tn_cluster_bond_marginal): exact up to the truncation of the boundaries.
+          Ising: stores `bond_pairs` (n, 2), the model spins i < j of every off-diagonal J0[i, j] != 0 (sorted), and
+          `correlations` (n,), <sigma_i sigma_j> with sigma = +1 where binary_states writes 1; returns `correlations`.
+          RMF: stores `pair_marginals`, {two-cell factor key of the model: P[s1, s2] in the key's order}; returns it.
+        Both store `energy_mean` (<E> in the convention of `energy`), `correlations_negative` (<= 0, the smallest table entry)
+        and `correlation_row_log2` (Ny, Nx) in the rotated frame (log2 of each row's contraction, as marginal_row_log2).
+        Leaves the search results, marginals, gauges and rotation alone; rebuilds rhoT and rhoB."""
+        kw = dict(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        self.logger.info('Correlations with beta = %.2f', self.beta)
+        self._setup_rhoT(**kw)
+        self._setup_rhoB(**kw)
+        Pl, Pu, minB, log2z = self._correlation_pass()
+        self.correlation_row_log2 = log2z
+        self.correlations_negative = min(float(minB.min()), 0.0)
+        self.energy_mean = self._bond_energy(Pl, Pu)
+        if self.mode == 'Ising':
+            self.bond_pairs, self.correlations = model_correlations(Pl, Pu, self.order, self.Nx, self.Ny, J0=self.J0, ind=self.ind,
+                                                                    ir=self.ir, idn=self.id)
+            self.pair_marginals = None
+            return self.correlations
+        self.pair_marginals = model_correlations(Pl, Pu, self.order, self.Nx, self.Ny, keys=list(self.J['fac']), Nx_model=self.Nx_model)
+        self.bond_pairs = self.correlations = None
+        return self.pair_marginals
+
+    def _bond_energy(self, Pl, Pu):
+        """<E> = sum_k [sum_s p_k Es_k + sum_{s,l} Pl_k E1_k + sum_{s,u} Pu_k E4_k] from the bond tables of the rotated frame
+        (p_k[s] = sum_l Pl_k[s, l]); the energy tables are those of _cell_energies, unshifted and unscaled (host)."""
+        Em = 0.0
+        for ny in range(self.Ny):
+            for nx in range(self.Nx):
+                c = ny * self.Nx + nx
+                Es, E1, E4 = self._cell_energies(ny, nx)
+                Em += float(Pl[c].sum(1) @ Es) + float(np.sum(Pl[c] * E1)) + float(np.sum(Pu[c] * E4))
+        return Em
+
+    def _correlation_pass(self):
+        """Bond tables of the rotated lattice from rhoT / rhoB as they stand: the environments and half-products of
+        _marginal_pass, tn_cluster_bond_marginal per cell, one read-back at the end.  Returns (Pl list (q, bl), Pu list (q, pu),
+        row-major over cells; minB (Ny*Nx,); log2 row contractions (Ny, Nx))."""
+        Nx, Ny = self.Nx, self.Ny
+        dev = self.rhoT[0].A[0].device
+        one = torch.ones((1, 1, 1), dtype=torch.float64, device=dev)
+        zero = torch.zeros(1, dtype=torch.float64, device=dev)
+        Pls, Pus, mBs, lzs = [], [], [], []
+        for ny in range(Ny):
+            top, bot = self.rhoT[ny + 1].A, self.rhoB[ny].A
+            fac = self._peps_factors_dev([(ny, nx) for nx in range(Nx)])
+            Ws = [ops.mpo_from_factor(F, dm, rm, pd, br) for (F, dm, rm, pd, br) in fac]
+            At = [a.contiguous() for a in top]
+            Ab = [a.contiguous() for a in bot]
+            ER, lgR, HR = one, zero, [None] * Nx
+            lgRs = [None] * (Nx + 1)
+            lgRs[Nx] = zero
+            for nx in range(Nx - 1, -1, -1):
+                ER, lgR, HR[nx] = ops.env3(1, ER, At[nx], Ws[nx], Ab[nx], lgR, keep_half=True)
+                lgRs[nx] = lgR
+            EL, lgL = one, zero
+            for nx in range(Nx):
+                F, dm, rm, _, _ = fac[nx]
+                ELn, lgLn, HL = ops.env3(0, EL, At[nx], Ws[nx], Ab[nx], lgL, keep_half=True)
+                Pl, Pu, mB, lz = ops.cluster_bond_marginal(HL, HR[nx], F, dm, rm, lgL, lgRs[nx + 1])
+                HR[nx] = None
+                Pls.append(Pl)
+                Pus.append(Pu)
+                mBs.append(mB)
+                lzs.append(lz)
+                EL, lgL = ELn, lgLn
+        flat = torch.cat([t.reshape(-1) for t in Pls + Pus] + mBs + lzs).cpu().numpy()
+        out, off = [], 0
+        for t in Pls + Pus:
+            n = int(t.numel())
+            out.append(flat[off:off + n].reshape(tuple(t.shape)).copy())
+            off += n
+        n = len(Pls)
+        minB = flat[off:off + n].copy()
+        log2z = flat[off + n:off + 2 * n].reshape(Ny, Nx).copy()
+        return out[:n], out[n:], minB, log2z
 
     # ------------------------------------------------------------------------------------ output
     def binary_states(self, number=-1):
