@@ -252,7 +252,9 @@ int tn_site_qr(int side, double* A, int64_t Dl, int64_t p, int64_t Dr, const dou
  * counterpart in the reference, whose first pass factors every site in full, mps.py:187):
  * tn_gram_weights: from the Gram matrix G (n x n) of the unfactored part on the other side of a bond, the squared weight of
  *   every bond index, d2[c] = max(G_cc, floor_rel max G), and stats65 = [ 64 partial sums of ||K||_F^2 with K = G / (d d^T) (to be
- *   added in order: reproducible bit for bit), max_c G_cc ].
+ *   added in order: reproducible bit for bit), max_c G_cc ].  Precondition: max_c G_cc > 0 (the chain's G is the Gram matrix of a
+ *   nonzero state).  An all-zero G is not rejected (that would take a read-back): it yields d2 = 0, stats65[64] = 0 -- the sign a caller
+ *   tests -- and NaN partial sums for the parts that hold rows.
  * tn_rows_norm2: out[r] = sum_c A[r,c]^2 for a row-major rows x cols matrix.
  * tn_gather_scale_rows: inverse = 0: out[j,:] = sqrt(w2[perm[j]]) A[perm[j],:];  inverse = 1: out[perm[j],:] = A[j,:] / sqrt(w2[perm[j]])
  *   (perm: int64 device vector). */
