@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 12 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -78,19 +78,14 @@ int tn_absorb(const double* A, const double* W, double* out, int64_t Dl, int64_t
  * back; once it is <= rank_tol x the largest column norm of A the factorisation stops and *keff_host (HOST) receives
  * the number of columns of Q / rows of R produced (A = Q[:, :keff] R[:keff, :] to rank_tol * max column norm).  With
  * rank_tol = 2^-56 this drops exactly the rows the Jacobi SVD (tn_svd_trunc) would deflate.  Synchronises the stream
- * at each check.  *keff_host = min(m, n) otherwise.
- * aux_stream (a second hipStream_t owned by the caller, or NULL): look-ahead.  The device-filling part of every trailing update
- * is enqueued on aux_stream while `stream` goes on factoring the next panel (a chain of latency-bound single-workgroup kernels);
- * the two are ordered by events inside the call, and on return all work the result depends on is ordered before anything
- * enqueued on `stream` afterwards.  Results are bit-identical with and without it (same kernels on the same data). */
+ * at each check.  *keff_host = min(m, n) otherwise. */
 int tn_qr(double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R,
-          int64_t rrs, int64_t rcs, int nb, double rank_tol, int64_t* keff_host, void* ws, int64_t ws_bytes, void* stream,
-          void* aux_stream);
+          int64_t rrs, int64_t rcs, int nb, double rank_tol, int64_t* keff_host, void* ws, int64_t ws_bytes, void* stream);
 int64_t tn_qr_ws_bytes(int64_t m, int64_t n, int nb);
 /* The panel step of tn_qr on its own (test and measurement hook): Y (nrows x b, b <= 32) <- an orthonormal basis of the column
  * space of the panel X (read only, must not overlap Y; completed arbitrarily where X is rank deficient).
- * method 0: iterated Cholesky-QR with deferral (csrc/cholqr.hip, what tn_qr uses); 1: Householder TSQR (csrc/tsqr.hip).
- * state9_host / dev_host (both or neither; method 0; synchronises the stream): {ticket counter, done, final_next, passes applied,
+ * method must be 0: iterated Cholesky-QR with deferral (csrc/cholqr.hip, what tn_qr uses); other values are rejected.
+ * state9_host / dev_host (both or neither; synchronises the stream): {ticket counter, done, final_next, passes applied,
  * input exponent, refill mask, deferred pivots, refilled columns, Householder fallback taken} and max|X^T X - I| before each pass.
  * tn_panel_stats_stream: DIAGNOSTIC counters of the panels launched on `stream` since its last reset (the library keeps them per
  * stream, so that concurrent chains do not mix their counts; streams beyond the 64th share one slot); tn_panel_stats: their sum
@@ -328,7 +323,7 @@ int tn_cluster_bond_marginal(const double* HL, const double* HR, const double* F
 
 /* ---- measurement: bracket every launch of the selected kernel families with HIP events on the launch stream.
  * family ids: 0-3 gemm_kernel<128,128> / <128,32> / <32,128> / <64,64> (all operand layouts), 4 splitk_reduce,
- * 5 absorb, 6 gram_partial, 7 eig_small, 8 rows_times_small, 9 small_t_times_vecs, 10 tsqr_factor/apply,
+ * 5 absorb, 6 gram_partial, 7 eig_small, 8 rows_times_small, 9 small_t_times_vecs, 10 panel step (cholqr.hip, smallqr.hip),
  * 11 lu_reconstruct, 12 QR auxiliaries (diag_qr, assemble_R, init_Q, norms, copies), 13 SVD auxiliaries (norms, init,
  * gather), 14 misc (nfactor, scaling, builders, beam kernels).
  * mask bit f enables family f.  tn_profile_get synchronises the recorded events and returns totals since the last

@@ -36,14 +36,15 @@ expect_neg(L.tn_absorb(P, P, P, 1, 1, 1, 1, 1, 1, 1, 0, -2, 0, 0, 0, None), 'tn_
 expect_neg(L.tn_qr_batched(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 32, 0.0, None, 3, 32, 32, 16, P, 16, None, None, 0), 'tn_qr_batched ws')
 expect_neg(L.tn_qr_batched(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 32, 0.0, None, 3, 32, 32, 16, P, 1 << 24, None, None, 9), 'tn_qr_batched sides')
 expect_neg(L.tn_svd_trunc_batched(P, 4, 1, 4, 4, 4, 0.0, P, 4, 1, P, P, 4, 1, None, None, None, None, 2, 16, 16, 4, 16, P, 1 << 20, None), 'tn_svd_trunc_batched keep')
-expect_neg(L.tn_qr(P, 4, 1, 0, 4, P, 4, 1, P, 4, 1, 32, 0.0, None, P, 1 << 20, None, None), 'tn_qr empty')
-expect_neg(L.tn_qr(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 48, 0.0, None, P, 1 << 20, None, None), 'tn_qr bad nb')
-expect_neg(L.tn_qr(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 32, 0.0, None, P, 16, None, None), 'tn_qr small ws')
-expect_neg(L.tn_qr(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 32, 2.0, None, P, 1 << 20, None, None), 'tn_qr rank_tol')
+expect_neg(L.tn_qr(P, 4, 1, 0, 4, P, 4, 1, P, 4, 1, 32, 0.0, None, P, 1 << 20, None), 'tn_qr empty')
+expect_neg(L.tn_qr(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 48, 0.0, None, P, 1 << 20, None), 'tn_qr bad nb')
+expect_neg(L.tn_qr(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 32, 0.0, None, P, 16, None), 'tn_qr small ws')
+expect_neg(L.tn_qr(P, 4, 1, 8, 4, P, 4, 1, P, 4, 1, 32, 2.0, None, P, 1 << 20, None), 'tn_qr rank_tol')
 expect_neg(L.tn_panel_orth(None, 4, 1, 64, 4, P, 4, 1, 0, None, None, P, 1 << 20, None), 'tn_panel_orth null')
 expect_neg(L.tn_panel_orth(P, 4, 1, 64, 4, P, 4, 1, 2, None, None, P, 1 << 20, None), 'tn_panel_orth method')
+expect_neg(L.tn_panel_orth(P, 4, 1, 64, 4, C.cast(C.byref(host, 8), C.c_void_p), 4, 1, 1, None, None, P, 1 << 20, None), 'tn_panel_orth method 1')
 expect_neg(L.tn_panel_orth(P, 4, 1, 64, 4, P, 4, 1, 0, None, None, P, 16, None), 'tn_panel_orth ws')
-expect_neg(L.tn_panel_orth(P, 40, 1, 64, 40, C.cast(C.byref(host, 8), C.c_void_p), 40, 1, 1, None, None, P, 1 << 22, None), 'tn_panel_orth width')
+expect_neg(L.tn_panel_orth(P, 40, 1, 64, 40, C.cast(C.byref(host, 8), C.c_void_p), 40, 1, 0, None, None, P, 1 << 22, None), 'tn_panel_orth width')
 expect_neg(L.tn_panel_stats(None, 0), 'tn_panel_stats null')
 expect_neg(L.tn_panel_stats_stream(None, 0, None), 'tn_panel_stats_stream null')
 expect_neg(L.tn_smallqr_stats(None, 0, None), 'tn_smallqr_stats null')

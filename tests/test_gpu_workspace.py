@@ -144,7 +144,7 @@ def test_qr_workspace(L, ops, m, n, nb, rank_tol, nbo, rank):
     def call(b, ws, wsb_):
         T = Ad.clone()                                           # (consumed)
         keff = ct.c_int64(k)
-        rc = L.tn_qr(T.data_ptr(), n, 1, m, n, b['Q'].ptr, k, 1, b['R'].ptr, n, 1, nb, rank_tol, ct.byref(keff), ws, wsb_, _st(), None)
+        rc = L.tn_qr(T.data_ptr(), n, 1, m, n, b['Q'].ptr, k, 1, b['R'].ptr, n, 1, nb, rank_tol, ct.byref(keff), ws, wsb_, _st())
         return rc, int(keff.value)
 
     def written(name, a, keff):
@@ -169,7 +169,7 @@ def test_qr_workspace(L, ops, m, n, nb, rank_tol, nbo, rank):
 
 # ------------------------------------------------------------------------------------------------------------------ tn_panel_orth
 @pytest.mark.parametrize('nrows,b', [(1, 1), (33, 32), (65, 7), (1000, 32), (4097, 31)])
-@pytest.mark.parametrize('method', (0, 1))
+@pytest.mark.parametrize('method', (0,))
 def test_panel_orth_workspace(L, ops, nrows, b, method):
     X = np.random.default_rng(nrows + b + method).standard_normal((nrows, b))
     Xd = dev(X)

@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libtnpeps.so')
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['api.hip', 'gemm_f64.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'tsqr.hip', 'cholqr.hip', 'smallqr.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip']
+SOURCES = ['api.hip', 'gemm_f64.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip']
 
 _i64, _f64, _int, _ptr = C.c_int64, C.c_double, C.c_int, C.c_void_p
 
@@ -23,7 +23,7 @@ SIGNATURES = {
     'tn_gemm_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'tn_absorb': (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _i64, _i64, _i64, _i64, _ptr]),
     'tn_qr': (_int, [_ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _i64, _int, _f64, C.POINTER(_i64), _ptr, _i64,
-              _ptr, _ptr]),
+              _ptr]),
     'tn_qr_ws_bytes': (_i64, [_i64, _i64, _int]),
     'tn_panel_orth_ws_bytes': (_i64, [_i64, _int]),
     'tn_panel_orth': (_int, [_ptr, _i64, _i64, _i64, _int, _ptr, _i64, _i64, _int, C.POINTER(_int), C.POINTER(_f64), _ptr, _i64, _ptr]),
@@ -185,7 +185,7 @@ SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes
                'tn_cluster_marginal', 'tn_cluster_marginal_ws_bytes', 'tn_cluster_bond_marginal', 'tn_cluster_bond_marginal_ws_bytes',
                'tn_last_error')
 _lib = None
-ABI_VERSION = 11         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
+ABI_VERSION = 12         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
 
 
 def lib():

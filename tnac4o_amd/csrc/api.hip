@@ -19,11 +19,6 @@ const char* get_error() { return g_err; }
 // implemented in the other translation units
 int absorb(hipStream_t, const double*, const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t,
            int64_t, int64_t, int64_t);
-int qr_factor(hipStream_t, double*, int64_t, int64_t, int64_t, int64_t, double*, int64_t, int64_t, double*, int64_t, int64_t, int,
-              void*, int64_t, double, int64_t*, hipStream_t, double* dropped2_host = nullptr, int frob_exit = 0,
-              int64_t* pivot_perm_host = nullptr, double* nf_out2 = nullptr,
-              int* nf_done = nullptr);
-int64_t qr_ws_bytes(int64_t, int64_t, int);
 int svd_trunc(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*,
               double*, int64_t, int64_t, int64_t*, double*, int*, int*, void*, int64_t);
 int svd_vals(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*, int*, int*, void*, int64_t);
@@ -76,7 +71,7 @@ using namespace tn;
 
 extern "C" {
 
-int tn_version(void) { return 11; }
+int tn_version(void) { return 12; }
 
 #ifndef TN_SRC_HASH
 #define TN_SRC_HASH "unknown"
@@ -156,13 +151,13 @@ int tn_absorb(const double* A, const double* W, double* out, int64_t Dl, int64_t
 }
 
 int tn_qr(double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R, int64_t rrs,
-          int64_t rcs, int nb, double rank_tol, int64_t* keff_host, void* ws, int64_t ws_bytes, void* stream, void* aux_stream) {
+          int64_t rcs, int nb, double rank_tol, int64_t* keff_host, void* ws, int64_t ws_bytes, void* stream) {
     TN_CHECK_ARG(A && Q && R && ws, "null operand");
     TN_CHECK_ARG(rank_tol >= 0.0 && rank_tol < 1.0, "rank_tol out of range");
     ProfPhase ph(PH_QR);
     const double dm = (double)m, dn = (double)(n < m ? n : m);
     prof_note(PROF_QR_NOMINAL, 1, 4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn, 8.0 * (2.0 * dm * dn + dn * dn));
-    return qr_factor(ST, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, (hipStream_t)aux_stream);
+    return qr_factor(ST, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host);
 }
 int64_t tn_qr_ws_bytes(int64_t m, int64_t n, int nb) { return qr_ws_bytes(m, n, nb); }
 
@@ -178,17 +173,14 @@ int tn_fused_timeouts(int* count_host, void* stream) {
     return fused_timeouts(ST, count_host);
 }
 
-int64_t tn_panel_orth_ws_bytes(int64_t nrows, int b) {
-    const int64_t a = tsqr_ws_bytes(nrows, b), c = cholqr_ws_bytes(nrows, b);
-    return a > c ? a : c;
-}
+int64_t tn_panel_orth_ws_bytes(int64_t nrows, int b) { return cholqr_ws_bytes(nrows, b); }
 int tn_panel_orth(const double* X, int64_t rs, int64_t cs, int64_t nrows, int b, double* Y, int64_t yrs, int64_t ycs, int method,
                   int* state9_host, double* dev_host, void* ws, int64_t ws_bytes, void* stream) {
     TN_CHECK_ARG(X && Y && ws, "null operand");
-    TN_CHECK_ARG(method == 0 || method == 1, "method must be 0 (Cholesky-QR) or 1 (Householder TSQR)");
+    TN_CHECK_ARG(method == 0, "method must be 0 (Cholesky-QR)");
+    TN_CHECK_ARG(b >= 1 && b <= 32, "panel width must be <= 32");
     TN_CHECK_ARG(ws_bytes >= tn_panel_orth_ws_bytes(nrows, b), "workspace too small");
     ProfPhase ph(PH_QR);
-    if (method == 1) return tsqr_orthonormalize(ST, X, rs, cs, Y, yrs, ycs, nrows, b, ws, ws_bytes);
     int rc = cholqr_reset(ST, ws);
     if (rc) return rc;
     int fbase = 0;

@@ -11,11 +11,6 @@
 
 namespace tn {
 
-int qr_factor(hipStream_t, double*, int64_t, int64_t, int64_t, int64_t, double*, int64_t, int64_t, double*, int64_t, int64_t, int,
-              void*, int64_t, double, int64_t*, hipStream_t, double* dropped2_host = nullptr, int frob_exit = 0,
-              int64_t* pivot_perm_host = nullptr, double* nf_out2 = nullptr,
-              int* nf_done = nullptr);
-int64_t qr_ws_bytes(int64_t, int64_t, int);
 int svd_trunc(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*,
               double*, int64_t, int64_t, int64_t*, double*, int*, int*, void*, int64_t);
 int svd_vals(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*, int*, int*, void*, int64_t);
@@ -65,7 +60,7 @@ int qr_batched(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int
         for (int64_t i = 0; i < batch && rc == 0; ++i) {
             hipStream_t si = used > 0 ? (hipStream_t)side[i % used] : st;
             rc = qr_factor(si, A + i * bsA, rs, cs, m, n, Q + i * bsQ, qrs, qcs, R + i * bsR, rrs, rcs, nb, (char*)ws + i * wsi, wsi, rank_tol,
-                           keff_host ? keff_host + i : nullptr, nullptr);
+                           keff_host ? keff_host + i : nullptr);
         }
     }
     for (int s = 0; s < used; ++s) {      // join even after an error so that the caller's stream stays ordered

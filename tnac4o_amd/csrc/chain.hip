@@ -30,10 +30,6 @@ namespace tn {
 // ---- other translation units ----------------------------------------------------------------------------------------------
 int absorb(hipStream_t, const double*, const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t,
            int64_t, int64_t, int64_t);
-int qr_factor(hipStream_t, double*, int64_t, int64_t, int64_t, int64_t, double*, int64_t, int64_t, double*, int64_t, int64_t, int, void*,
-              int64_t, double, int64_t*, hipStream_t, double* dropped2_host = nullptr, int frob_exit = 0, int64_t* pivot_perm_host = nullptr, double* nf_out2 = nullptr,
-              int* nf_done = nullptr);
-int64_t qr_ws_bytes(int64_t, int64_t, int);
 int copy_mat(hipStream_t, const double*, int64_t, int64_t, double*, int64_t, int64_t, int64_t, int64_t);
 int svd_trunc(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*, double*,
               int64_t, int64_t, int64_t*, double*, int*, int*, void*, int64_t);
@@ -533,7 +529,7 @@ public:
         CH(scratch(0, wsb, w));
         int64_t keff = k;
         ProfPhase ph(PH_QR);
-        return qr_factor(st, Tc, n, 1, m, n, Q.p, k, 1, Rm.p, n, 1, 32, w, wsb, 0.0, &keff, nullptr);
+        return qr_factor(st, Tc, n, 1, m, n, Q.p, k, 1, Rm.p, n, 1, 32, w, wsb, 0.0, &keff);
     }
     // U (k x keep, leading dimension o.U.c), S, Vt (keep x n) of the centre matrix Cm
     int svd_trunc_full(const M2& Cm, int64_t Dmax, double tol, SvdOut& o) {

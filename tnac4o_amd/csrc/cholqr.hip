@@ -1,7 +1,7 @@
-// Panel orthonormalisation for the blocked QR (K3), second generation: iterated Cholesky-QR with deferral.
+// Panel orthonormalisation for the blocked QR (K3): iterated Cholesky-QR with deferral.
 //
-// tsqr.hip orthonormalises a tall nrows x b panel (b <= 32) with Householder TSQR: unconditionally stable, but every tree
-// level is a chain of 32 column steps of ~1.3 us in a single workgroup (3 levels x (41 + 22) us for 16384 rows).  Here
+// A Householder TSQR of a tall nrows x b panel (b <= 32) is unconditionally stable, but every tree level is a chain of 32
+// column steps of ~1.3 us in a single workgroup (3 levels x (41 + 22) us for 16384 rows; measured, removed).  Here
 // the serial part shrinks to the Cholesky factorisation of ONE 32 x 32 Gram matrix per pass, done by one wave:
 //
 //   pass 0 (cq_gram_kernel):   G = X^T X    (every workgroup: its 256 rows on the matrix cores; the last workgroup to finish
@@ -21,7 +21,7 @@
 //     exactly what a tau = 0 Householder reflector stands for;
 //   * the panel only has to be an orthonormal basis of span(X): the blocked QR takes R from H^T A (qr.hip), never from here.
 // If the panel is still not orthonormal after CQ_MAXPASS passes, the last workgroup of the last launch redoes it from the
-// untouched input with a plain (slow, single-workgroup) Householder QR: unconditional like tsqr.hip, never seen on the
+// untouched input with a plain (slow, single-workgroup) Householder QR: unconditionally stable, never seen on the
 // contraction path so far (tn_debug_panel_stats counts it).
 //
 // Launches are plain stream-ordered kernels: nothing spins, nothing needs co-residency, so interleaved chains cannot
@@ -1701,34 +1701,34 @@ int cholqr_panel(hipStream_t st, const double* X, int64_t irs, int64_t ics, doub
         fused_note_launch();
         // one launch for the whole chain.  Algorithmic bytes: the panel in, the reflectors (and W, Wq) out -- the tile never
         // leaves LDS in between; flops: Gram + post at launch time, the passes are booked from the device counter (cq_stats[3])
-        prof_begin(st, PROF_TSQR);
+        prof_begin(st, PROF_PANEL);
         hipLaunchKernelGGL(cq_fused_kernel, dim3(nblk), dim3(256), 0, st, X, irs, ics, Y, rs, cs, nrows, b, nblk, part, bexp, topblk, stt,
                            *fused_base, seed, lu, Tp, W, wrs, wcs, Wq, maxpass, slot, spin_limit, gsum, active);
         TN_CHECK_LAUNCH("cq_fused_kernel");
         if (tall) { cq_big_launched(st, slot); big_lock.unlock(); }
         *fused_base += (maxpass + 1) * nblk * (nblk > CQ_SLICE_FROM ? 2 : 1);
         const double e = (double)nrows * b;
-        prof_end(st, PROF_TSQR, (2.0 + (reconstruct ? (Wq ? 6.0 : 4.0) : 0.0)) * e * b, (reconstruct ? (Wq ? 32.0 : 24.0) : 16.0) * e);
+        prof_end(st, PROF_PANEL, (2.0 + (reconstruct ? (Wq ? 6.0 : 4.0) : 0.0)) * e * b, (reconstruct ? (Wq ? 32.0 : 24.0) : 16.0) * e);
         cq_capture(st, X, irs, ics, nrows, b, stt);
         return 0;
     }
-    prof_begin(st, PROF_TSQR);
+    prof_begin(st, PROF_PANEL);
     hipLaunchKernelGGL(cq_gram_kernel, dim3(nblk), dim3(256), 0, st, X, irs, ics, nrows, b, nblk, part, bexp, stt, Rg, slot, active);
     TN_CHECK_LAUNCH("cq_gram_kernel");
-    prof_end(st, PROF_TSQR, 2.0 * nrows * b * b, 8.0 * nrows * b);
+    prof_end(st, PROF_PANEL, 2.0 * nrows * b * b, 8.0 * nrows * b);
     for (int t = 1; t <= maxpass; ++t) {
-        prof_begin(st, PROF_TSQR);
+        prof_begin(st, PROF_PANEL);
         hipLaunchKernelGGL(cq_pass_kernel, dim3(nblk), dim3(256), 0, st, X, irs, ics, Y, rs, cs, nrows, b, nblk, t == 1 ? 1 : 0, t, part, stt,
                            Rg, seed + 0x9E3779B97F4A7C15ULL * (uint64_t)t, lu, Tp, maxpass, slot, active);
         TN_CHECK_LAUNCH("cq_pass_kernel");
         // (the passes that really run are booked from the device counter cq_stats[7] by the caller of tn_panel_stats:
         //  3 n b^2 flops and 16 n b bytes per applied pass; a launch that finds the panel converged moves nothing)
-        prof_end(st, PROF_TSQR, 0.0, 0.0);
+        prof_end(st, PROF_PANEL, 0.0, 0.0);
     }
-    prof_begin(st, PROF_TSQR);
+    prof_begin(st, PROF_PANEL);
     hipLaunchKernelGGL(cq_post_kernel, dim3(nblk), dim3(256), 0, st, X, irs, ics, Y, rs, cs, nrows, b, nblk, stt, lu, Tp, W, wrs, wcs, Wq, active);
     TN_CHECK_LAUNCH("cq_post_kernel");
-    prof_end(st, PROF_TSQR, reconstruct ? (Wq ? 6.0 : 4.0) * nrows * b * b : 0.0, reconstruct ? (Wq ? 32.0 : 24.0) * nrows * b : 0.0);
+    prof_end(st, PROF_PANEL, reconstruct ? (Wq ? 6.0 : 4.0) * nrows * b * b : 0.0, reconstruct ? (Wq ? 32.0 : 24.0) * nrows * b : 0.0);
     cq_capture(st, X, irs, ics, nrows, b, stt);
     return 0;
 }

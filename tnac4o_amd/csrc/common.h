@@ -60,7 +60,8 @@ static __device__ __forceinline__ double fast_rcp(double x) {
 
 // ---- optional event timing per kernel family (prof.hip) ---------------------------------------------
 enum { PROF_GEMM_128x128 = 0, PROF_GEMM_128x32, PROF_GEMM_32x128, PROF_GEMM_64x64, PROF_SPLITK_REDUCE, PROF_ABSORB,
-       PROF_GRAM, PROF_EIG, PROF_ROWS_SMALL, PROF_VECS_SMALL, PROF_TSQR,
+       PROF_GRAM, PROF_EIG, PROF_ROWS_SMALL, PROF_VECS_SMALL,
+       PROF_PANEL,     // panel step of tn_qr (cholqr.hip) and the one-launch factorisation (smallqr.hip)
        PROF_LU,        // lu_reconstruct_kernel (Householder reconstruction of a panel)
        PROF_QR_AUX,    // diag_qr, assemble_R, init_Q, column norms, panel copies
        PROF_SVD_AUX,   // vector norms, init, gather of the Jacobi SVD
@@ -170,10 +171,12 @@ int small_t_times_vecs(hipStream_t st, const double* S, double* X, int64_t vs, i
                        const int* pairs, int ngroups, const int* nrot);
 
 
-// ---- TSQR panel orthonormalisation (tsqr.hip) -------------------------------------------------------------------
-int64_t tsqr_ws_bytes(int64_t nrows, int b);
-int tsqr_orthonormalize(hipStream_t st, const double* Xin, int64_t irs, int64_t ics, double* X, int64_t rs, int64_t cs,
-                        int64_t nrows, int b, void* ws, int64_t ws_bytes);
+// ---- blocked QR (qr.hip): the factorisation behind tn_qr, tn_qr_batched, tn_site_qr and the chain driver -------------
+int qr_factor(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R,
+              int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol, int64_t* keff_host,
+              double* dropped2_host = nullptr, int frob_exit = 0, int64_t* pivot_perm_host = nullptr, double* nf_out2 = nullptr,
+              int* nf_done = nullptr);
+int64_t qr_ws_bytes(int64_t m, int64_t n, int nb);
 
 
 // ---- iterated Cholesky-QR panel orthonormalisation (cholqr.hip), the default panel step -------------------------------

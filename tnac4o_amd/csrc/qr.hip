@@ -335,103 +335,6 @@ __global__ __launch_bounds__(256) void rows_times_small3_kernel(double* __restri
     }
 }
 
-// MFMA form of rows_times_small3 for 32-wide panels: one workgroup per 256 rows computes the (256 x 32) . (32 x 96)
-// product [x S0 | x S1 | x S2] on v_mfma_f64_16x16x4_f64 (wave w owns rows 64w .. 64w+63 = 4 row tiles; its A fragments
-// are read from the LDS tile once and kept in registers, so the tile can stage the three outputs one after the other).
-// Every global access is a coalesced pass over the tile, whatever the operand layout.
-typedef double d4q __attribute__((ext_vector_type(4)));
-
-__global__ __launch_bounds__(256) void rows_times_small3_mfma_kernel(double* __restrict__ X, int64_t rs, int64_t cs, int64_t nrows,
-                                                                     int b, const double* __restrict__ S0,
-                                                                     const double* __restrict__ S1, const double* __restrict__ S2,
-                                                                     double* __restrict__ W1, int64_t w1rs, int64_t w1cs,
-                                                                     double* __restrict__ W2) {
-    constexpr int NB = 32, P = 36;
-    __shared__ double Ss[3][NB * NB];
-    __shared__ double tile[256 * P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // every global load of the prologue is issued before the first one is consumed (one memory round trip)
-    const int64_t r0 = (int64_t)blockIdx.x * 256;
-    const int nr = (int)((nrows - r0 < 256) ? nrows - r0 : 256);
-    const bool xrow = (cs == 1);
-    double sv[3][NB * NB / 256], xv[NB];
-#pragma unroll
-    for (int t = 0; t < NB * NB / 256; ++t) {
-        const int e = tid + 256 * t, i = e / NB, j = e % NB;
-        const bool in = (i < b && j < b);
-        sv[0][t] = in ? S0[i * b + j] : 0.0;
-        sv[1][t] = in ? S1[i * b + j] : 0.0;
-        sv[2][t] = (in && S2) ? S2[i * b + j] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        const int e = tid + 256 * u;
-        const int i = xrow ? e / NB : e % 256, j = xrow ? e % NB : e / 256;
-        xv[u] = (i < nr && j < b) ? X[(r0 + i) * rs + j * cs] : 0.0;
-    }
-#pragma unroll
-    for (int t = 0; t < NB * NB / 256; ++t) {
-        const int e = tid + 256 * t;
-        Ss[0][e] = sv[0][t];
-        Ss[1][e] = sv[1][t];
-        Ss[2][e] = sv[2][t];
-    }
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        const int e = tid + 256 * u;
-        const int i = xrow ? e / NB : e % 256, j = xrow ? e % NB : e / 256;
-        tile[i * P + j] = xv[u];
-    }
-    __syncthreads();
-    const int li = lane & 15, lk = lane >> 4;
-    double fa[4][8];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) fa[mt][ks] = tile[(wave * 64 + mt * 16 + li) * P + ks * 4 + lk];
-    __syncthreads();
-#pragma unroll 1
-    for (int o = 0; o < 3; ++o) {
-        double* dst = (o == 0) ? X : (o == 1) ? W1 : W2;
-        if (dst == nullptr) continue;                    // uniform
-        const int64_t drs = (o == 1) ? w1rs : rs, dcs = (o == 1) ? w1cs : cs;
-        const double* Sm = Ss[o];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            double fb[8];
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) fb[ks] = Sm[(ks * 4 + lk) * NB + nt * 16 + li];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                d4q acc = d4q{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mt][ks], fb[ks], acc, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) tile[(wave * 64 + mt * 16 + lk + 4 * r) * P + nt * 16 + li] = acc[r];
-            }
-        }
-        __syncthreads();
-        const bool drow = (dcs == 1);
-#pragma unroll
-        for (int u0 = 0; u0 < NB; u0 += 8) {             // 8 LDS reads, then 8 stores
-            double ov[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int e = tid + 256 * (u0 + u);
-                const int i = drow ? e / NB : e % 256, j = drow ? e % NB : e / 256;
-                ov[u] = tile[i * P + j];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int e = tid + 256 * (u0 + u);
-                const int i = drow ? e / NB : e % 256, j = drow ? e % NB : e / 256;
-                if (i < nr && j < b) dst[(r0 + i) * drs + j * dcs] = ov[u];
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // ------------------------------------------------------------------------------------------ diagonal blocks
 // One workgroup per diagonal block: Householder QR  D = Z Tri  with diag(Tri) >= 0.
 template <int NB>
@@ -455,7 +358,7 @@ __global__ __launch_bounds__(256) void diag_qr_kernel(const double* __restrict__
     __syncthreads();
     // Householder QR with all 256 threads: thread (c, g) = (tid % NB, tid / NB) owns rows g, g + NG, ... of column c.
     // Per column one pass gives sum_{r>j} a_rj a_rc for every c (partials meet in LDS), from which the reflector and
-    // its action follow (same scheme as tsqr_factor_kernel); entries are first scaled to [0.5,1) by a power of two.
+    // its action follow; entries are first scaled to [0.5,1) by a power of two.
     constexpr int NG = 256 / NB;
     __shared__ double part[256];
     __shared__ double dscale;
@@ -479,8 +382,8 @@ __global__ __launch_bounds__(256) void diag_qr_kernel(const double* __restrict__
         __syncthreads();
     }
     const int c = tid % NB, g = tid / NB;
-    // Fast path: the panel step hands over an orthonormal basis Q1 with span(Q1[:, :j]) = span(panel[:, :j]) (Cholesky-QR and the
-    // Householder TSQR are both triangular orthogonalisations), so the block D = S Q1^T A_panel is upper triangular already, up to
+    // Fast path: the panel step hands over an orthonormal basis Q1 with span(Q1[:, :j]) = span(panel[:, :j]) (Cholesky-QR is a
+    // triangular orthogonalisation), so the block D = S Q1^T A_panel is upper triangular already, up to
     // rounding (|d_ij| <~ eps ||a_j|| below the diagonal).  Then Z = I: dropping entries below 4e-15 of their column's norm is a
     // column-wise backward error of the size every other step of the factorisation makes, and it saves the 2 x 32 serial
     // Householder steps (50 us of pure latency per tn_qr call).  Anything else (64-wide first-generation panels) takes the general path.
@@ -810,29 +713,18 @@ static void dbg_check(hipStream_t st, const double* p, int64_t rs, int64_t cs, i
     fprintf(stderr, "[tn_qr dbg] panel %d it %d %-10s %lldx%lld nonfinite=%d max=%.3e min|.|=%.3e\n", panel, it, what, (long long)m, (long long)n, bad, mx, mn);
 }
 
-// The panel step: iterated Cholesky-QR (cholqr.hip) by default, TN_PANEL=tsqr selects the Householder TSQR (A/B, cross-checks).
-static bool panel_tsqr() {
-    const char* e = getenv("TN_PANEL");                              // read per call: the tests switch it
-    return e && e[0] == 't';
-}
-static int panel_orthonormalize(hipStream_t st, const double* Xin, int64_t irs, int64_t ics, double* X, int64_t rs, int64_t cs, int64_t nrows,
-                                int b, void* ws, int64_t ws_bytes, bool tsqr, uint64_t seed, int* fused_base, void* state) {
-    if (tsqr) return tsqr_orthonormalize(st, Xin, irs, ics, X, rs, cs, nrows, b, ws, ws_bytes);
-    return cholqr_orthonormalize(st, Xin, irs, ics, X, rs, cs, nrows, b, ws, ws_bytes, seed, fused_base, state);
-}
-
 constexpr int QR_NBO_MAX = 256;       // widest outer block of the two-level factorisation
 struct QrWs {
-    double *Y, *Wq, *W, *W2, *UT, *UTq, *gemm_ws2;
+    double *Y, *Wq, *W, *UT, *UTq;
     double *G, *Tblk, *Zo, *Zo2, *tmpT;
-    double *T, *X, *X2, *part, *Js, *Uinv, *Z, *Tri, *gemm_ws, *cn;
+    double *T, *X, *part, *Js, *Uinv, *Z, *Tri, *gemm_ws, *cn;
     int* dead;
     int* pairs;          // swap list of the pivoted panel step (2 nb ints)
     char* piv;           // PivState + int permutation (device-side panel pivoting)
     int64_t gemm_ws_bytes;
-    void* tsqr_ws;
-    int64_t tsqr_bytes;
-    void* cq_state = nullptr;      // the stream's panel state block (cholqr_begin), or NULL = head of tsqr_ws
+    void* panel_ws;      // workspace of the Cholesky-QR panel step (cholqr.hip)
+    int64_t panel_bytes;
+    void* cq_state = nullptr;      // the stream's panel state block (cholqr_begin), or NULL = head of panel_ws
 };
 
 static int64_t qr_layout(int64_t m, int64_t n, int nb, char* base, QrWs* w) {
@@ -842,12 +734,10 @@ static int64_t qr_layout(int64_t m, int64_t n, int nb, char* base, QrWs* w) {
     double* Y = (double*)take(m * k * 8);
     double* Wq = (double*)take(m * k * 8);            // Y T of every panel (Q accumulation)
     double* Wp = (double*)take(m * nb * 8);           // Y T^T of the current panel (trailing update)
-    double* Wp2 = (double*)take(m * nb * 8);          // ... of the next one (look-ahead: the wide update of panel p still reads W_p)
     double* UT = (double*)take((int64_t)nb * nb * 8);
     double* UTq = (double*)take((int64_t)nb * nb * 8);
     double* T = (double*)take(P * nb * nb * 8);
     double* X = (double*)take((int64_t)nb * (n > k ? n : k) * 8);
-    double* X2 = (double*)take((int64_t)nb * (n > k ? n : k) * 8);
     double* part = (double*)take((int64_t)64 * nb * nb * 8);
     double* Js = (double*)take((int64_t)nb * nb * 8);
     double* Uinv = (double*)take((int64_t)nb * nb * 8);
@@ -866,7 +756,6 @@ static int64_t qr_layout(int64_t m, int64_t n, int nb, char* base, QrWs* w) {
         if (g2 > gw) gw = g2;
     }
     double* gws = (double*)take(gw + 256);
-    double* gws2 = (double*)take(gw + 256);           // split-K scratch of the look-ahead stream
     // two-level blocking: Gram of an outer block, its merged T factors (one per block), the two (NBO x n) operands of the
     // outer update and a scratch for the T recurrence
     const int64_t nblk_o = cdiv(k, QR_NBO_MAX / 2);           // enough for the narrowest outer width used (128)
@@ -876,11 +765,11 @@ static int64_t qr_layout(int64_t m, int64_t n, int nb, char* base, QrWs* w) {
     double* Zb2 = (double*)take((int64_t)QR_NBO_MAX * (n > k ? n : k) * 8);
     double* tmpT = (double*)take((int64_t)QR_NBO_MAX * 64 * 8);
     if (w) { w->G = Gm; w->Tblk = Tblk; w->Zo = Zb; w->Zo2 = Zb2; w->tmpT = tmpT; }
-    const int64_t tsb = std::max(tsqr_ws_bytes(m, nb < 32 ? nb : 32), cholqr_ws_bytes(m, nb < 32 ? nb : 32));
-    void* tsw = (void*)take(tsb);
-    if (w) { w->tsqr_ws = tsw; w->tsqr_bytes = tsb; }
-    if (w) { w->Wq = Wq; w->W = Wp; w->W2 = Wp2; w->UT = UT; w->UTq = UTq; w->gemm_ws2 = gws2; }
-    if (w) { w->Y = Y; w->T = T; w->X = X; w->X2 = X2; w->part = part; w->Js = Js; w->Uinv = Uinv; w->Z = Z; w->Tri = Tri;
+    const int64_t pb = cholqr_ws_bytes(m, nb < 32 ? nb : 32);
+    void* pw = (void*)take(pb);
+    if (w) { w->panel_ws = pw; w->panel_bytes = pb; }
+    if (w) { w->Wq = Wq; w->W = Wp; w->UT = UT; w->UTq = UTq; }
+    if (w) { w->Y = Y; w->T = T; w->X = X; w->part = part; w->Js = Js; w->Uinv = Uinv; w->Z = Z; w->Tri = Tri;
              w->dead = dead; w->gemm_ws = gws; w->gemm_ws_bytes = gw; w->cn = cn; w->pairs = pairs; w->piv = piv; }
     return off;
 }
@@ -904,7 +793,7 @@ int64_t qr_ws_bytes(int64_t m, int64_t n, int nb) { return qr_layout(m, n, nb, n
 // truncating passes checks the trailing block after every second panel, which needs it up to date.
 static int qr_two_level(hipStream_t st, Mat Am, int64_t m, int64_t n, int64_t k, Mat Ym, QrWs& w, int nbo, int64_t rs, int64_t cs,
                         int64_t yrs, int64_t ycs, int64_t wrs, int64_t wcs, double* Q, int64_t qrs, int64_t qcs, double* R, int64_t rrs,
-                        int64_t rcs, bool use_tsqr, int* fused_base) {
+                        int64_t rcs, int* fused_base) {
     const int nb = 32;
     int rc;
     const int nblk = (int)cdiv(k, nbo);
@@ -926,26 +815,10 @@ static int qr_two_level(hipStream_t st, Mat Am, int64_t m, int64_t n, int64_t k,
             Mat Ap = sub(Am, j0, j0), Yp = sub(Ym, j0, j0);
             double* Tp = w.T + (int64_t)p * nb * nb;
             Mat Wp = mat(w.W, wrs, wcs);
-            if (!use_tsqr) {
-                // orthonormalisation + Householder reconstruction + the tall products in one chain of launches (cholqr.hip)
-                if ((rc = cholqr_panel(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.tsqr_ws, w.tsqr_bytes, (uint64_t)p + 1, 1, Tp, Wp.p, wrs, wcs,
-                                       nullptr, fused_base, w.cq_state)))
-                    return rc;
-            } else {
-            if ((rc = panel_orthonormalize(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.tsqr_ws, w.tsqr_bytes, use_tsqr, (uint64_t)p + 1, fused_base, w.cq_state))) return rc;
-            // Wq_top goes to a scratch corner of the (otherwise unused here) Wq buffer: only Y, T and W = Y T^T are needed
-            TN_PROF_LAUNCH(st, PROF_LU, hipLaunchKernelGGL((lu_reconstruct_kernel<32>), dim3(1), dim3(256), 0, st, Yp.p, yrs, ycs, b, w.Uinv, Tp, w.UT,
-                               w.UTq, Wp.p, wrs, wcs, w.Wq));
-            TN_CHECK_LAUNCH("lu_reconstruct_kernel");
-            if (mp > b) {
-                dim3 grid((unsigned)cdiv(mp - b, 256));
-                prof_begin(st, PROF_ROWS_SMALL);
-                hipLaunchKernelGGL(rows_times_small3_mfma_kernel, grid, dim3(256), 0, st, sub(Yp, b, 0).p, yrs, ycs, mp - b, b, w.Uinv, w.UT,
-                                   (const double*)nullptr, sub(Wp, b, 0).p, wrs, wcs, (double*)nullptr);
-                TN_CHECK_LAUNCH("rows_times_small3_kernel");
-                prof_end(st, PROF_ROWS_SMALL, 4.0 * (mp - b) * b * b, 24.0 * (mp - b) * b);
-            }
-            }
+            // orthonormalisation + Householder reconstruction + the tall products in one chain of launches (cholqr.hip)
+            if ((rc = cholqr_panel(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.panel_ws, w.panel_bytes, (uint64_t)p + 1, 1, Tp, Wp.p, wrs, wcs,
+                                   nullptr, fused_base, w.cq_state)))
+                return rc;
             Mat Xm = mat(w.X, nin, 1);
             if ((rc = gemm(st, b, nin, mp, 1.0, tr(Yp), Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
             if ((rc = gemm(st, mp, nin, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
@@ -1210,11 +1083,7 @@ __global__ __launch_bounds__(256) void swap_columns_dev_kernel(double* __restric
 #pragma unroll
     for (int i = 0; i < 16; ++i) { const int t = g * 16 + i; if (in && t < ns) row[(int64_t)dst[i] * cs] = v[i]; }
 }
-// Look-ahead (aux != nullptr, nb = 32): the trailing update of panel p is split.  The columns of the next panel (and the
-// panel's own) are updated on the caller's stream, which then factors panel p+1 right away -- a chain of latency-bound
-// single-workgroup kernels -- while the device-filling update of everything to the right of it runs on `aux`.  Ordering:
-// aux waits for panel p's reflectors (ev.panel), the caller's stream waits for the wide update of panel p-1 before it touches
-// the columns of panel p+1 (ev.wide); W = Y T^T and the split-K scratch are double-buffered between the two streams.
+
 // ---- Q accumulation through merged reflectors (round 5) ---------------------------------------------------------------------
 // The single-level paths used to apply every 32-wide reflector to Q on its own: per panel a split-K product Y_p^T Q, its reduction and a
 // rank-32 update -- three launches and three passes over Q[j0:, j0:] per panel, ~35 us each in the pivoted factorisations of the first
@@ -1290,7 +1159,7 @@ __global__ __launch_bounds__(256) void apply_merged_T_kernel(const double* __res
         const int q = NP - 1 - qq;
         if (q >= npan) continue;                                   // (uniform)
         const int r0 = q * 32, kr = bw - r0 - 32;                   // kr: columns of G right of the panel (<= 96; <= 0 for the last one)
-        d4q acc = {zr[q][0], zr[q][1], zr[q][2], zr[q][3]};
+        d4l acc = {zr[q][0], zr[q][1], zr[q][2], zr[q][3]};
         for (int kk = 0; kk < kr; kk += 4) {
             const int k = kk + lk;
             const double a = (k < kr) ? -gs[r0 + 16 * ti + lr][k] : 0.0;
@@ -1300,7 +1169,7 @@ __global__ __launch_bounds__(256) void apply_merged_T_kernel(const double* __res
 #pragma unroll
         for (int r = 0; r < 4; ++r) vs[16 * ti + lk + 4 * r][16 * tj + lr] = acc[r];
         __syncthreads();
-        d4q x = {0.0, 0.0, 0.0, 0.0};
+        d4l x = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int kk = 0; kk < 32; kk += 4) {
             const int k = kk + lk;
@@ -1315,23 +1184,6 @@ __global__ __launch_bounds__(256) void apply_merged_T_kernel(const double* __res
         if (c0 + cc < nq) X[(int64_t)i * nq + c0 + cc] = xs[i][cc];
     }
 }
-
-struct LookaheadEvents {
-    hipEvent_t panel[2] = {nullptr, nullptr}, wide[2] = {nullptr, nullptr};
-    bool ok = false;
-    bool init() {
-        if (ok) return true;
-        for (int i = 0; i < 2; ++i) {
-            if (hipEventCreateWithFlags(&panel[i], hipEventDisableTiming) != hipSuccess) return false;
-            if (hipEventCreateWithFlags(&wide[i], hipEventDisableTiming) != hipSuccess) return false;
-        }
-        return ok = true;
-    }
-    ~LookaheadEvents() {
-        if (!ok) return;
-        for (int i = 0; i < 2; ++i) { (void)hipEventDestroy(panel[i]); (void)hipEventDestroy(wide[i]); }
-    }
-};
 
 // TN_QR_TRACE=1 (diagnostics): every call is timed synchronously with a pair of events and booked under its shape and kind; the
 // table is printed when the process exits.  Perturbs the run (one synchronisation per factorisation).
@@ -1370,11 +1222,11 @@ QrTrace g_qr_trace;
 
 static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
                           int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-                          int64_t* keff_host, hipStream_t aux, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2,
+                          int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2,
                           int* nf_done, bool* input_intact);
 static int qr_factor_traced(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
               int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-              int64_t* keff_host, hipStream_t aux, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done,
+              int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done,
               bool* input_intact);
 
 // nf_out2 != NULL (device, 2 doubles): a path that can divide R by its power-of-two norm factor in the launch that produces it does
@@ -1385,9 +1237,9 @@ static int qr_factor_traced(hipStream_t st, double* A, int64_t rs, int64_t cs, i
 // with -7 (the input was overwritten: the caller must rerun from a copy; the stream no longer takes the single-launch forms).
 int qr_factor(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
               int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-              int64_t* keff_host, hipStream_t aux, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done) {
+              int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done) {
     bool intact = false;
-    int rc = qr_factor_traced(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, aux, dropped2_host, frob_exit,
+    int rc = qr_factor_traced(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host, frob_exit,
                               pivot_perm_host, nf_out2, nf_done, &intact);
     if (fused_check_deferred() || !fused_check_needed()) return rc;
     int gave_up = 0;
@@ -1399,22 +1251,22 @@ int qr_factor(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int6
                   "results are invalid and the input was overwritten -- rerun from a copy (this stream now takes the six-launch panel chain)", gave_up);
         return -7;
     }
-    return qr_factor_traced(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, aux, dropped2_host, frob_exit,
+    return qr_factor_traced(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host, frob_exit,
                             pivot_perm_host, nf_out2, nf_done, &intact);
 }
 
 static int qr_factor_traced(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
               int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-              int64_t* keff_host, hipStream_t aux, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done,
+              int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done,
               bool* input_intact) {
     if (nf_done) *nf_done = 0;
     if (!g_qr_trace.on)
-        return qr_factor_impl(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, aux, dropped2_host, frob_exit,
+        return qr_factor_impl(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host, frob_exit,
                               pivot_perm_host, nf_out2, nf_done, input_intact);
     thread_local hipEvent_t e0 = nullptr, e1 = nullptr;
     if (!e0) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); }
     (void)hipEventRecord(e0, st);
-    const int rc = qr_factor_impl(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, aux, dropped2_host,
+    const int rc = qr_factor_impl(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host,
                                   frob_exit, pivot_perm_host, nf_out2, nf_done, input_intact);
     (void)hipEventRecord(e1, st);
     (void)hipEventSynchronize(e1);
@@ -1434,7 +1286,7 @@ static int qr_factor_traced(hipStream_t st, double* A, int64_t rs, int64_t cs, i
 
 static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
                           int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-                          int64_t* keff_host, hipStream_t aux, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2,
+                          int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2,
                           int* nf_done, bool* input_intact) {
     TN_CHECK_ARG(m >= 1 && n >= 1, "empty matrix");
     if (dropped2_host) *dropped2_host = 0.0;
@@ -1488,32 +1340,20 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
     const int64_t wrs = rowmajor ? nb : 1, wcs = rowmajor ? 1 : m;
     Mat Am = mat(A, rs, cs), Ym = mat(w.Y, yrs, ycs), Wqm = mat(w.Wq, yrs, ycs);
     int rc;
-    const bool use_tsqr = panel_tsqr();
-    if (nb == 32 && !use_tsqr && (rc = cholqr_begin(st, w.tsqr_ws, &w.cq_state))) return rc;
+    if (nb == 32 && (rc = cholqr_begin(st, w.panel_ws, &w.cq_state))) return rc;
     int fbase = 0;                            // arrivals booked by the single-launch panel steps of this call (cholqr.hip)
     {   // two-level blocking for the plain factorisation of matrices with several outer blocks (TN_QR_NBO = 0 disables it)
         const char* e_nbo = getenv("TN_QR_NBO");                      // read per call: the tests switch it
         const int v_nbo = e_nbo ? atoi(e_nbo) : 256, nbo = (v_nbo == 128 || v_nbo == 256) ? v_nbo : 0;
         if (nbo > 0 && nb == 32 && !(rank_tol > 0.0 && keff_host != nullptr) && k >= 2 * nbo && m >= 4 * nbo) {
             if (keff_host) *keff_host = k;
-            return qr_two_level(st, Am, m, n, k, Ym, w, nbo, rs, cs, yrs, ycs, wrs, wcs, Q, qrs, qcs, R, rrs, rcs, use_tsqr, &fbase);
+            return qr_two_level(st, Am, m, n, k, Ym, w, nbo, rs, cs, yrs, ycs, wrs, wcs, Q, qrs, qcs, R, rrs, rcs, &fbase);
         }
     }
-    thread_local LookaheadEvents ev;
-    // worth it only when there is a wide part to overlap with (at least 4 panels) and the panel is tall enough to be slow
-    const bool lookahead = aux != nullptr && aux != st && nb == 32 && P >= 4 && m >= 2048 && ev.init();
-    int wide_pending = -1;                    // parity of the ev.wide event the caller's stream has not waited for yet
     hipError_t he;
-    auto join_wide = [&]() -> int {           // caller's stream waits for the outstanding wide update
-        if (wide_pending >= 0) {
-            if ((he = hipStreamWaitEvent(st, ev.wide[wide_pending], 0)) != hipSuccess) return hip_fail(he, "wait wide update");
-            wide_pending = -1;
-        }
-        return 0;
-    };
     // device-side panel pivoting (see pivot_select_kernel): the host runs one panel ahead of the verdicts it reads back
     const bool piv_dev_on = [] { const char* e = getenv("TN_PIVOT_DEVICE"); return !(e && e[0] == '0'); }();      // (read per call: the tests switch it)
-    const bool piv_dev = pivot && piv_dev_on && n <= PIV_MAXN && !lookahead && !use_tsqr;
+    const bool piv_dev = pivot && piv_dev_on && n <= PIV_MAXN;
     PivState* pst = (PivState*)w.piv;
     int* pperm = (int*)(w.piv + 1024);
     const int* active = piv_dev ? &pst->h.active : nullptr;
@@ -1596,18 +1436,16 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
                 TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(swap_columns_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, A, rs, cs, m, sl));
             TN_CHECK_LAUNCH("swap_columns_kernel");
         }
-        // --- panel orthonormalisation
-        const bool fused_panel = (nb == 32 && !use_tsqr);     // orthonormalisation + reconstruction + tall products in one chain (cholqr.hip)
+        // --- panel orthonormalisation and Householder reconstruction
+        const bool fused_panel = (nb == 32);     // orthonormalisation + reconstruction + tall products in one chain (cholqr.hip)
+        double* Tp = w.T + (int64_t)p * nb * nb;
+        // fused: W_p = Y_p T_p^T of EVERY panel is kept (in the m x k array that holds Y T for nb = 64): besides the trailing update it
+        // serves the Q accumulation, H_p Q = Q - Y_p (W_p^T Q), so Y T is never formed (a third of the panel step's output)
+        Mat Wqp = sub(Wqm, j0, j0), Wp = fused_panel ? Wqp : mat(w.W, wrs, wcs);
         if (fused_panel) {
-            // W_p = Y_p T_p^T of EVERY panel is kept (in the m x k array that holds Y T on the other paths): besides the trailing update it
-            // serves the Q accumulation, H_p Q = Q - Y_p (W_p^T Q), so Y T is never formed (a third of the panel step's output)
-            double* Tpf = w.T + (int64_t)p * nb * nb;
-            Mat Wpf = sub(Wqm, j0, j0);
-            if ((rc = cholqr_panel(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.tsqr_ws, w.tsqr_bytes, (uint64_t)p + 1, 1, Tpf, Wpf.p, yrs, ycs,
+            if ((rc = cholqr_panel(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.panel_ws, w.panel_bytes, (uint64_t)p + 1, 1, Tp, Wp.p, yrs, ycs,
                                    nullptr, &fbase, w.cq_state, active)))
                 return rc;
-        } else if (nb == 32) {
-            if ((rc = panel_orthonormalize(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.tsqr_ws, w.tsqr_bytes, use_tsqr, (uint64_t)p + 1, &fbase, w.cq_state))) return rc;
         } else {
             if ((rc = copy_mat(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b))) return rc;
             const int nchunk = gram_nchunk(mp);
@@ -1628,62 +1466,33 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
                     TN_CHECK_LAUNCH("refill_dead_kernel");
                 }
             }
-        }
-        // --- Householder reconstruction
-        double* Tp = w.T + (int64_t)p * nb * nb;
-        Mat Wqp = sub(Wqm, j0, j0), Wp = fused_panel ? sub(Wqm, j0, j0) : mat((lookahead && (p & 1)) ? w.W2 : w.W, wrs, wcs);
-        if (fused_panel) {
-        } else if (nb == 32)
-            TN_PROF_LAUNCH(st, PROF_LU, hipLaunchKernelGGL((lu_reconstruct_kernel<32>), dim3(1), dim3(256), 0, st, Yp.p, yrs, ycs, b, w.Uinv, Tp, w.UT, w.UTq,
-                               Wp.p, wrs, wcs, Wqp.p));
-        else
             TN_PROF_LAUNCH(st, PROF_LU, hipLaunchKernelGGL((lu_reconstruct_kernel<64>), dim3(1), dim3(256), 0, st, Yp.p, yrs, ycs, b, w.Uinv, Tp, w.UT, w.UTq,
                                Wp.p, wrs, wcs, Wqp.p));
-        if (!fused_panel) TN_CHECK_LAUNCH("lu_reconstruct_kernel");
+            TN_CHECK_LAUNCH("lu_reconstruct_kernel");
+        }
         dbg_check(st, Tp, b, 1, b, b, "T", p, 9);
         dbg_check(st, w.Uinv, b, 1, b, b, "Uinv", p, 9);
         if (mp > b && !fused_panel) {            // rows below the top block: Y <- Q1 Uinv,  W <- Q1 (Uinv T^T),  Wq <- Q1 (Uinv T)
             dim3 grid((unsigned)cdiv(mp - b, 256));
             prof_begin(st, PROF_ROWS_SMALL);
-            if (nb == 32)
-                hipLaunchKernelGGL(rows_times_small3_mfma_kernel, grid, dim3(256), 0, st, sub(Yp, b, 0).p, yrs, ycs, mp - b, b,
-                                   w.Uinv, w.UT, w.UTq, sub(Wp, b, 0).p, wrs, wcs, sub(Wqp, b, 0).p);
-            else
-                hipLaunchKernelGGL((rows_times_small3_kernel<64>), grid, dim3(256), 0, st, sub(Yp, b, 0).p, yrs, ycs, mp - b, b,
-                                   w.Uinv, w.UT, w.UTq, sub(Wp, b, 0).p, wrs, wcs, sub(Wqp, b, 0).p);
+            hipLaunchKernelGGL((rows_times_small3_kernel<64>), grid, dim3(256), 0, st, sub(Yp, b, 0).p, yrs, ycs, mp - b, b,
+                               w.Uinv, w.UT, w.UTq, sub(Wp, b, 0).p, wrs, wcs, sub(Wqp, b, 0).p);
             TN_CHECK_LAUNCH("rows_times_small3_kernel");
             prof_end(st, PROF_ROWS_SMALL, 6.0 * (mp - b) * b * b, 32.0 * (mp - b) * b);
         }
         // --- trailing update  A[j0:, j0:] -= (Y T^T) (Y^T A[j0:, j0:])
-        const int64_t nnar = lookahead ? std::min<int64_t>(ntr, 2 * (int64_t)nb) : ntr;     // columns updated on this stream
-        if (lookahead && ntr > nnar) {
-            // the wide part goes to the look-ahead stream as soon as this panel's reflectors exist
-            if ((he = hipEventRecord(ev.panel[p & 1], st)) != hipSuccess) return hip_fail(he, "record panel");
-            if ((he = hipStreamWaitEvent(aux, ev.panel[p & 1], 0)) != hipSuccess) return hip_fail(he, "wait panel");
-            const int64_t nw = ntr - nnar;
-            Mat Aw = sub(Ap, 0, nnar), Xw = mat(w.X2, nw, 1);
-            if ((rc = gemm(aux, b, nw, mp, 1.0, tr(Yp), Aw, 0.0, Xw, w.gemm_ws2, w.gemm_ws_bytes))) return rc;
-            if ((rc = gemm(aux, mp, nw, b, -1.0, Wp, Xw, 1.0, Aw))) return rc;
-            // columns j0+nb .. j0+2nb (the next panel) were last written by the previous wide update
-            if ((rc = join_wide())) return rc;
-            if ((he = hipEventRecord(ev.wide[p & 1], aux)) != hipSuccess) return hip_fail(he, "record wide");
-            wide_pending = p & 1;
-        } else if (lookahead) {
-            if ((rc = join_wide())) return rc;
-        }
-        Mat Xm = mat(w.X, nnar, 1);
+        Mat Xm = mat(w.X, ntr, 1);
         if (piv_dev) {         // (the same two products, skipped on the device once the exit test has fired)
             const Mat Yt = tr(Yp);
-            if ((rc = gemm_ex(st, b, nnar, mp, 1.0, Yt.p, Yt.rs, Yt.cs, Ap.p, Ap.rs, Ap.cs, 0.0, Xm.p, Xm.rs, Xm.cs, 1, 0, 0, 0, w.gemm_ws, w.gemm_ws_bytes,
+            if ((rc = gemm_ex(st, b, ntr, mp, 1.0, Yt.p, Yt.rs, Yt.cs, Ap.p, Ap.rs, Ap.cs, 0.0, Xm.p, Xm.rs, Xm.cs, 1, 0, 0, 0, w.gemm_ws, w.gemm_ws_bytes,
                               &gx_active)))
                 return rc;
-            if ((rc = gemm_ex(st, mp, nnar, b, -1.0, Wp.p, Wp.rs, Wp.cs, Xm.p, Xm.rs, Xm.cs, 1.0, Ap.p, Ap.rs, Ap.cs, 1, 0, 0, 0, nullptr, 0, &gx_active))) return rc;
+            if ((rc = gemm_ex(st, mp, ntr, b, -1.0, Wp.p, Wp.rs, Wp.cs, Xm.p, Xm.rs, Xm.cs, 1.0, Ap.p, Ap.rs, Ap.cs, 1, 0, 0, 0, nullptr, 0, &gx_active))) return rc;
         } else {
-        if ((rc = gemm(st, b, nnar, mp, 1.0, tr(Yp), Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-        if ((rc = gemm(st, mp, nnar, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
+            if ((rc = gemm(st, b, ntr, mp, 1.0, tr(Yp), Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
+            if ((rc = gemm(st, mp, ntr, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
         }
         if (reveal && (p & 1) == 1 && p + 1 < P) {
-            if ((rc = join_wide())) return rc;                  // the norms below read the whole trailing block
             const int64_t j1 = j0 + b;
             const int64_t nt = n - j1;
             TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(colnorm2_kernel, dim3((unsigned)nt), dim3(256), 0, st, sub(Am, j1, j1).p, rs, cs, m - j1,
@@ -1719,7 +1528,6 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
             }
         }
     }
-    if ((rc = join_wide())) return rc;
     if (piv_dev) {
         // the last panel's own verdict (it may have stopped the factorisation in front of itself), then the permutation
         if (P >= 1 && k == kfull) {
@@ -1756,7 +1564,7 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
     const int fold_b = (nb == 32 && P >= 1 && m * k <= 256 * 512) ? (int)(k - jf) : 0;
     // fused panel step: the m x k array holds W = Y T^T of every panel and  H_p Q = Q - Y_p (W_p^T Q);  otherwise it holds Y T and
     // H_p Q = Q - (Y_p T_p) (Y_p^T Q).  The kernel below forms  second (first_top^T Z)  either way.
-    const bool wform = (nb == 32 && !use_tsqr);
+    const bool wform = (nb == 32);
     {
         const unsigned nR = (unsigned)cdiv(k * n, 256), nQ = (unsigned)cdiv(m * k, 256);
         TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(assemble_R_init_Q_kernel, dim3(nR + nQ), dim3(256), 0, st, A, rs, cs, nb, k, n, w.Z, w.Tri, R, rrs,

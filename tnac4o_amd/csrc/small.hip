@@ -85,369 +85,16 @@ int gram_partial(hipStream_t st, const double* X, int64_t vs, int64_t es, int64_
 }
 
 // ------------------------------------------------------------------------------------------ eig_small
-// Round-robin ("circle") pairing of n (even) indices: step s in [0, n-1), slot a in [0, n/2).
-__device__ __forceinline__ void rr_pair(int n, int s, int a, int& p, int& q) {
-    if (a == 0) {
-        p = n - 1;
-        q = s;
-    } else {
-        p = (s + a) % (n - 1);
-        q = (s - a + (n - 1)) % (n - 1);
-    }
-    if (p > q) {
-        const int t = p;
-        p = q;
-        q = t;
-    }
-}
-
-template <int NB>
-__global__ __launch_bounds__(256) void eig_small_kernel(const double* __restrict__ part, int nchunk, int nvec, int mode,
-                                                        int max_sweeps, double dead_thresh,
-                                                        double* __restrict__ out, int* __restrict__ dead,
-                                                        int* __restrict__ nrot_out, double* __restrict__ maxoff_out,
-                                                        double relevant2) {
-    constexpr int P = NB + 1;
-    __shared__ double G[NB * P];
-    __shared__ double J[NB * P];
-    __shared__ double dsc[NB];
-    __shared__ int cnt, total;
-    __shared__ int stepflag[2];             // "some rotation in this step", double-buffered over consecutive steps
-    __shared__ double red[256];
-    const int tid = threadIdx.x, grp = blockIdx.x;
-    const int n = (nvec + 1) & ~1;          // even working size (a padding index never rotates)
-    const double* pg = part + (int64_t)grp * nchunk * nvec * nvec;
-
-    {   // Gram = sum of the split-K partials.  All of a thread's loads of one chunk are issued together (a loop that
-        // loads, adds and moves on would wait a full memory round trip per element: 128 dependent trips here).
-        constexpr int EPT = NB * NB / 256;
-        double acc[EPT];
-#pragma unroll
-        for (int t = 0; t < EPT; ++t) acc[t] = 0.0;
-        for (int c = 0; c < nchunk; c += 2) {
-            double v0[EPT], v1[EPT];
-            const bool two = (c + 1 < nchunk);
-#pragma unroll
-            for (int t = 0; t < EPT; ++t) {
-                const int e = tid + 256 * t, i = e / NB, j = e % NB;
-                const bool in = (i < nvec && j < nvec);
-                const int64_t o = (int64_t)c * nvec * nvec + i * nvec + j;
-                v0[t] = in ? pg[o] : 0.0;
-                v1[t] = (in && two) ? pg[o + (int64_t)nvec * nvec] : 0.0;
-            }
-#pragma unroll
-            for (int t = 0; t < EPT; ++t) acc[t] = (acc[t] + v0[t]) + v1[t];
-        }
-#pragma unroll
-        for (int t = 0; t < EPT; ++t) {
-            const int e = tid + 256 * t, i = e / NB, j = e % NB;
-            const bool in = (i < nvec && j < nvec);
-            G[i * P + j] = in ? acc[t] : (i == j ? 1.0 : 0.0);
-            J[i * P + j] = (i == j) ? 1.0 : 0.0;
-        }
-    }
-    if (tid == 0) total = 0;
-    __syncthreads();
-    if (mode != 2) {
-        if (tid < NB) {
-            const double gii = G[tid * P + tid];
-            const bool ok = (gii > dead_thresh) && (gii < 1.7e308);
-            dsc[tid] = ok ? sqrt(gii) : 1.0;
-            if (tid < nvec && dead) dead[grp * nvec + tid] = ok ? 0 : 1;
-            if (!ok) dsc[tid] = 0.0;        // marks a dead column
-        }
-        __syncthreads();
-        for (int e = tid; e < NB * NB; e += 256) {
-            const int i = e / NB, j = e % NB;
-            const double di = dsc[i], dj = dsc[j];
-            double g;
-            if (di == 0.0 || dj == 0.0) g = (i == j) ? 1.0 : 0.0;
-            else g = (i == j) ? 1.0 : G[i * P + j] * fast_rcp(di * dj);
-            G[i * P + j] = g;
-        }
-        __syncthreads();
-    }
-    // largest relative off-diagonal before rotating (diagnostic / convergence measure): max of g_ij^2 / (g_ii g_jj) with the
-    // reciprocal diagonal prepared once, one square root at the end, wave-level reduction
-    {
-        __shared__ double rdg[NB];
-        if (tid < NB) {
-            const double gii = fabs(G[tid * P + tid]);
-            // vectors whose squared norm is <= relevant2 do not enter the convergence measure (SVD: they lie a factor 4 below
-            // the truncation threshold and are discarded whatever their mutual angles are); a group in which only such
-            // vectors are non-orthogonal is not rotated at all
-            rdg[tid] = (gii > relevant2 && tid < nvec) ? fast_rcp(gii) : 0.0;
-        }
-        __syncthreads();
-        double m = 0.0;
-#pragma unroll
-        for (int t = 0; t < NB * NB / 256; ++t) {
-            const int e = tid + 256 * t, i = e / NB, j = e % NB;
-            const double g = G[i * P + j];
-            const double r2 = (i < j) ? g * g * rdg[i] * rdg[j] : 0.0;
-            m = r2 > m ? r2 : m;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-        if ((tid & 63) == 0) red[tid >> 6] = m;
-        __syncthreads();
-        if (tid == 0) {
-            const double mm = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-            red[0] = sqrt(mm);
-            if (maxoff_out) maxoff_out[grp] = red[0];
-        }
-        __syncthreads();
-    }
-
-    // Parallel-order Jacobi on the full NB x NB arrays (indices >= nvec are isolated: unit diagonal, zero coupling,
-    // so they never rotate).  Trip counts are compile-time so that each phase issues all of its LDS loads at once.
-    const bool need = (mode != 1) && (nvec >= 2) && (red[0] > 8.881784197001252e-16);
-    if (need) {
-        // Each step of the round-robin tournament applies NB/2 disjoint plane rotations R:  G <- R^T G R  and  J <- J R.
-        //  * G lives in LDS and is updated as independent 2 x 2 blocks (rotation a x rotation b) by all 256 threads.  A thread
-        //    keeps the same rotation slots for the whole sweep and derives their index pairs arithmetically; the HP lanes that
-        //    share a row read HP distinct columns of it (no bank conflicts).
-        //  * J never touches LDS during the sweeps (it was half of the traffic of an LDS-bound step): lane i of wave 3 holds
-        //    ROW i of J in registers, so a rotation of columns (p, q) mixes two registers of the same lane.  Register indices
-        //    must be compile-time constants, so the row is kept in a frame that turns with the tournament: in step s position f
-        //    holds column (f + s) mod (NB-1) (position NB-1 holds column NB-1), which makes the pairs of every step the fixed
-        //    positions (a, NB-1-a) and (0, NB-1); after the rotations the frame advances by one position (NB-2 register moves).
-        //    A sweep has NB-1 steps, so the frame is back in place at its end.  J only follows the rotations, nothing of a
-        //    later step depends on it: wave 3 applies step s-1 while wave 0 decides the rotations of step s.
-        constexpr int HP = NB / 2, GB = HP * HP / 256;
-        __shared__ __attribute__((aligned(16))) double cs2[2][HP * 2];      // (c, s) of slot a, double-buffered over the steps
-        __shared__ __attribute__((aligned(16))) double csj[2][HP * 2];      // (c, +-s): the same rotation as seen from J's frame
-        const double tol = 8.881784197001252e-16;      // 2^-50
-        const int tb = tid % HP, t0 = tid / HP;
-        constexpr int TS = 256 / HP;
-        constexpr int nsteps = NB - 1;
-        auto slot_pair = [](int s, int a, int& p, int& q) {
-            if (a == 0) { p = NB - 1; q = s; }
-            else { p = s + a; p -= (p >= NB - 1) ? NB - 1 : 0; q = s - a; q += (q < 0) ? NB - 1 : 0; }
-            if (p > q) { const int t = p; p = q; q = t; }
-        };
-        const bool jwave = (tid >= 192);                   // wave 3
-        double jr[NB];                                     // (wave 3) row `tid - 192` of J in the turning frame
-#pragma unroll
-        for (int k = 0; k < NB; ++k) jr[k] = (k == tid - 192) ? 1.0 : 0.0;
-        // The frame is advanced once per group of FU steps (FU divides NB-1), so that the register moves are amortised: within
-        // a group, step s = s0 + u finds column (s + a) at position (u + a) mod (NB-1) and column (s - a) at (u - a) mod (NB-1),
-        // column s itself (slot 0) at position u -- all compile-time constants once the loop over u is unrolled.
-        constexpr int FU = (NB == 64) ? 7 : ((NB == 32) ? 1 : 1);      // 63 = 9 x 7; 31 is prime (one step per group)
-        static_assert((NB - 1) % FU == 0, "group length must divide the sweep");
-        auto apply_j = [&](int t, auto uc) {               // rotations of step t (position offset u) on the register row
-            constexpr int u = decltype(uc)::value;
-            if (stepflag[t & 1]) {
-                double2 r[HP];
-#pragma unroll
-                for (int a = 0; a < HP; ++a) r[a] = *reinterpret_cast<const double2*>(&csj[t & 1][2 * a]);      // all reads in flight
-                {   // slot 0: (column s at position u, column NB-1 at position NB-1)
-                    const double x = jr[u], y = jr[NB - 1];
-                    jr[u] = r[0].x * x - r[0].y * y;
-                    jr[NB - 1] = r[0].y * x + r[0].x * y;
-                }
-#pragma unroll
-                for (int a = 1; a < HP; ++a) {
-                    constexpr int M = NB - 1;
-                    const int px = (u + a) % M, py = (u - a + M) % M;
-                    const double x = jr[px], y = jr[py];
-                    jr[px] = r[a].x * x - r[a].y * y;
-                    jr[py] = r[a].y * x + r[a].x * y;
-                }
-            }
-        };
-        auto advance_frame = [&]() {                       // position f <- position (f + FU) mod (NB-1)
-            double tmp[FU];
-#pragma unroll
-            for (int f = 0; f < FU; ++f) tmp[f] = jr[f];
-#pragma unroll
-            for (int f = 0; f < NB - 1 - FU; ++f) jr[f] = jr[f + FU];
-#pragma unroll
-            for (int f = 0; f < FU; ++f) jr[NB - 1 - FU + f] = tmp[f];
-        };
-        auto step = [&](int s, auto uc, int& mine) -> void {     // one step of the tournament; u = s mod FU
-            constexpr int u = decltype(uc)::value;
-            if (tid < 64) {                                // wave 0 decides the rotations of this step
-                bool rot = false;
-                if (tid < HP) {
-                    int p, q;
-                    slot_pair(s, tid, p, q);
-                    const double gpq = G[p * P + q], gpp = G[p * P + p], gqq = G[q * P + q];
-                    double c = 1.0, sn = 0.0;
-                    // rotate iff |g_pq| > tol sqrt(g_pp g_qq), tested on the squares (no square root on the critical path)
-                    const double g2 = gpq * gpq;
-                    if (g2 > tol * tol * fabs(gpp * gqq)) {
-                        // smaller-angle rotation from the double angle: cos 2t = |d| / hyp, d = g_qq - g_pp,
-                        // hyp^2 = d^2 + 4 g_pq^2;  c^2 = (1 + cos 2t) / 2,  s = g_pq / (hyp c) with the sign of d g_pq
-                        const double d = gqq - gpp;
-                        const double rh = fast_rsqrt(d * d + 4.0 * g2);
-                        const double c2 = 0.5 + 0.5 * fabs(d) * rh;
-                        const double rcv = fast_rsqrt(c2);
-                        const double sabs = fabs(gpq) * rh * rcv;
-                        if (sabs <= 1.0 && c2 <= 1.0000000000000002) {     // (fails for non-finite intermediates: no rotation)
-                            c = c2 * rcv;
-                            sn = ((d >= 0.0) == (gpq >= 0.0)) ? sabs : -sabs;
-                            ++mine;
-                            rot = true;
-                        }
-                    }
-                    *reinterpret_cast<double2*>(&cs2[s & 1][2 * tid]) = make_double2(c, sn);
-                    // J's frame holds the pair as (column (s + a) mod (NB-1), column (s - a) mod (NB-1)), slot 0 as (s, NB-1);
-                    // the rotation is defined on (smaller, larger) column: flip the sine where the frame has them the other way
-                    int up = s + tid; up -= (up >= NB - 1) ? NB - 1 : 0;
-                    const bool flipped = (tid > 0) && (up != p);
-                    *reinterpret_cast<double2*>(&csj[s & 1][2 * tid]) = make_double2(c, flipped ? -sn : sn);
-                }
-                const unsigned long long any = __ballot(rot);
-                if (tid == 0) stepflag[s & 1] = (any != 0ull) ? 1 : 0;
-            } else if (jwave && s > 0) {                   // J follows one step behind (reads the other halves of csj / stepflag)
-                if constexpr (u == 0) {
-                    apply_j(s - 1, std::integral_constant<int, FU - 1>{});
-                    advance_frame();
-                } else {
-                    apply_j(s - 1, std::integral_constant<int, u - 1>{});
-                }
-            }
-            __syncthreads();
-            if (stepflag[s & 1] == 0) return;              // uniform: nothing to rotate in this step
-            {
-                int pb, qb;
-                slot_pair(s, tb, pb, qb);
-                const double2 rb = *reinterpret_cast<const double2*>(&cs2[s & 1][2 * tb]);
-                const double cb = rb.x, sb = rb.y;
-                double g00[GB], g01[GB], g10[GB], g11[GB];
-                int pa[GB], qa[GB];
-                double2 ra[GB];
-#pragma unroll
-                for (int k = 0; k < GB; ++k) {
-                    slot_pair(s, t0 + TS * k, pa[k], qa[k]);
-                    ra[k] = *reinterpret_cast<const double2*>(&cs2[s & 1][2 * (t0 + TS * k)]);
-                    g00[k] = G[pa[k] * P + pb]; g01[k] = G[pa[k] * P + qb];
-                    g10[k] = G[qa[k] * P + pb]; g11[k] = G[qa[k] * P + qb];
-                }
-#pragma unroll
-                for (int k = 0; k < GB; ++k) {
-                    const double ca = ra[k].x, sa = ra[k].y;
-                    const double t00 = ca * g00[k] - sa * g10[k], t01 = ca * g01[k] - sa * g11[k];
-                    const double t10 = sa * g00[k] + ca * g10[k], t11 = sa * g01[k] + ca * g11[k];
-                    G[pa[k] * P + pb] = cb * t00 - sb * t01; G[pa[k] * P + qb] = sb * t00 + cb * t01;
-                    G[qa[k] * P + pb] = cb * t10 - sb * t11; G[qa[k] * P + qb] = sb * t10 + cb * t11;
-                }
-            }
-            __syncthreads();
-        };
-        for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-            if (tid == 0) cnt = 0;
-            int mine = 0;                                  // rotations decided by this thread in this sweep
-            __syncthreads();
-            for (int s0 = 0; s0 < nsteps; s0 += FU) {
-                if constexpr (FU == 7) {
-                    step(s0 + 0, std::integral_constant<int, 0>{}, mine);
-                    step(s0 + 1, std::integral_constant<int, 1>{}, mine);
-                    step(s0 + 2, std::integral_constant<int, 2>{}, mine);
-                    step(s0 + 3, std::integral_constant<int, 3>{}, mine);
-                    step(s0 + 4, std::integral_constant<int, 4>{}, mine);
-                    step(s0 + 5, std::integral_constant<int, 5>{}, mine);
-                    step(s0 + 6, std::integral_constant<int, 6>{}, mine);
-                } else {
-                    step(s0, std::integral_constant<int, 0>{}, mine);
-                }
-            }
-            if (jwave) {                                   // the last step of the sweep; the frame is back in place afterwards
-                apply_j(nsteps - 1, std::integral_constant<int, FU - 1>{});
-                advance_frame();
-            }
-            if (mine) atomicAdd(&cnt, mine);               // once per sweep, off the per-step critical path
-            __syncthreads();
-            if (tid == 0) total += cnt;
-            const int done = (cnt == 0);
-            __syncthreads();
-            if (done) break;
-        }
-        if (jwave && tid - 192 < NB) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) J[(tid - 192) * P + k] = jr[k];
-        }
-        __syncthreads();
-    }
-    if (tid == 0 && nrot_out) nrot_out[grp] = total;
-    if (mode != 1 && total > 0) {
-        // One Newton-Schulz step J <- J (3I - J^T J)/2: the accumulated product of ~n*sweeps plane rotations drifts
-        // from orthogonality by ~sqrt(n*sweeps) eps; this squares the defect, so repeated application of J over many
-        // Jacobi rounds does not inflate vector norms (singular values) beyond rounding.
-        // Both products run on the matrix cores, each wave owning a strip of 16 x 16 output tiles.
-        __shared__ double eigdiag[NB];
-        typedef double d4e __attribute__((ext_vector_type(4)));
-        constexpr int NT = NB / 16, TPW = NT * NT / 4;          // tiles per wave: 4 (NB = 64) or 1 (NB = 32)
-        const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
-        const int ti = (NB == 64) ? wave : (wave >> 1), tj0 = (NB == 64) ? 0 : (wave & 1);
-        if (tid < NB) eigdiag[tid] = G[tid * P + tid];          // rotated diagonal = eigenvalues (needed below)
-        __syncthreads();
-        d4e acc[TPW];
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) acc[t] = d4e{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < NB / 4; ++ks) {                   // S = J^T J
-            const int k = ks * 4 + lk;
-            const double fa = J[k * P + ti * 16 + li];
-#pragma unroll
-            for (int t = 0; t < TPW; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, J[k * P + (tj0 + t) * 16 + li], acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) G[(ti * 16 + lk + 4 * r) * P + (tj0 + t) * 16 + li] = acc[t][r];
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) acc[t] = d4e{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < NB / 4; ++ks) {                   // N = J S
-            const int k = ks * 4 + lk;
-            const double fa = J[(ti * 16 + li) * P + k];
-#pragma unroll
-            for (int t = 0; t < TPW; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, G[k * P + (tj0 + t) * 16 + li], acc[t], 0, 0, 0);
-        }
-        double nv[TPW][4];
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                nv[t][r] = 1.5 * J[(ti * 16 + lk + 4 * r) * P + (tj0 + t) * 16 + li] - 0.5 * acc[t][r];
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) J[(ti * 16 + lk + 4 * r) * P + (tj0 + t) * 16 + li] = nv[t][r];
-        if (tid < NB) G[tid * P + tid] = eigdiag[tid];
-        __syncthreads();
-    }
-    double* o = out + (int64_t)grp * nvec * nvec;
-    for (int e = tid; e < nvec * nvec; e += 256) {
-        const int i = e / nvec, j = e % nvec;
-        double v = J[i * P + j];
-        if (mode != 2) {
-            const double di = dsc[i];
-            v = (di == 0.0) ? 0.0 : v / di;
-            if (dsc[j] == 0.0) v = 0.0;
-        }
-        o[e] = v;
-    }
-}
-
-// ------------------------------------------------------------------------------------------ eig_small, pipelined form
-// Same mathematics as eig_small_kernel (parallel-order two-sided Jacobi on the <= 64 x 64 Gram matrix, J accumulated in the
-// registers of one wave), reorganised so that a step costs ONE barrier and nothing serial sits between barriers:
-//   * G is double-buffered: the update of step s reads G[cur] and writes G[nxt] (waves 1 and 2, HP*HP/128 independent 2 x 2
-//     blocks per thread);
+// Parallel-order two-sided Jacobi on the <= 64 x 64 Gram matrix, one workgroup per matrix, ONE barrier per step and nothing serial
+// between barriers:
+//   * G is double-buffered: the update of step s reads G[cur] and writes G[nxt];
 //   * wave 0 decides the rotations of step s+1 DURING step s: the three entries a rotation depends on (g_pp, g_qq, g_pq of its
 //     pair in step s+1) are single outputs of three 2 x 2 blocks of step s, which wave 0 evaluates itself from G[cur] and the
 //     rotations of step s with the very operations of the update (rot_p / rot_q below: explicit mul + fma, so the values are
-//     bit-identical to what the update stores) -- the chain of reciprocal square roots that used to sit between two barriers of
-//     every step now runs beside the update;
-//   * wave 3 applies step s to its register rows of J in the same phase (no lag any more).
+//     bit-identical to what the update stores);
+//   * wave 3 applies step s to its register rows of J in the same phase.
 // A step without any rotation (flag decided together with the parameters) skips the update and keeps the buffers.
+// (Two earlier generations, with two barriers per step and with one barrier on four waves, were measured slower and removed.)
 __device__ __forceinline__ double rot_p(double c, double s, double x, double y) { return __fma_rn(-s, y, __dmul_rn(c, x)); }   // c x - s y
 __device__ __forceinline__ double rot_q(double c, double s, double x, double y) { return __fma_rn(s, x, __dmul_rn(c, y)); }    // s x + c y
 __device__ __forceinline__ double rsqrt2n(double x) {      // hardware seed (~2^-26) + two Newton steps: full double accuracy
@@ -455,372 +102,6 @@ __device__ __forceinline__ double rsqrt2n(double x) {      // hardware seed (~2^
     r = r * (1.5 - 0.5 * x * r * r);
     r = r * (1.5 - 0.5 * x * r * r);
     return r;
-}
-
-template <int NB>
-__global__ __launch_bounds__(256) void eig_small2_kernel(const double* __restrict__ part, int nchunk, int nvec, int mode,
-                                                         int max_sweeps, double dead_thresh,
-                                                         double* __restrict__ out, int* __restrict__ dead,
-                                                         int* __restrict__ nrot_out, double* __restrict__ maxoff_out,
-                                                         double relevant2) {
-    constexpr int P = NB + 1;
-    __shared__ double Gb[2][NB * P];
-    __shared__ double J[NB * P];
-    __shared__ double dsc[NB];
-    __shared__ int cnt, total;
-    __shared__ int stepflag[2];
-    __shared__ double red[256];
-    const int tid = threadIdx.x, grp = blockIdx.x;
-    const double* pg = part + (int64_t)grp * nchunk * nvec * nvec;
-    double* G = Gb[0];
-    {
-        constexpr int EPT = NB * NB / 256;
-        double acc[EPT];
-#pragma unroll
-        for (int t = 0; t < EPT; ++t) acc[t] = 0.0;
-        for (int c = 0; c < nchunk; c += 2) {
-            double v0[EPT], v1[EPT];
-            const bool two = (c + 1 < nchunk);
-#pragma unroll
-            for (int t = 0; t < EPT; ++t) {
-                const int e = tid + 256 * t, i = e / NB, j = e % NB;
-                const bool in = (i < nvec && j < nvec);
-                const int64_t o = (int64_t)c * nvec * nvec + i * nvec + j;
-                v0[t] = in ? pg[o] : 0.0;
-                v1[t] = (in && two) ? pg[o + (int64_t)nvec * nvec] : 0.0;
-            }
-#pragma unroll
-            for (int t = 0; t < EPT; ++t) acc[t] = (acc[t] + v0[t]) + v1[t];
-        }
-#pragma unroll
-        for (int t = 0; t < EPT; ++t) {
-            const int e = tid + 256 * t, i = e / NB, j = e % NB;
-            const bool in = (i < nvec && j < nvec);
-            G[i * P + j] = in ? acc[t] : (i == j ? 1.0 : 0.0);
-            J[i * P + j] = (i == j) ? 1.0 : 0.0;
-        }
-    }
-    if (tid == 0) total = 0;
-    __syncthreads();
-    if (mode != 2) {
-        if (tid < NB) {
-            const double gii = G[tid * P + tid];
-            const bool ok = (gii > dead_thresh) && (gii < 1.7e308);
-            dsc[tid] = ok ? sqrt(gii) : 1.0;
-            if (tid < nvec && dead) dead[grp * nvec + tid] = ok ? 0 : 1;
-            if (!ok) dsc[tid] = 0.0;
-        }
-        __syncthreads();
-        for (int e = tid; e < NB * NB; e += 256) {
-            const int i = e / NB, j = e % NB;
-            const double di = dsc[i], dj = dsc[j];
-            double g;
-            if (di == 0.0 || dj == 0.0) g = (i == j) ? 1.0 : 0.0;
-            else g = (i == j) ? 1.0 : G[i * P + j] * fast_rcp(di * dj);
-            G[i * P + j] = g;
-        }
-        __syncthreads();
-    }
-    {
-        __shared__ double rdg[NB];
-        if (tid < NB) {
-            const double gii = fabs(G[tid * P + tid]);
-            rdg[tid] = (gii > relevant2 && tid < nvec) ? fast_rcp(gii) : 0.0;
-        }
-        __syncthreads();
-        double m = 0.0;
-#pragma unroll
-        for (int t = 0; t < NB * NB / 256; ++t) {
-            const int e = tid + 256 * t, i = e / NB, j = e % NB;
-            const double g = G[i * P + j];
-            const double r2 = (i < j) ? g * g * rdg[i] * rdg[j] : 0.0;
-            m = r2 > m ? r2 : m;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-        if ((tid & 63) == 0) red[tid >> 6] = m;
-        __syncthreads();
-        if (tid == 0) {
-            const double mm = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-            red[0] = sqrt(mm);
-            if (maxoff_out) maxoff_out[grp] = red[0];
-        }
-        __syncthreads();
-    }
-    const bool need = (mode != 1) && (nvec >= 2) && (red[0] > 8.881784197001252e-16);
-    int cur = 0;
-    if (need) {
-        constexpr int HP = NB / 2;
-        constexpr int M = NB - 1;                          // steps per sweep
-        constexpr int UB = HP * HP / 128;                  // 2 x 2 blocks per thread of the two updating waves
-        __shared__ __attribute__((aligned(16))) double cs2[2][HP * 2];
-        __shared__ __attribute__((aligned(16))) double csj[2][HP * 2];
-        const double tol = 8.881784197001252e-16;          // 2^-50
-        auto slot_pair = [](int s, int a, int& p, int& q) {
-            if (a == 0) { p = NB - 1; q = s; }
-            else { p = s + a; p -= (p >= M) ? M : 0; q = s - a; q += (q < 0) ? M : 0; }
-            if (p > q) { const int t = p; p = q; q = t; }
-        };
-        // slot of index i in step s, and whether i is the larger member of its pair
-        auto slot_of = [&](int s, int i, int& a, int& hi) {
-            if (i == NB - 1 || i == s) a = 0;
-            else { int d = i - s; d += (d < 0) ? M : 0; a = (d <= HP - 1) ? d : M - d; }
-            int p, q;
-            slot_pair(s, a, p, q);
-            hi = (i == q) ? 1 : 0;
-        };
-        // rotation of pair (p < q) from g_pp, g_qq, g_pq (the smaller-angle rotation, as in eig_small_kernel)
-        auto decide = [&](double gpp, double gqq, double gpq, double& c, double& sn) -> bool {
-            c = 1.0; sn = 0.0;
-            const double g2 = gpq * gpq;
-            if (g2 > tol * tol * fabs(gpp * gqq)) {
-                const double d = gqq - gpp;
-                const double rh = rsqrt2n(d * d + 4.0 * g2);
-                const double c2 = 0.5 + 0.5 * fabs(d) * rh;
-                const double rcv = rsqrt2n(c2);
-                const double sabs = fabs(gpq) * rh * rcv;
-                if (sabs <= 1.0 && c2 <= 1.0000000000000002) {
-                    c = c2 * rcv;
-                    sn = ((d >= 0.0) == (gpq >= 0.0)) ? sabs : -sabs;
-                    return true;
-                }
-            }
-            return false;
-        };
-        // wave 0, lane a < HP: parameters of step s into buffer `pb` (the buffers alternate from step to step ACROSS sweeps: a sweep
-        // has an odd number of steps, so the parity of s itself would collide at the sweep boundary)
-        auto publish = [&](int pb, int s, int a, int p, double c, double sn, bool rot) {
-            *reinterpret_cast<double2*>(&cs2[pb][2 * a]) = make_double2(c, sn);
-            int up = s + a; up -= (up >= M) ? M : 0;
-            const bool flipped = (a > 0) && (up != p);
-            *reinterpret_cast<double2*>(&csj[pb][2 * a]) = make_double2(c, flipped ? -sn : sn);
-            const unsigned long long any = __ballot(rot);
-            if (a == 0) stepflag[pb] = (any != 0ull) ? 1 : 0;
-        };
-        const bool jwave = (tid >= 192);
-        double jr[NB];
-#pragma unroll
-        for (int k = 0; k < NB; ++k) jr[k] = (k == tid - 192) ? 1.0 : 0.0;
-        constexpr int FU = (NB == 64) ? 7 : 1;
-        static_assert(M % FU == 0, "group length must divide the sweep");
-        auto apply_j = [&](int pb, auto uc) {
-            constexpr int u = decltype(uc)::value;
-            double2 r[HP];
-#pragma unroll
-            for (int a = 0; a < HP; ++a) r[a] = *reinterpret_cast<const double2*>(&csj[pb][2 * a]);
-            {
-                const double x = jr[u], y = jr[NB - 1];
-                jr[u] = r[0].x * x - r[0].y * y;
-                jr[NB - 1] = r[0].y * x + r[0].x * y;
-            }
-#pragma unroll
-            for (int a = 1; a < HP; ++a) {
-                const int px = (u + a) % M, py = (u - a + M) % M;
-                const double x = jr[px], y = jr[py];
-                jr[px] = r[a].x * x - r[a].y * y;
-                jr[py] = r[a].y * x + r[a].x * y;
-            }
-        };
-        auto advance_frame = [&]() {
-            double tmp[FU];
-#pragma unroll
-            for (int f = 0; f < FU; ++f) tmp[f] = jr[f];
-#pragma unroll
-            for (int f = 0; f < NB - 1 - FU; ++f) jr[f] = jr[f + FU];
-#pragma unroll
-            for (int f = 0; f < FU; ++f) jr[NB - 1 - FU + f] = tmp[f];
-        };
-        int mine = 0;                                      // (wave 0) rotations decided for the sweep in progress
-        int mine_next = 0;                                 // ... for the next sweep (the look-ahead of a sweep's last step)
-        // parameters of step 0 straight from G
-        if (tid < 64) {
-            bool rot = false;
-            double c = 1.0, sn = 0.0;
-            int p = 0, q = 0;
-            if (tid < HP) {
-                slot_pair(0, tid, p, q);
-                rot = decide(G[p * P + p], G[q * P + q], G[p * P + q], c, sn);
-                if (rot) ++mine;
-            }
-            if (tid < HP) publish(0, 0, tid, p, c, sn, rot);
-            else (void)__ballot(false);
-        }
-        __syncthreads();
-        int par = 0;                                       // parameter buffer of the step in progress
-        // one step of the tournament: phase of step s (u = s mod FU compile-time for the register frame of J)
-        auto step = [&](int s, auto uc) -> void {
-            constexpr int u = decltype(uc)::value;
-            const int flag = stepflag[par];                 // uniform
-            const double* Gc = Gb[cur];
-            double* Gn = Gb[cur ^ 1];
-            if (tid < 64) {
-                // ---- wave 0: rotations of step s+1 from G[cur] and the rotations of step s
-                const int s1 = (s + 1 == M) ? 0 : s + 1;
-                bool rot = false;
-                double c = 1.0, sn = 0.0;
-                int p = 0, q = 0;
-                if (tid < HP) {
-                    slot_pair(s1, tid, p, q);
-                    double gpp, gqq, gpq;
-                    if (flag) {
-                        int ap, hp_, aq, hq_;
-                        slot_of(s, p, ap, hp_);
-                        slot_of(s, q, aq, hq_);
-                        int pp, qp, pq, qq;
-                        slot_pair(s, ap, pp, qp);           // pair holding p in step s
-                        slot_pair(s, aq, pq, qq);           // pair holding q in step s
-                        const double2 rp = *reinterpret_cast<const double2*>(&cs2[par][2 * ap]);
-                        const double2 rq = *reinterpret_cast<const double2*>(&cs2[par][2 * aq]);
-                        // block (ap, ap) -> g_pp;  block (aq, aq) -> g_qq;  block (ap, aq) -> g_pq
-                        const double a00 = Gc[pp * P + pp], a01 = Gc[pp * P + qp], a10 = Gc[qp * P + pp], a11 = Gc[qp * P + qp];
-                        const double b00 = Gc[pq * P + pq], b01 = Gc[pq * P + qq], b10 = Gc[qq * P + pq], b11 = Gc[qq * P + qq];
-                        const double x00 = Gc[pp * P + pq], x01 = Gc[pp * P + qq], x10 = Gc[qp * P + pq], x11 = Gc[qp * P + qq];
-                        {
-                            const double t0 = hp_ ? rot_q(rp.x, rp.y, a00, a10) : rot_p(rp.x, rp.y, a00, a10);
-                            const double t1 = hp_ ? rot_q(rp.x, rp.y, a01, a11) : rot_p(rp.x, rp.y, a01, a11);
-                            gpp = hp_ ? rot_q(rp.x, rp.y, t0, t1) : rot_p(rp.x, rp.y, t0, t1);
-                        }
-                        {
-                            const double t0 = hq_ ? rot_q(rq.x, rq.y, b00, b10) : rot_p(rq.x, rq.y, b00, b10);
-                            const double t1 = hq_ ? rot_q(rq.x, rq.y, b01, b11) : rot_p(rq.x, rq.y, b01, b11);
-                            gqq = hq_ ? rot_q(rq.x, rq.y, t0, t1) : rot_p(rq.x, rq.y, t0, t1);
-                        }
-                        {
-                            const double t0 = hp_ ? rot_q(rp.x, rp.y, x00, x10) : rot_p(rp.x, rp.y, x00, x10);
-                            const double t1 = hp_ ? rot_q(rp.x, rp.y, x01, x11) : rot_p(rp.x, rp.y, x01, x11);
-                            gpq = hq_ ? rot_q(rq.x, rq.y, t0, t1) : rot_p(rq.x, rq.y, t0, t1);
-                        }
-                    } else {
-                        gpp = Gc[p * P + p]; gqq = Gc[q * P + q]; gpq = Gc[p * P + q];
-                    }
-                    rot = decide(gpp, gqq, gpq, c, sn);
-                    if (rot) { if (s + 1 == M) ++mine_next; else ++mine; }
-                }
-                if (tid < HP) publish(par ^ 1, s1, tid, p, c, sn, rot);
-                else (void)__ballot(false);
-            } else if (jwave) {
-                if (flag) apply_j(par, uc);
-                if constexpr (u == FU - 1) advance_frame();
-            } else if (flag) {
-                // ---- waves 1 and 2: G[nxt] <- R^T G[cur] R, block (a, b) = rows of slot a x columns of slot b
-                const int t128 = tid - 64;
-                const int tb = t128 % HP, t0 = t128 / HP;
-                constexpr int TS = 128 / HP;
-                int pb, qb;
-                slot_pair(s, tb, pb, qb);
-                const double2 rb = *reinterpret_cast<const double2*>(&cs2[par][2 * tb]);
-                double g00[UB], g01[UB], g10[UB], g11[UB];
-                int pa[UB], qa[UB];
-                double2 ra[UB];
-#pragma unroll
-                for (int k = 0; k < UB; ++k) {
-                    slot_pair(s, t0 + TS * k, pa[k], qa[k]);
-                    ra[k] = *reinterpret_cast<const double2*>(&cs2[par][2 * (t0 + TS * k)]);
-                    g00[k] = Gc[pa[k] * P + pb]; g01[k] = Gc[pa[k] * P + qb];
-                    g10[k] = Gc[qa[k] * P + pb]; g11[k] = Gc[qa[k] * P + qb];
-                }
-#pragma unroll
-                for (int k = 0; k < UB; ++k) {
-                    const double ca = ra[k].x, sa = ra[k].y;
-                    const double t00 = rot_p(ca, sa, g00[k], g10[k]), t01 = rot_p(ca, sa, g01[k], g11[k]);
-                    const double t10 = rot_q(ca, sa, g00[k], g10[k]), t11 = rot_q(ca, sa, g01[k], g11[k]);
-                    Gn[pa[k] * P + pb] = rot_p(rb.x, rb.y, t00, t01); Gn[pa[k] * P + qb] = rot_q(rb.x, rb.y, t00, t01);
-                    Gn[qa[k] * P + pb] = rot_p(rb.x, rb.y, t10, t11); Gn[qa[k] * P + qb] = rot_q(rb.x, rb.y, t10, t11);
-                }
-            }
-            __syncthreads();
-            cur ^= flag;
-            par ^= 1;
-        };
-        for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-            if (tid == 0) cnt = 0;
-            for (int s0 = 0; s0 < M; s0 += FU) {
-                if constexpr (FU == 7) {
-                    step(s0 + 0, std::integral_constant<int, 0>{});
-                    step(s0 + 1, std::integral_constant<int, 1>{});
-                    step(s0 + 2, std::integral_constant<int, 2>{});
-                    step(s0 + 3, std::integral_constant<int, 3>{});
-                    step(s0 + 4, std::integral_constant<int, 4>{});
-                    step(s0 + 5, std::integral_constant<int, 5>{});
-                    step(s0 + 6, std::integral_constant<int, 6>{});
-                } else {
-                    step(s0, std::integral_constant<int, 0>{});
-                }
-            }
-            if (mine) atomicAdd(&cnt, mine);
-            __syncthreads();
-            if (tid == 0) total += cnt;
-            const int done = (cnt == 0);
-            __syncthreads();
-            mine = mine_next;
-            mine_next = 0;
-            if (done) break;
-        }
-        if (jwave && tid - 192 < NB) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) J[(tid - 192) * P + k] = jr[k];
-        }
-        __syncthreads();
-    }
-    double* Gf = Gb[cur];                                  // the rotated Gram matrix
-    double* Gs = Gb[cur ^ 1];                              // scratch for the Newton-Schulz step
-    if (tid == 0 && nrot_out) nrot_out[grp] = total;
-    if (mode != 1 && total > 0) {
-        typedef double d4e __attribute__((ext_vector_type(4)));
-        constexpr int NT = NB / 16, TPW = NT * NT / 4;
-        const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
-        const int ti = (NB == 64) ? wave : (wave >> 1), tj0 = (NB == 64) ? 0 : (wave & 1);
-        d4e acc[TPW];
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) acc[t] = d4e{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < NB / 4; ++ks) {                   // S = J^T J
-            const int k = ks * 4 + lk;
-            const double fa = J[k * P + ti * 16 + li];
-#pragma unroll
-            for (int t = 0; t < TPW; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, J[k * P + (tj0 + t) * 16 + li], acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Gs[(ti * 16 + lk + 4 * r) * P + (tj0 + t) * 16 + li] = acc[t][r];
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) acc[t] = d4e{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < NB / 4; ++ks) {                   // N = J S
-            const int k = ks * 4 + lk;
-            const double fa = J[(ti * 16 + li) * P + k];
-#pragma unroll
-            for (int t = 0; t < TPW; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, Gs[k * P + (tj0 + t) * 16 + li], acc[t], 0, 0, 0);
-        }
-        double nv[TPW][4];
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                nv[t][r] = 1.5 * J[(ti * 16 + lk + 4 * r) * P + (tj0 + t) * 16 + li] - 0.5 * acc[t][r];
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) J[(ti * 16 + lk + 4 * r) * P + (tj0 + t) * 16 + li] = nv[t][r];
-        __syncthreads();
-    }
-    (void)Gf;
-    double* o = out + (int64_t)grp * nvec * nvec;
-    for (int e = tid; e < nvec * nvec; e += 256) {
-        const int i = e / nvec, j = e % nvec;
-        double v = J[i * P + j];
-        if (mode != 2) {
-            const double di = dsc[i];
-            v = (di == 0.0) ? 0.0 : v / di;
-            if (dsc[j] == 0.0) v = 0.0;
-        }
-        o[e] = v;
-    }
 }
 
 // Jacobi rotation of a pair (p < q) from g_pp, g_qq, g_pq: the smaller-angle rotation, (c, sn) with G' = R^T G R, R = [[c, sn], [-sn, c]];
@@ -843,12 +124,12 @@ __device__ __forceinline__ bool eig_decide(double gpp, double gqq, double gpq, d
     return false;
 }
 
-// ------------------------------------------------------------------------------------------ eig_small, third form
-// The pipelined kernel above is bound by the instruction streams of its single waves (a wave issues one fp64 instruction per 4
-// cycles: 128 for the update of a quarter of G, 128 for J, ~70 dependent ones for the rotation parameters), not by its barrier.
-// Here the workgroup has 8 waves: wave 0 decides the next step's rotations, wave 3 turns its register rows of J, and FIVE waves
-// (1, 2, 4, 5, 6) update G over the 2 x 2 blocks of the upper triangle only (528 instead of 1024 for a 64 x 64 matrix), writing
-// every block and its mirror image, so that G stays exactly symmetric and a thread has two blocks per step instead of eight.
+// ------------------------------------------------------------------------------------------ eig_small, the kernel
+// A step is bound by the instruction streams of single waves (a wave issues one fp64 instruction per 4 cycles: 128 for the update
+// of a quarter of G, 128 for J, ~70 dependent ones for the rotation parameters), not by its barrier.  So the workgroup has 8 waves:
+// wave 0 decides the next step's rotations, wave 3 turns its register rows of J, and FIVE waves (1, 2, 4, 5, 6) update G over the
+// 2 x 2 blocks of the upper triangle only (528 instead of 1024 for a 64 x 64 matrix), writing every block and its mirror image, so
+// that G stays exactly symmetric and a thread has two blocks per step instead of eight.
 // -DTN_CLOCKS: thread 0 of group 0 of the persistent SVD kernel accumulates the 100 MHz wall clock per phase of the eigenproblem:
 // [0] partial sums -> G  [1] measure + fast path  [2] cyclic sweeps  [3] Newton-Schulz  [4] store  [5] calls  [6] calls with cyclic sweeps
 #ifdef TN_CLOCKS
@@ -1174,7 +455,7 @@ __device__ __forceinline__ void eig_small3_body(double* pool, const int grp, con
             slot_pair(s, a, p, q);
             hi = (i == q) ? 1 : 0;
         };
-        // rotation of pair (p < q) from g_pp, g_qq, g_pq (the smaller-angle rotation, as in eig_small_kernel)
+        // rotation of pair (p < q) from g_pp, g_qq, g_pq (the smaller-angle rotation)
         auto decide = [&](double gpp, double gqq, double gpq, double& c, double& sn) -> bool {
             c = 1.0; sn = 0.0;
             const double g2 = gpq * gpq;
@@ -1499,33 +780,16 @@ int eig_small(hipStream_t st, const double* part, int nchunk, int nvec, int ngro
     TN_CHECK_ARG(nvec >= 1 && nvec <= NBMAX, "nvec out of range");
     if (ngroups <= 0) return 0;
     prof_begin(st, PROF_EIG);
-    // TN_EIG_PIPELINED=0 selects the first-generation kernel (two barriers per Jacobi step) for A/B measurements
-    static const int gen = [] { const char* e = getenv("TN_EIG_PIPELINED"); return e ? atoi(e) : 2; }();      // 0, 1 (256 threads), 2 (512 threads)
-    const bool pipelined = gen == 1;
     static const int dbg = [] { const char* e = getenv("TN_EIG_DBG"); return e ? atoi(e) : 0; }();      // timing diagnostics of the third form
     // TN_EIG_FAST: largest relative off-diagonal up to which a pair takes the near-diagonal fast path (0 = never; see eig_small3_kernel)
     static const double fast_thr = [] { const char* e = getenv("TN_EIG_FAST"); return e ? atof(e) : 1e-2; }();
-    if (gen >= 2) {
-        if (nvec <= 32)
-            hipLaunchKernelGGL((eig_small3_kernel<32>), dim3(ngroups), dim3(512), 0, st, part, nchunk, nvec, mode, max_sweeps,
-                               dead_thresh, out, dead, nrot, maxoff, relevant2, dbg, 0.0);
-        else
-            hipLaunchKernelGGL((eig_small3_kernel<64>), dim3(ngroups), dim3(512), 0, st, part, nchunk, nvec, mode, max_sweeps,
-                               dead_thresh, out, dead, nrot, maxoff, relevant2, dbg, allow_fast ? fast_thr : 0.0);
-    } else if (pipelined) {
-        if (nvec <= 32)
-            hipLaunchKernelGGL((eig_small2_kernel<32>), dim3(ngroups), dim3(256), 0, st, part, nchunk, nvec, mode, max_sweeps,
-                               dead_thresh, out, dead, nrot, maxoff, relevant2);
-        else
-            hipLaunchKernelGGL((eig_small2_kernel<64>), dim3(ngroups), dim3(256), 0, st, part, nchunk, nvec, mode, max_sweeps,
-                               dead_thresh, out, dead, nrot, maxoff, relevant2);
-    } else if (nvec <= 32)
-        hipLaunchKernelGGL((eig_small_kernel<32>), dim3(ngroups), dim3(256), 0, st, part, nchunk, nvec, mode, max_sweeps,
-                           dead_thresh, out, dead, nrot, maxoff, relevant2);
+    if (nvec <= 32)
+        hipLaunchKernelGGL((eig_small3_kernel<32>), dim3(ngroups), dim3(512), 0, st, part, nchunk, nvec, mode, max_sweeps,
+                           dead_thresh, out, dead, nrot, maxoff, relevant2, dbg, 0.0);
     else
-        hipLaunchKernelGGL((eig_small_kernel<64>), dim3(ngroups), dim3(256), 0, st, part, nchunk, nvec, mode, max_sweeps,
-                           dead_thresh, out, dead, nrot, maxoff, relevant2);
-    TN_CHECK_LAUNCH("eig_small_kernel");
+        hipLaunchKernelGGL((eig_small3_kernel<64>), dim3(ngroups), dim3(512), 0, st, part, nchunk, nvec, mode, max_sweeps,
+                           dead_thresh, out, dead, nrot, maxoff, relevant2, dbg, allow_fast ? fast_thr : 0.0);
+    TN_CHECK_LAUNCH("eig_small3_kernel");
     prof_end(st, PROF_EIG, 0.0, 8.0 * ngroups * ((double)nchunk + 1.0) * nvec * nvec);
     return 0;
 }
@@ -1808,8 +1072,6 @@ int svd_rounds_fused(hipStream_t st, const SvdRoundsJob& j) {
         const char* e = getenv("TN_SVD_FUSED");                       // read per call: the tests switch it
         if (e && e[0] == '0') return 1;
     }
-    static const int gen = [] { const char* e = getenv("TN_EIG_PIPELINED"); return e ? atoi(e) : 2; }();
-    if (gen < 2) return 1;
     static const int dbg = [] { const char* e = getenv("TN_EIG_DBG"); return e ? atoi(e) : 0; }();
     static const double fast_thr = [] { const char* e = getenv("TN_EIG_FAST"); return e ? atof(e) : 1e-2; }();
     static const int eig_naps = [] { const char* e = getenv("TN_SVDJ_NAPS"); return e ? atoi(e) : 2; }();

@@ -830,12 +830,12 @@ int smallqr_factor(hipStream_t st, const double* A, int64_t rs, int64_t cs, int6
         a.spin_limit = e ? (unsigned)strtoul(e, nullptr, 10) : (1u << 22);
     }
     if (nblk > 1) fused_note_launch();
-    prof_begin(st, PROF_TSQR);
+    prof_begin(st, PROF_PANEL);
     if (N == 32) hipLaunchKernelGGL((sq_kernel<32, 256>), dim3(nblk), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((sq_kernel<64, 128>), dim3(nblk), dim3(256), 0, st, a);
     TN_CHECK_LAUNCH("sq_kernel");
     const double e = (double)m * (double)n;
-    prof_end(st, PROF_TSQR, 2.0 * e * n, 16.0 * e + 8.0 * n * n);
+    prof_end(st, PROF_PANEL, 2.0 * e * n, 16.0 * e + 8.0 * n * n);
     return 0;
 }
 

@@ -222,11 +222,6 @@ class _DeferredSchmidt:
         self.items = []                 # (pC, measure, row index | None, host array | None, centre tensor kept alive)
         self.small = []                 # centre matrices up to 64 x 64 of this sweep, decomposed together in finish()
         self.table = None
-        self.side = None
-        cur = torch.cuda.current_stream()
-        if cur.cuda_stream != 0 and ops.SCHMIDT_SIDE:   # never make the legacy default stream wait on / for others
-            self.side = ops.side_stream()
-        self.cur = cur
 
     def add(self, measure):
         psi = self.psi
@@ -242,9 +237,7 @@ class _DeferredSchmidt:
             if self.table is None:
                 self.table = torch.zeros((2 * psi.L + 2, 66), dtype=torch.float64, device=Cm.device)
             row = sum(1 for it in self.items if it[2] is not None)
-            if self.side is not None:
-                self.side.wait_stream(self.cur)
-            ops.svdvals_async(Cm, self.table[row], stream=self.side)
+            ops.svdvals_async(Cm, self.table[row])
             self.items.append((psi.pC, measure, row, None, Cm))
         else:
             self.items.append((psi.pC, measure, None, ops.svdvals(Cm), None))
@@ -256,8 +249,6 @@ class _DeferredSchmidt:
             host = ops.svdvals_small_batched(self.small).cpu().numpy()
             self.small = []
         elif self.table is not None:
-            if self.side is not None:
-                self.cur.wait_stream(self.side)
             host = self.table.cpu().numpy()
         diff = 0.0
         for pC, measure, row, S, Cm in self.items:

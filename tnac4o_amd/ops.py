@@ -10,39 +10,6 @@ from ._lib import lib, check, TnError
 
 QR_NB = 32
 _ws = {}
-_aux = {}
-SCHMIDT_SIDE = os.environ.get('TN_SCHMIDT_SIDE', '0') == '1'   # deferred Schmidt-value checks on a side stream (off: with 4
-# chains a second stream per chain costs 6-10 % of the step, measured; on the chain's own stream the launch is still asynchronous)
-LOOKAHEAD = os.environ.get('TN_QR_LOOKAHEAD', '0') == '1'      # tn_qr look-ahead on a second stream per chain (off: no gain measured)
-
-
-def register_aux_stream(main, aux):
-    """Pair a chain's stream with the side stream tn_qr may use for its look-ahead (parallel.run_concurrent does this for
-    the streams it creates, so the mapping of chains to hardware queues is deterministic)."""
-    _aux[(main.device.index, main.cuda_stream)] = aux
-
-
-def side_stream():
-    """The side stream paired with the current stream (created on first use): used for work that is off a chain's critical
-    path (deferred Schmidt-value checks, tn_qr's look-ahead when enabled)."""
-    cur = torch.cuda.current_stream()
-    key = (cur.device.index, cur.cuda_stream)
-    a = _aux.get(key)
-    if a is None:
-        a = _aux[key] = torch.cuda.Stream()
-    return a
-
-
-def aux_stream():
-    """The side stream paired with the current stream (created on first use), or None when look-ahead is disabled."""
-    if not LOOKAHEAD:
-        return None
-    cur = torch.cuda.current_stream()
-    key = (cur.device.index, cur.cuda_stream)
-    a = _aux.get(key)
-    if a is None:
-        a = _aux[key] = torch.cuda.Stream()
-    return a
 
 
 try:                                   # raw handle of the current stream without building a Stream object (and without the
@@ -222,14 +189,12 @@ def qr_into(T, Q, R, overwrite=False, nb=None, rank_tol=0.0):
     wsb = L.tn_qr_ws_bytes(m, n, nb)
     ws = workspace(wsb, 0)
     keff = C.c_int64(min(m, n))
-    aux = aux_stream() if (nb == 32 and m >= 2048 and min(m, n) >= 128) else None
     src = T
     for attempt in range(2):
         if not overwrite:
             T = src.clone(memory_format=torch.preserve_format)
         rc = L.tn_qr(T.data_ptr(), T.stride(0), T.stride(1), m, n, Q.data_ptr(), Q.stride(0), Q.stride(1), R.data_ptr(),
-                     R.stride(0), R.stride(1), nb, float(rank_tol), C.byref(keff), ws.data_ptr(), wsb, _stream(),
-                     C.c_void_p(aux.cuda_stream) if aux is not None else None)
+                     R.stride(0), R.stride(1), nb, float(rank_tol), C.byref(keff), ws.data_ptr(), wsb, _stream())
         # -7: a single-launch panel step gave up at a barrier (results invalid, input overwritten); the stream has been taken off
         # those launch forms, so a second run from the untouched source takes the six-launch chain
         if rc != -7 or overwrite or attempt == 1:
@@ -240,7 +205,7 @@ def qr_into(T, Q, R, overwrite=False, nb=None, rank_tol=0.0):
 
 def panel_orth(X, method=0, state=False, out=None):
     """The panel step of tn_qr on its own (tn_panel_orth): an orthonormal basis of the column space of the (strided) n x b panel X,
-    b <= 32.  method 0: iterated Cholesky-QR with deferral (what tn_qr uses), 1: Householder TSQR.  With state=True also returns
+    b <= 32.  method must be 0: iterated Cholesky-QR with deferral (what tn_qr uses).  With state=True also returns
     the panel's state record (list of 9 ints, see include/tnpeps.h) and max|X^T X - I| before each pass (synchronises)."""
     _need_gpu(X)
     n, b = X.shape
@@ -373,14 +338,12 @@ def svdvals(Cm, _preconditioned=False):
     return out
 
 
-def svdvals_async(Cm, out66, stream=None):
+def svdvals_async(Cm, out66):
     """Schmidt values of a centre matrix with both dimensions <= 64 into the device buffer out66 (66 doubles: 64 values
-    sorted descending, sweeps, converged flag) without synchronising (tn_svdvals_async).  `stream`: a torch stream to launch
-    on instead of the current one (the caller orders it after the producer of Cm and keeps Cm alive until it joins)."""
+    sorted descending, sweeps, converged flag) without synchronising (tn_svdvals_async)."""
     _need_gpu(Cm)
     k, n = Cm.shape
-    st = C.c_void_p(stream.cuda_stream) if stream is not None else _stream()
-    check(lib().tn_svdvals_async(Cm.data_ptr(), Cm.stride(0), Cm.stride(1), k, n, out66.data_ptr(), st))
+    check(lib().tn_svdvals_async(Cm.data_ptr(), Cm.stride(0), Cm.stride(1), k, n, out66.data_ptr(), _stream()))
 
 
 def svdvals_small_batched(mats):

@@ -73,7 +73,6 @@ def run_concurrent(fns):
     # included, so with 4 chains + the default stream two chains end up on one queue (measured: 4 queues 4.48 s, 2 queues 4.65 s,
     # 8 or 16 queues 2.90 s per step; the round-2 form with fresh pool streams on every call happened to dodge the collision until
     # the pool wrapped, every 8th call).  tnac4o_amd/__init__.py therefore asks for 8 queues before the runtime starts.
-    from . import ops
     import tnac4o_amd as _pkg
     if _pkg.HIP_STARTED_BEFORE_IMPORT and n > 3 and not getattr(run_concurrent, '_warned', False):
         run_concurrent._warned = True
@@ -84,16 +83,6 @@ def run_concurrent(fns):
     streams = _CHAIN_STREAMS.get(key)
     if streams is None:
         streams = _CHAIN_STREAMS[key] = _make_chain_streams(n)
-    # side streams (deferred Schmidt-value checks; tn_qr's look-ahead when enabled), taken right after the chains' own streams
-    # so that the pairing with hardware queues is the same on every call (torch hands out pool streams round-robin, pool
-    # stream k sits on hardware queue k mod 4): chain i's side stream is rotated by TN_AUX_ROT so that it does not share a
-    # queue with its own chain
-    if ops.LOOKAHEAD or ops.SCHMIDT_SIDE:
-        import os
-        rot = int(os.environ.get('TN_AUX_ROT', '2'))
-        side = [torch.cuda.Stream() for _ in range(n)]
-        for i in range(n):
-            ops.register_aux_stream(streams[i], side[(i + rot) % n])
     out, err = [None] * n, [None] * n
     # The caller's pending work must be visible to the chains: wait for it on the HOST.  streams[i].wait_stream(current)
     # would record an event on the (legacy) default stream, after which every launch of the chain pays for a dependency on

@@ -1,4 +1,4 @@
-"""Timing diagnostics of eig_small (third form): TN_EIG_DBG bit 0 = no J update, bit 1 = no G update, bit 2 = no look-ahead arithmetic
+"""Timing diagnostics of eig_small (eig_small3_kernel): TN_EIG_DBG bit 0 = no J update, bit 1 = no G update, bit 2 = no look-ahead arithmetic
 (rotations forced "on" so that every step runs).  Results are meaningless with a non-zero value; only the time per launch matters."""
 import ctypes as C
 import os

@@ -1,6 +1,5 @@
-"""The panel step of tn_qr on its own (tn_panel_orth): iterated Cholesky-QR (method 0) against the Householder TSQR (method 1)
-on well-conditioned, graded, nearly dependent, rank-deficient and badly scaled panels: orthonormality, span residual, passes,
-time per panel."""
+"""The panel step of tn_qr on its own (tn_panel_orth, iterated Cholesky-QR) on well-conditioned, graded, nearly dependent,
+rank-deficient and badly scaled panels: orthonormality, span residual, passes, time per panel."""
 import ctypes as C
 import os
 import sys
@@ -76,25 +75,22 @@ def main():
         Y, st, devh = panel_orth(X, 0, state=True)
         assert torch.equal(X, Xc), 'input modified'
         o0, r0 = quality(X, Y)
-        Y1 = panel_orth(X, 1)
-        o1, r1 = quality(X, Y1)
-        print('%-40s cholqr orth %.1e res %.1e passes %d defer %d refill %d fallback %d dev %s | tsqr orth %.1e res %.1e'
-              % (name, o0, r0, st[3], st[6], st[7], st[8], ' '.join('%.0e' % d for d in devh[:st[3] + 1]), o1, r1), flush=True)
+        print('%-40s cholqr orth %.1e res %.1e passes %d defer %d refill %d fallback %d dev %s'
+              % (name, o0, r0, st[3], st[6], st[7], st[8], ' '.join('%.0e' % d for d in devh[:st[3] + 1])), flush=True)
         worst = max(worst, o0, r0 if 'zero' not in name else 0.0)
     print('worst', worst)
     # timing
     for (n, b) in [(16384, 32), (8192, 32), (4096, 32), (1024, 32), (256, 32)]:
         X = torch.randn(n, b, dtype=torch.float64, device=dev)
         Y = torch.empty_like(X)
-        for method in (0, 1):
-            for _ in range(3):
-                panel_orth(X, method, out=Y)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(200):
-                panel_orth(X, method, out=Y)
-            torch.cuda.synchronize()
-            print('%6d x %2d  %s  %.1f us / panel' % (n, b, ('cholqr', 'tsqr')[method], 1e6 * (time.perf_counter() - t0) / 200), flush=True)
+        for _ in range(3):
+            panel_orth(X, 0, out=Y)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(200):
+            panel_orth(X, 0, out=Y)
+        torch.cuda.synchronize()
+        print('%6d x %2d  cholqr  %.1f us / panel' % (n, b, 1e6 * (time.perf_counter() - t0) / 200), flush=True)
     st = (C.c_uint64 * 8)()
     check(lib().tn_panel_stats(st, 0))
     print('stats', list(st))
