@@ -938,7 +938,7 @@ print('TALL_OK' if ok else 'TALL_FAIL')
 
 def test_tall_panels_single_launch_when_admitted(ops):
     """Panels of more than 8192 rows (up to 64 workgroups) take the single-launch form when the co-residency budget admits them
-    (csrc/cholqr.hip: cq_big_admit): in a fresh process with one stream they always are -- same bits as the six-launch chain
+    (csrc/fused.hip: FusedTallLaunch): in a fresh process with one stream they always are -- same bits as the six-launch chain
     (TN_PANEL_FUSED_BIG=0), and the statistics show which form ran."""
     import subprocess
     import sys

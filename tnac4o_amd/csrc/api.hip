@@ -62,7 +62,6 @@ int qr_batched(hipStream_t, double*, int64_t, int64_t, int64_t, int64_t, double*
 int svd_trunc_batched(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*,
                       double*, int64_t, int64_t, int64_t*, double*, int*, int*, int64_t, int64_t, int64_t, int64_t, int64_t, void*, int64_t);
 int svd_vals_batched(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*, int*, int*, int64_t, int64_t, void*, int64_t);
-int smallqr_stats(hipStream_t st, unsigned long long* out4, int reset);
 
 }  // namespace tn
 

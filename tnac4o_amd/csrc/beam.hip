@@ -7,34 +7,9 @@
 // replaced by its non-zero factor F[s,l,u] with the index maps dmap/rmap, so Pn[s] = F[s,l,u] * T2[dmap[s], rmap[s]].
 // The negative-probability rule and normalisation of tnac4o.py:1795-1807 are applied in the same kernel.
 #include "common.h"
+#include "devprim.h"
 
 namespace tn {
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) red[tid] += red[tid + k];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ double block_min(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) red[tid] = fmin(red[tid], red[tid + k]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
 
 __global__ __launch_bounds__(256) void calc_pn_kernel(const double* __restrict__ T1, const double* __restrict__ RR,
                                                       const double* __restrict__ F, const int32_t* __restrict__ dmap,
@@ -70,17 +45,17 @@ __global__ __launch_bounds__(256) void calc_pn_kernel(const double* __restrict__
         sP[s] = v;
         mn = fmin(mn, v);
     }
-    double mPn = block_min(mn, red);
+    double mPn = block_tree_min(mn, red);
     if (mPn < 0.0) {                                   // tnac4o.py:1796-1799
         const double a = fabs(mPn);
         double cnt = 0.0;
         for (int s = tid; s < q; s += 256)
             if (sP[s] < a) { sP[s] = a; cnt += 1.0; }
-        mPn *= block_sum(cnt, red);
+        mPn *= block_tree_sum(cnt, red);
     }
     double part = 0.0;
     for (int s = tid; s < q; s += 256) part += sP[s];
-    const double no = block_sum(part, red);
+    const double no = block_tree_sum(part, red);
     double* out = P + kk * q;
     if (no > 0.0) {                                    // tnac4o.py:1800-1803
         const double inv = 1.0 / no;

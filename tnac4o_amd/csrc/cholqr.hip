@@ -28,11 +28,11 @@
 // deadlock.  A launch that finds the panel converged returns at once (~3 us).
 #include <stdlib.h>
 
-#include <map>
 #include <mutex>
 #include <vector>
 
 #include "common.h"
+#include "devprim.h"
 
 // -DTN_CLOCKS: thread 0 of the last workgroup of a launch records the 100 MHz wall clock at phase boundaries (diagnostics only)
 #ifdef TN_CLOCKS
@@ -58,10 +58,6 @@ typedef double d4c __attribute__((ext_vector_type(4)));
 constexpr int CQ_RB = 256;            // rows per workgroup
 constexpr int CQ_P = 33;              // LDS pitch of the row tile
 constexpr int CQ_PART = 768;          // per-block partial Gram: tiles (0,0), (0,1), (1,1) of 16 x 16
-constexpr int CQ_MAXPASS = 4;         // substitution passes enqueued per panel (later ones return at once when converged)
-constexpr double CQ_THETA = 1e-10;    // deferral threshold on pivot / squared column norm
-constexpr double CQ_DONE = 5e-15;     // Gram matrix = identity to rounding: converged
-constexpr double CQ_LAST = 1e-8;      // below this one more pass lands at rounding level without another check
 
 struct CqState {
     int counter;          // arrival ticket of the workgroups of the launch in flight
@@ -79,42 +75,6 @@ struct CqState {
 };
 constexpr int CQ_STATE_BYTES = 256;
 static_assert(sizeof(CqState) <= CQ_STATE_BYTES, "state block too small");
-
-__device__ __forceinline__ double cq_readlane(double v, int lane) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, lane);
-    hi = __builtin_amdgcn_readlane(hi, lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double cq_rsqrt2(double x) {      // hardware seed (~2^-26) + two Newton steps
-    double r = __builtin_amdgcn_rsq(x);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
-// acc -= a * b, pinned in program order: left to itself the compiler sinks the rank-1 updates of the unrolled factorisation
-// into 31-long dependent chains at the point of use and spills the multipliers it keeps alive for them
-__device__ __forceinline__ void cq_fnma(double& acc, double a, double b) {
-    asm volatile("v_fma_f64 %0, -%1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ double cq_hash_unit(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return ((double)(x >> 11) * (1.0 / 9007199254740992.0)) - 0.5;
-}
-__device__ __forceinline__ void cq_block_rows(int64_t nrows, int nblk, int blk, int64_t& r0, int& nr) {
-    const int64_t base = nrows / nblk, rem = nrows % nblk;
-    r0 = blk * base + (blk < rem ? blk : rem);
-    nr = (int)(base + (blk < rem ? 1 : 0));
-}
-
-__device__ __forceinline__ double cq_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// What the workgroups publish to the last one (partial Gram matrices, block exponents) is written with agent-scope stores:
-// they go through to memory, so the publisher only waits for their completion before it takes its ticket -- a release
-// fence would also write back every dirty line of the XCD's L2 (the tile just stored: 3.6 us measured against ~1).
-__device__ __forceinline__ void cq_st(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void cq_sti(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void cq_publish_wait() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_waitcnt(0); }
-__device__ __forceinline__ int cq_ldi(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // Partial Gram of the 256 x 32 LDS tile T (pitch CQ_P): wave w covers rows 64w .. 64w+63 on the matrix cores, the four
 // partials meet in the LDS scratch S (4 x 768 doubles; callers that are done with the tile pass T itself) and their sum goes
@@ -140,18 +100,17 @@ __device__ __forceinline__ void cq_block_gram(const double* T, double* S, double
         sp[512 + i * 16 + li] = g11[r];
     }
     __syncthreads();
-    for (int e = tid; e < CQ_PART; e += 256) cq_st(part + e, (S[e] + S[CQ_PART + e]) + (S[2 * CQ_PART + e] + S[3 * CQ_PART + e]));
+    for (int e = tid; e < CQ_PART; e += 256) st_agent(part + e, (S[e] + S[CQ_PART + e]) + (S[2 * CQ_PART + e] + S[3 * CQ_PART + e]));
 }
 
-// diagnostic counters (tn_panel_stats / tn_panel_stats_stream), kept PER STREAM -- slot of the launching stream, CQ_STAT_SLOTS for the
+// diagnostic counters (tn_panel_stats / tn_panel_stats_stream), kept PER STREAM -- slot of the launching stream, CHOLQR_SLOTS for the
 // streams beyond that many; concurrent chains do not mix their counts -- one 64-bit word each, no packed sub-fields that could carry
 // into each other:
 //   [0] panels  [1] substitution passes applied  [2] deferred pivots  [3] refilled columns  [4] Householder fallbacks
 //   [5] panels with >= 3 passes  [6] panels with >= 4 passes  [7] panel elements x passes applied by the six-launch chain (each such
 //   pass reads and writes the panel: 16 bytes per element)  [8] the same for the single-launch form (the tile stays in LDS: flops only)
 //   [9] panels handled by the single-launch form  [10] single-launch panels that gave up at an in-kernel barrier (time-outs)
-constexpr int CQ_STAT_SLOTS = 64;
-__device__ unsigned long long cq_stats[(CQ_STAT_SLOTS + 1) * 16];
+__device__ unsigned long long cq_stats[(CHOLQR_SLOTS + 1) * 16];
 // one thread, once per panel; the adds do not return a value, so the wave does not wait for them
 __device__ __forceinline__ void cq_count(int slot, int passes, int ndefer, int nrefill, bool fallback, long long elems, bool single_launch = false) {
     unsigned long long* cs = cq_stats + slot * 16;
@@ -164,16 +123,6 @@ __device__ __forceinline__ void cq_count(int slot, int passes, int ndefer, int n
     if (fallback) atomicAdd(&cs[4], 1ull);
     if (passes >= 3) atomicAdd(&cs[5], 1ull);
     if (passes >= 4) atomicAdd(&cs[6], 1ull);
-}
-
-// 256-thread sum through LDS (two barriers); red: >= 4 doubles
-__device__ __forceinline__ double cq_block_sum(double v, double* red, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // Last resort, one workgroup: Householder QR of the whole panel in global memory (dgeqr2 + dorg2r, column by column).
@@ -193,7 +142,7 @@ __device__ void cq_fallback_householder(const double* X, int64_t xrs, int64_t xc
     for (int j = 0; j < b; ++j) {
         double s = 0.0;
         for (int64_t r = j + 1 + tid; r < nrows; r += 256) { const double y = Y[r * rs + j * cs]; s += y * y; }
-        s = cq_block_sum(s, red, tid);
+        s = block_sum(s, red, tid);
         const double alpha = Y[j * rs + j * cs];
         double tau = 0.0;
         if (s > 1e-300) {                                   // dlarfg: nothing below the diagonal -> H = I
@@ -206,7 +155,7 @@ __device__ void cq_fallback_householder(const double* X, int64_t xrs, int64_t xc
             for (int c = j + 1; c < b; ++c) {
                 double w = 0.0;
                 for (int64_t r = j + 1 + tid; r < nrows; r += 256) w += Y[r * rs + j * cs] * Y[r * rs + c * cs];
-                w = cq_block_sum(w, red, tid);
+                w = block_sum(w, red, tid);
                 if (tid == 0) wv[c] = tau * (w + Y[j * rs + c * cs]);
                 __syncthreads();
                 const double tw = wv[c];
@@ -224,7 +173,7 @@ __device__ void cq_fallback_householder(const double* X, int64_t xrs, int64_t xc
         for (int c = j + 1; c < b; ++c) {                  // apply H_j to the columns already formed
             double w = 0.0;
             for (int64_t r = j + 1 + tid; r < nrows; r += 256) w += Y[r * rs + j * cs] * Y[r * rs + c * cs];
-            w = cq_block_sum(w, red, tid);
+            w = block_sum(w, red, tid);
             // row j of the columns formed so far is zero (they live in rows > j), so v^T q = w
             const double tw = tau * w;
             for (int64_t r = j + 1 + tid; r < nrows; r += 256) Y[r * rs + c * cs] -= Y[r * rs + j * cs] * tw;
@@ -238,11 +187,6 @@ __device__ void cq_fallback_householder(const double* X, int64_t xrs, int64_t xc
         __threadfence();
         __syncthreads();
     }
-}
-
-// acc -= s * v with the first factor wave-uniform (an SGPR pair), pinned in program order like cq_fnma
-__device__ __forceinline__ void cq_fnma_s(double& acc, double s_uniform, double v) {
-    asm volatile("v_fma_f64 %0, -%1, %2, %0" : "+v"(acc) : "s"(s_uniform), "v"(v));
 }
 
 // Slots of the reconstruction buffer `lu` (7 x 1024 doubles, 32 x 32 row-major each): the top block of the orthonormal panel as
@@ -278,7 +222,7 @@ __device__ __forceinline__ void cq_lu(const double* ytop, bool coherent_loads, i
     {   // the matrix, padded with an identity block that is never eliminated: one coalesced round trip
         double v[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) { const int e = tid + 256 * t; v[t] = coherent_loads ? cq_ld(ytop + e) : ytop[e]; }
+        for (int t = 0; t < 4; ++t) { const int e = tid + 256 * t; v[t] = coherent_loads ? ld_agent(ytop + e) : ytop[e]; }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int e = tid + 256 * t, r = e >> 5, c = e & 31;
@@ -296,14 +240,14 @@ __device__ __forceinline__ void cq_lu(const double* ytop, bool coherent_loads, i
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int gi = c0 + i;
-            const double bii = cq_readlane(u[i], i);
+            const double bii = readlane_f64(u[i], i);
             const bool live = gi < b;                      // uniform
             const double sgn = (bii >= 0.0) ? -1.0 : 1.0, piv = bii - sgn, rp = fast_rcp(live ? piv : 1.0);
             const double lv = (live && r > gi) ? u[i] * rp : 0.0;
 #pragma unroll
             for (int c = i + 1; c < 16; ++c) {
-                const double uic = cq_readlane(u[c], i);
-                cq_fnma_s(u[c], uic, lv);
+                const double uic = readlane_f64(u[c], i);
+                fnma_s(u[c], uic, lv);
             }
             l[i] = (r > gi) ? lv : l[i];
             u[i] = (r > gi) ? 0.0 : ((r == gi && live) ? piv : u[i]);
@@ -482,23 +426,33 @@ __device__ __forceinline__ void cq_lu(const double* ytop, bool coherent_loads, i
     __syncthreads();
 }
 
-// Tail of a launch, run by the last workgroup to arrive: sum the partial Gram matrices (block order, optional per-block
-// power-of-two weights), measure the distance from the identity, decide, and factor G = R^T R with deferral (wave 0).
-// Gs: LDS 32 x 33, Rs: LDS 32 x 32 (16-byte aligned).  pass = number of passes applied to the panel whose Gram matrix this is.  Returns 1 when the caller
-// decision (0: factor again, 1: converged, 2: out of passes; all threads get the same value).
-__device__ __forceinline__ int cq_tail(const double* part, const int* bexp, int nblk, int b, int pass, CqState* stt, double* Rg, double* Gs,
-                                       double* Rs, int maxpass, int tid, long long elems, int slot) {
-    __shared__ int s_dec;
-    const int lane = tid & 63;
-    // exponents of pass 0: block weights 4^(e_blk - emax); every wave finds emax itself (no barrier)
-    int emax = 0;
-    if (bexp) {
-        int e = -100000;
-        for (int i = lane; i < nblk; i += 64) { const int x = cq_ldi(bexp + i); e = x > e ? x : e; }
+// largest of the block exponents of pass 0 (block weights 4^(e_blk - emax)); every wave finds it itself (no barrier)
+__device__ __forceinline__ int cq_max_exponent(const int* bexp, int nblk, int lane) {
+    int e = -100000;
+    for (int i = lane; i < nblk; i += 64) { const int x = ldi_agent(bexp + i); e = x > e ? x : e; }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(e, o, 64); e = y > e ? y : e; }
-        emax = e;
-    }
+    for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(e, o, 64); e = y > e ? y : e; }
+    return e;
+}
+
+// Tail of a Cholesky-QR pass: sum the partial Gram matrices (block order, optional per-block power-of-two weights), measure the
+// distance from the identity, decide, and factor G = R^T R with deferral (wave 0).  One text for both forms, so that they give the
+// same bits:
+//   FUSED == false (six-launch chain; run by the last workgroup of a launch to arrive): the factor goes to Rf (LDS, 32 x 32, 16-byte
+//     aligned) and from there, with the reciprocals of its diagonal, to global memory Rg; the decision to s_out[0]; state block and
+//     statistics are always kept.
+//   FUSED == true (single-launch form; run by EVERY workgroup on the same published partials): the factor stays in Rf (32 x 32
+//     row-major + the 32 reciprocals of its diagonal); s_out (LDS, 4 ints): [0] decision, [1] final_next, [2] dead-column mask,
+//     [3] emax (pass 0); only `writer` (workgroup 0) keeps the panel's state block and the statistics.  emax_known > -100000: `part`
+//     is ONE pre-summed matrix (sliced reduction, see cq_slice_reduce) of a pass-0 Gram whose weights were applied with that exponent.
+// Gs: LDS 32 x 33.  pass = number of passes applied to the panel whose Gram matrix this is.  Decision: 0 factor again, 1 converged,
+// 2 out of passes.  Ends with a barrier.
+template <bool FUSED>
+__device__ __forceinline__ void cq_tail_any(const double* part, const int* bexp, int nblk, int b, int pass, CqState* stt, bool writer, double* Rg,
+                                            double* Gs, double* Rf, int* s_out, int maxpass, int tid, long long elems, int slot, int emax_known) {
+    const int lane = tid & 63;
+    int emax = (FUSED && emax_known > -100000) ? emax_known : 0;
+    if (bexp) emax = cq_max_exponent(bexp, nblk, lane);
     {   // thread tid sums entries tid, tid + 256, tid + 512 over the blocks, in block order; 96 loads in flight per thread
         double acc[3] = {0.0, 0.0, 0.0};
         for (int blk0 = 0; blk0 < nblk; blk0 += 32) {
@@ -508,9 +462,9 @@ __device__ __forceinline__ int cq_tail(const double* part, const int* bexp, int 
             for (int u = 0; u < 32; ++u) {
                 const int blk = blk0 + u;
                 const bool in = blk < nblk;
-                ex[u] = (bexp && in) ? cq_ldi(bexp + blk) : emax;
+                ex[u] = (bexp && in) ? ldi_agent(bexp + blk) : emax;
 #pragma unroll
-                for (int q = 0; q < 3; ++q) v[q][u] = in ? cq_ld(part + (int64_t)blk * CQ_PART + tid + 256 * q) : 0.0;
+                for (int q = 0; q < 3; ++q) v[q][u] = in ? ld_agent(part + (int64_t)blk * CQ_PART + tid + 256 * q) : 0.0;
             }
 #pragma unroll
             for (int u = 0; u < 32; ++u) {
@@ -549,19 +503,25 @@ __device__ __forceinline__ int cq_tail(const double* part, const int* bexp, int 
         if (pass > 0 && dev <= CQ_DONE) dec = 1;
         else if (pass >= maxpass) dec = 2;
         if (lane == 0) {
-            stt->dev_hist[pass <= CQ_MAXPASS ? pass : CQ_MAXPASS] = dev;
-            if (bexp) stt->emax = emax;
-            s_dec = dec;
-        }
-        if (dec != 0) {
-            if (lane == 0) {
-                stt->done = 1;
-                stt->final_next = 0;
-                stt->dead = 0u;
-                if (dec == 2) stt->fallback = 1;
-                cq_count(slot, pass, stt->ndefer_total, stt->nrefill_total, dec == 2, elems);
+            if constexpr (FUSED) {
+                s_out[0] = dec;
+                s_out[3] = emax;
+                if (dec != 0) { s_out[1] = 0; s_out[2] = 0; }
             }
-        } else {
+            if (writer) {
+                stt->dev_hist[pass <= CQ_MAXPASS ? pass : CQ_MAXPASS] = dev;
+                if (bexp || (FUSED && emax_known > -100000)) stt->emax = emax;
+                if constexpr (!FUSED) s_out[0] = dec;
+                if (dec != 0) {
+                    stt->done = 1;
+                    stt->final_next = 0;
+                    stt->dead = 0u;
+                    if (dec == 2) stt->fallback = 1;
+                    cq_count(slot, pass, stt->ndefer_total, stt->nrefill_total, dec == 2, elems, FUSED);
+                }
+            }
+        }
+        if (dec == 0) {
             // ---- Cholesky, right-looking.  Lane k holds column k of the trailing matrix; row j of R (lane k: R[j][k]) goes
             // to LDS, from where every lane reads the multipliers R[j][i] as broadcasts (a cross-lane read per multiplier
             // would cost three VALU instructions per update instead of one).  Only the multiplier of row j+1, which the next
@@ -578,45 +538,65 @@ __device__ __forceinline__ int cq_tail(const double* part, const int* bexp, int 
             double dkk = 1.0;
 #pragma unroll
             for (int j = 0; j < 32; ++j) {
-                const double d = cq_readlane(g[j], j), thr = cq_readlane(thr_k, j);
+                const double d = readlane_f64(g[j], j), thr = readlane_f64(thr_k, j);
                 const bool ok = d > thr;                  // uniform
                 badmask |= ok ? 0u : (1u << j);
-                const double rinv = cq_rsqrt2(ok ? d : 1.0);
+                const double rinv = rsqrt2(ok ? d : 1.0);
                 double r = (k >= j) ? g[j] * (ok ? rinv : 0.0) : 0.0;
                 r = (!ok && k == j) ? 1.0 : r;
                 if (j == k) dkk = r;
-                if (lane < 32) Rs[j * 32 + k] = r;
+                if (lane < 32) Rf[j * 32 + k] = r;
                 if (j < 31) {
-                    const double m1 = cq_readlane(r, j + 1);
+                    const double m1 = readlane_f64(r, j + 1);
                     const int i0 = (j + 3) & ~1;          // 16-byte pairs (i, i+1) with i even; an odd row j+2 goes alone
                     double2 m[16];
                     double m2 = 0.0;
-                    if (j + 2 < 32 && ((j + 2) & 1)) m2 = Rs[j * 32 + j + 2];
+                    if (j + 2 < 32 && ((j + 2) & 1)) m2 = Rf[j * 32 + j + 2];
 #pragma unroll
-                    for (int i = i0; i < 32; i += 2) m[i >> 1] = *reinterpret_cast<const double2*>(&Rs[j * 32 + i]);   // all reads in flight
-                    cq_fnma(g[j + 1], m1, r);
-                    if (j + 2 < 32 && ((j + 2) & 1)) cq_fnma(g[j + 2], m2, r);
+                    for (int i = i0; i < 32; i += 2) m[i >> 1] = *reinterpret_cast<const double2*>(&Rf[j * 32 + i]);   // all reads in flight
+                    fnma(g[j + 1], m1, r);
+                    if (j + 2 < 32 && ((j + 2) & 1)) fnma(g[j + 2], m2, r);
 #pragma unroll
                     for (int i = i0; i < 32; i += 2) {
-                        cq_fnma(g[i], m[i >> 1].x, r);
-                        cq_fnma(g[i + 1], m[i >> 1].y, r);
+                        fnma(g[i], m[i >> 1].x, r);
+                        fnma(g[i + 1], m[i >> 1].y, r);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);        // keep the updates of step j in step j (the scheduler otherwise
             }                                             // sinks them into 31-long dependent chains and spills the multipliers)
             __builtin_amdgcn_wave_barrier();
-            for (int e = lane; e < 1024; e += 64) Rg[e] = Rs[e];
-            if (lane < 32) Rg[1024 + k] = fast_rcp(dkk);  // reciprocal diagonal for the substitution
+            if constexpr (!FUSED)
+                for (int e = lane; e < 1024; e += 64) Rg[e] = Rf[e];
+            if (lane < 32) (FUSED ? Rf : Rg)[1024 + k] = fast_rcp(dkk);      // reciprocal diagonal for the substitution
             if (lane == 0) {
-                const int ndefer = __popc(badmask & ~deadmask);
-                stt->final_next = (pass > 0 && dev <= CQ_LAST && badmask == 0u) ? 1 : 0;
-                stt->dead = deadmask;
-                stt->ndefer_total += ndefer;
-                stt->nrefill_total += __popc(deadmask);
+                if constexpr (FUSED) {
+                    const int fin = (pass > 0 && dev <= CQ_LAST && badmask == 0u) ? 1 : 0;
+                    s_out[1] = fin;
+                    s_out[2] = (int)deadmask;
+                    if (writer) {
+                        stt->final_next = fin;
+                        stt->dead = deadmask;
+                        stt->ndefer_total += __popc(badmask & ~deadmask);
+                        stt->nrefill_total += __popc(deadmask);
+                    }
+                } else {
+                    const int ndefer = __popc(badmask & ~deadmask);
+                    stt->final_next = (pass > 0 && dev <= CQ_LAST && badmask == 0u) ? 1 : 0;
+                    stt->dead = deadmask;
+                    stt->ndefer_total += ndefer;
+                    stt->nrefill_total += __popc(deadmask);
+                }
             }
         }
     }
     __syncthreads();
+}
+
+// the tail of a launch of the six-launch chain; returns the decision (all threads get the same value)
+__device__ __forceinline__ int cq_tail(const double* part, const int* bexp, int nblk, int b, int pass, CqState* stt, double* Rg, double* Gs,
+                                       double* Rs, int maxpass, int tid, long long elems, int slot) {
+    __shared__ int s_dec;
+    cq_tail_any<false>(part, bexp, nblk, b, pass, stt, true, Rg, Gs, Rs, &s_dec, maxpass, tid, elems, slot, -100001);
     return s_dec;                                          // 0: another pass, 1: converged, 2: fallback flagged
 }
 
@@ -673,11 +653,11 @@ __global__ __launch_bounds__(256) void cq_gram_kernel(const double* __restrict__
     if (active && *active == 0) return;                      // the factorisation this panel belongs to has stopped (device-side exit test, qr.hip)
     int64_t r0;
     int nr;
-    cq_block_rows(nrows, nblk, blk, r0, nr);
+    block_rows(nrows, nblk, blk, r0, nr);
     const int ex = cq_load_scaled_tile(X, rs, cs, r0, nr, b, T, red, tid);
     cq_block_gram(T, T, part + (int64_t)blk * CQ_PART, tid);
-    if (tid == 0) cq_sti(bexp + blk, ex);
-    cq_publish_wait();
+    if (tid == 0) sti_agent(bexp + blk, ex);
+    publish_wait();
     __syncthreads();
     if (tid == 0) s_ticket = atomicAdd(&stt->counter, 1);
     __syncthreads();
@@ -713,11 +693,11 @@ __device__ __forceinline__ void cq_substitute(double* T, const double* Rs, int t
             const double xj = x[j] * dc;
             x[j] = xj;
             if (j < 31) {
-                if ((j + 1) & 1) cq_fnma(x[j + 1], xj, sc);
+                if ((j + 1) & 1) fnma(x[j + 1], xj, sc);
 #pragma unroll
                 for (int q = (j + 2) >> 1; q < 16; ++q) {
-                    cq_fnma(x[2 * q], xj, mc[q].x);
-                    cq_fnma(x[2 * q + 1], xj, mc[q].y);
+                    fnma(x[2 * q], xj, mc[q].x);
+                    fnma(x[2 * q + 1], xj, mc[q].y);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -728,7 +708,7 @@ __device__ __forceinline__ void cq_substitute(double* T, const double* Rs, int t
         if (deadmask) {
 #pragma unroll
             for (int j = 0; j < 32; ++j)
-                if ((deadmask >> j) & 1u) x[j] = (tid < nr) ? cq_hash_unit(seed + (uint64_t)(r0 + tid) * 64 + j) : 0.0;
+                if ((deadmask >> j) & 1u) x[j] = (tid < nr) ? hash_unit(seed + (uint64_t)(r0 + tid) * 64 + j) : 0.0;
         }
 #pragma unroll
         for (int j = 0; j < 32; ++j) T[tid * CQ_P + j] = x[j];
@@ -774,12 +754,12 @@ __global__ __launch_bounds__(256) void cq_pass_kernel(const double* Xsrc, int64_
     CQ_CLK(0);
     int64_t r0;
     int nr;
-    cq_block_rows(nrows, nblk, blk, r0, nr);
+    block_rows(nrows, nblk, blk, r0, nr);
     const double* src = first ? Xsrc : Y;
     const int64_t xrs = first ? srs : rs, xcs = first ? scs : cs;
     const bool colfast = (xcs == 1);
     if (launch_no >= 3) {                                 // 94 % of the third and 99.8 % of the fourth passes find the panel converged:
-        if (tid == 0) s_st[0] = cq_ldi(&stt->done);       // look before fetching the tile
+        if (tid == 0) s_st[0] = ldi_agent(&stt->done);       // look before fetching the tile
         __syncthreads();
         if (s_st[0]) return;
         __syncthreads();
@@ -788,7 +768,7 @@ __global__ __launch_bounds__(256) void cq_pass_kernel(const double* Xsrc, int64_
         // throws the tile away)
         double xv[32], rv[5];
         int sv = 0;
-        if (tid < 4) sv = cq_ldi(tid == 0 ? &stt->done : tid == 1 ? &stt->final_next : tid == 2 ? &stt->emax : (const int*)&stt->dead);
+        if (tid < 4) sv = ldi_agent(tid == 0 ? &stt->done : tid == 1 ? &stt->final_next : tid == 2 ? &stt->emax : (const int*)&stt->dead);
 #pragma unroll
         for (int u = 0; u < 5; ++u) rv[u] = (tid + 256 * u < 1056) ? Rg[tid + 256 * u] : 0.0;
 #pragma unroll
@@ -833,7 +813,7 @@ __global__ __launch_bounds__(256) void cq_pass_kernel(const double* Xsrc, int64_
     }
     if (!fin) cq_block_gram(T, T, part + (int64_t)blk * CQ_PART, tid);      // (its first barrier follows its reads of T)
     CQ_CLK(3);
-    cq_publish_wait();
+    publish_wait();
     __syncthreads();
     CQ_CLK(4);
     if (tid == 0) s_ticket = atomicAdd(&stt->counter, 1);
@@ -872,7 +852,7 @@ __device__ __forceinline__ void cq_post_tile(int blk, int nblk, int64_t nrows, i
     const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
     int64_t r0;
     int nr;
-    cq_block_rows(nrows, nblk, blk, r0, nr);
+    block_rows(nrows, nblk, blk, r0, nr);
     const bool xrow = (cs == 1);
     {
         double sv[3][4], xv[32];
@@ -997,7 +977,7 @@ __global__ __launch_bounds__(256) void cq_post_kernel(const double* X, int64_t x
     __shared__ int s_st[2];
     const int tid = threadIdx.x, blk = blockIdx.x;
     if (active && *active == 0) return;
-    if (tid == 0) { s_st[0] = cq_ldi(&stt->fallback); s_st[1] = cq_ldi(&stt->emax); }
+    if (tid == 0) { s_st[0] = ldi_agent(&stt->fallback); s_st[1] = ldi_agent(&stt->emax); }
     __syncthreads();
     if (!s_st[0]) {
         if (lu) cq_post_tile(blk, nblk, nrows, b, Y, rs, cs, W, wrs, wcs, Wq, lu, tile, Ss, tid);
@@ -1012,7 +992,7 @@ __global__ __launch_bounds__(256) void cq_post_kernel(const double* X, int64_t x
     __syncthreads();
     for (int e = tid; e < 1024; e += 256) {
         const int i = e >> 5, j = e & 31;
-        lu[CQ_LU_YTOP + e] = (i < b && j < b && i < nrows) ? cq_ld(Y + (int64_t)i * rs + j * cs) : 0.0;
+        lu[CQ_LU_YTOP + e] = (i < b && j < b && i < nrows) ? ld_agent(Y + (int64_t)i * rs + j * cs) : 0.0;
     }
     __threadfence();
     __syncthreads();
@@ -1027,13 +1007,13 @@ __global__ __launch_bounds__(256) void cq_post_kernel(const double* X, int64_t x
 }
 
 // ---- the whole panel step in ONE launch ------------------------------------------------------------------------------
-// For panels of up to CQ_FUSED_MAXBLK x 256 = 8192 rows -- and for taller ones, up to 16384 rows, when cq_big_admit lets them in -- the chain
+// For panels of up to CQ_FUSED_MAXBLK x 256 = 8192 rows -- and for taller ones, up to 16384 rows, when FusedTallLaunch (fused.hip) lets them in -- the chain
 // gram -> pass ... pass -> post  runs inside one kernel: every workgroup keeps its 256-row tile in
 // LDS from the first load to the last store (the six-launch form reloads and stores it in every launch), the workgroups meet at
 // in-kernel barriers (a monotone arrival counter polled by one lane, MI355X guide "Guideline 16": partials written with
 // agent-scope stores, drained, one atomic add per workgroup, relaxed agent-scope poll, agent-scope loads of the partials),
 // and after each barrier EVERY workgroup reduces the published partial Gram matrices, takes the decision and factors G itself
-// -- the same arithmetic in the same order as cq_tail, hence the same bits in every workgroup and the same result as the
+// -- the same text as the tail of the six-launch chain (cq_tail_any), hence the same bits in every workgroup and the same result as the
 // six-launch form -- so no second hand-off is needed to distribute R.  The Householder reconstruction is redundant in the same
 // way: workgroup 0 publishes the top 32 x 32 block of the panel next to its partial Gram matrix.
 // Co-residency: a workgroup needs a whole CU (127 KB of LDS) and only ever waits for workgroups of its OWN launch, so the launches in
@@ -1042,161 +1022,11 @@ __global__ __launch_bounds__(256) void cq_post_kernel(const double* X, int64_t x
 // other kernel on the device finishes without waiting for anyone.  Should a process be configured with more queues than that, the
 // spins are bounded (CQ_SPIN_LIMIT polls, seconds): a launch that gives up poisons its output with NaN and raises the sticky
 // stt->timeout, which later launches of the call honour.
-constexpr int CQ_FUSED_MAXBLK = 32;
-constexpr unsigned CQ_SPIN_LIMIT = 1u << 22;
 
-__device__ __forceinline__ bool cq_grid_barrier(int* counter, int target, int* s_flag, int tid, unsigned spin_limit = CQ_SPIN_LIMIT) {
-    cq_publish_wait();                                     // every wave: its agent-scope stores have completed
-    __syncthreads();
-    if (tid == 0) {
-        atomicAdd(counter, 1);
-        int ok = 1;
-        unsigned spins = 0;
-        while (cq_ldi(counter) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > spin_limit) { ok = 0; break; }
-        }
-        *s_flag = ok;
-    }
-    __syncthreads();
-    return *s_flag != 0;
-}
-
-// cq_tail for the single-launch form, run by EVERY workgroup on the same published partials: sum (block order, optional
-// per-block power-of-two weights), distance from the identity, decision, Cholesky with deferral.  The factor goes to Rf (LDS:
-// 32 x 32 row-major + the 32 reciprocals of its diagonal) instead of global memory.  s_out (LDS, 4 ints): [0] decision
-// (0 factor again, 1 converged, 2 out of passes), [1] final_next, [2] dead-column mask, [3] emax (pass 0).  Only `writer`
-// (workgroup 0) keeps the panel's state block and the statistics.  Ends with a barrier.
-// emax_known > -100000: `part` is ONE pre-summed matrix (sliced reduction, see cq_slice_reduce) of a pass-0 Gram whose weights were
-// applied with that exponent.
+// the tail of a pass of the single-launch form (see cq_tail_any)
 __device__ __forceinline__ void cq_tail_fused(const double* part, const int* bexp, int nblk, int b, int pass, CqState* stt, bool writer, double* Gs,
                                               double* Rf, int* s_out, int maxpass, int tid, long long elems, int slot, int emax_known = -100001) {
-    const int lane = tid & 63;
-    int emax = emax_known > -100000 ? emax_known : 0;
-    if (bexp) {
-        int e = -100000;
-        for (int i = lane; i < nblk; i += 64) { const int x = cq_ldi(bexp + i); e = x > e ? x : e; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(e, o, 64); e = y > e ? y : e; }
-        emax = e;
-    }
-    {
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (int blk0 = 0; blk0 < nblk; blk0 += 32) {
-            double v[3][32];
-            int ex[32];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) {
-                const int blk = blk0 + u;
-                const bool in = blk < nblk;
-                ex[u] = (bexp && in) ? cq_ldi(bexp + blk) : emax;
-#pragma unroll
-                for (int q = 0; q < 3; ++q) v[q][u] = in ? cq_ld(part + (int64_t)blk * CQ_PART + tid + 256 * q) : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 32; ++u) {
-                const double w = bexp ? ldexp(1.0, 2 * (ex[u] - emax)) : 1.0;
-#pragma unroll
-                for (int q = 0; q < 3; ++q) acc[q] = fma(w, v[q][u], acc[q]);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int e = tid + 256 * q, i = (e >> 4) & 15, j = e & 15;
-            const int gi = (q == 2 ? 16 : 0) + i, gj = (q == 0 ? 0 : 16) + j;
-            Gs[gi * CQ_P + gj] = acc[q];
-            if (q == 1) Gs[gj * CQ_P + gi] = acc[q];
-        }
-    }
-    __syncthreads();
-    if (tid < 64) {
-        const int k = lane & 31;
-        double g[32];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const double x = Gs[i * CQ_P + k];
-            g[i] = (i < b && k < b) ? x : ((i == k) ? 1.0 : 0.0);
-        }
-        double dev = 0.0;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const double x = fabs(g[i] - (i == k ? 1.0 : 0.0));
-            dev = (x == x) ? fmax(dev, x) : 1e300;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) dev = fmax(dev, __shfl_xor(dev, o, 64));
-        int dec = 0;
-        if (pass > 0 && dev <= CQ_DONE) dec = 1;
-        else if (pass >= maxpass) dec = 2;
-        if (lane == 0) {
-            s_out[0] = dec;
-            s_out[3] = emax;
-            if (dec != 0) { s_out[1] = 0; s_out[2] = 0; }
-            if (writer) {
-                stt->dev_hist[pass <= CQ_MAXPASS ? pass : CQ_MAXPASS] = dev;
-                if (bexp || emax_known > -100000) stt->emax = emax;
-                if (dec != 0) {
-                    stt->done = 1;
-                    stt->final_next = 0;
-                    stt->dead = 0u;
-                    if (dec == 2) stt->fallback = 1;
-                    cq_count(slot, pass, stt->ndefer_total, stt->nrefill_total, dec == 2, elems, true);
-                }
-            }
-        }
-        if (dec == 0) {
-            double gd = 0.0;
-#pragma unroll
-            for (int i = 0; i < 32; ++i) gd = (i == k) ? g[i] : gd;
-            const bool zero_k = !(gd > 1e-290) || !(gd < 1e300);
-            const unsigned deadmask = (unsigned)(__ballot(zero_k) & 0xffffffffull);
-            const double thr_k = zero_k ? 1e308 : CQ_THETA * gd;
-            unsigned badmask = 0u;
-            double dkk = 1.0;
-#pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                const double d = cq_readlane(g[j], j), thr = cq_readlane(thr_k, j);
-                const bool ok = d > thr;
-                badmask |= ok ? 0u : (1u << j);
-                const double rinv = cq_rsqrt2(ok ? d : 1.0);
-                double r = (k >= j) ? g[j] * (ok ? rinv : 0.0) : 0.0;
-                r = (!ok && k == j) ? 1.0 : r;
-                if (j == k) dkk = r;
-                if (lane < 32) Rf[j * 32 + k] = r;
-                if (j < 31) {
-                    const double m1 = cq_readlane(r, j + 1);
-                    const int i0 = (j + 3) & ~1;
-                    double2 m[16];
-                    double m2 = 0.0;
-                    if (j + 2 < 32 && ((j + 2) & 1)) m2 = Rf[j * 32 + j + 2];
-#pragma unroll
-                    for (int i = i0; i < 32; i += 2) m[i >> 1] = *reinterpret_cast<const double2*>(&Rf[j * 32 + i]);
-                    cq_fnma(g[j + 1], m1, r);
-                    if (j + 2 < 32 && ((j + 2) & 1)) cq_fnma(g[j + 2], m2, r);
-#pragma unroll
-                    for (int i = i0; i < 32; i += 2) {
-                        cq_fnma(g[i], m[i >> 1].x, r);
-                        cq_fnma(g[i + 1], m[i >> 1].y, r);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (lane < 32) Rf[1024 + k] = fast_rcp(dkk);
-            if (lane == 0) {
-                const int fin = (pass > 0 && dev <= CQ_LAST && badmask == 0u) ? 1 : 0;
-                s_out[1] = fin;
-                s_out[2] = (int)deadmask;
-                if (writer) {
-                    stt->final_next = fin;
-                    stt->dead = deadmask;
-                    stt->ndefer_total += __popc(badmask & ~deadmask);
-                    stt->nrefill_total += __popc(deadmask);
-                }
-            }
-        }
-    }
-    __syncthreads();
+    cq_tail_any<true>(part, bexp, nblk, b, pass, stt, writer, nullptr, Gs, Rf, s_out, maxpass, tid, elems, slot, emax_known);
 }
 
 // Sliced reduction of the published partial Gram matrices (launches of more than CQ_SLICE_FROM workgroups; an in-kernel barrier costs 1-2 us): workgroup w adds slice w of
@@ -1207,13 +1037,7 @@ constexpr int CQ_SLICE_FROM = 4;
 __device__ __forceinline__ int cq_slice_reduce(const double* part, const int* bexp, int nblk, int blk, double* gsum, int tid) {
     const int lane = tid & 63;
     int emax = 0;
-    if (bexp) {
-        int e = -100000;
-        for (int i = lane; i < nblk; i += 64) { const int x = cq_ldi(bexp + i); e = x > e ? x : e; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(e, o, 64); e = y > e ? y : e; }
-        emax = e;
-    }
+    if (bexp) emax = cq_max_exponent(bexp, nblk, lane);
     const int sl = (CQ_PART + nblk - 1) / nblk;            // <= 154 entries per workgroup
     const int e0 = blk * sl + tid;
     if (tid < sl && e0 < CQ_PART) {
@@ -1224,13 +1048,13 @@ __device__ __forceinline__ int cq_slice_reduce(const double* part, const int* be
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const bool in = b0 + u < nblk;
-                v[u] = in ? cq_ld(part + (int64_t)(b0 + u) * CQ_PART + e0) : 0.0;
-                ex[u] = (bexp && in) ? cq_ldi(bexp + b0 + u) : emax;
+                v[u] = in ? ld_agent(part + (int64_t)(b0 + u) * CQ_PART + e0) : 0.0;
+                ex[u] = (bexp && in) ? ldi_agent(bexp + b0 + u) : emax;
             }
 #pragma unroll
             for (int u = 0; u < 16; ++u) acc = fma(bexp ? ldexp(1.0, 2 * (ex[u] - emax)) : 1.0, v[u], acc);
         }
-        cq_st(gsum + e0, acc);
+        st_agent(gsum + e0, acc);
     }
     return emax;
 }
@@ -1258,10 +1082,10 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
     const bool writer = (blk == 0);
     int64_t r0;
     int nr;
-    cq_block_rows(nrows, nblk, blk, r0, nr);
+    block_rows(nrows, nblk, blk, r0, nr);
     int nbar = 0;
     bool alive = true;
-    if (tid == 0) s_flag = cq_ldi(&stt->timeout) ? 0 : 1;
+    if (tid == 0) s_flag = ldi_agent(&stt->timeout) ? 0 : 1;
     __syncthreads();
     alive = s_flag != 0;
     __syncthreads();
@@ -1271,16 +1095,16 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
         const int ex = cq_load_scaled_tile(X, xrs, xcs, r0, nr, b, T, red, tid);
         FQ_CLK(1);
         cq_block_gram(T, scr, part + (int64_t)blk * CQ_PART, tid);
-        if (tid == 0) cq_sti(bexp + blk, ex);
+        if (tid == 0) sti_agent(bexp + blk, ex);
         FQ_CLK(2);
-        alive = cq_grid_barrier(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
+        alive = grid_barrier<1>(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
         FQ_CLK(3);
         int dec = 0, tlast = 0;
         const bool sliced = nblk > CQ_SLICE_FROM;
         int emax0 = 0;
         if (alive && sliced) {
             emax0 = cq_slice_reduce(part, bexp, nblk, blk, gsum, tid);
-            alive = cq_grid_barrier(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
+            alive = grid_barrier<1>(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
         }
         if (alive) {
             if (sliced) cq_tail_fused(gsum, nullptr, 1, b, 0, stt, writer, Gs, Rf, s_out, maxpass, tid, (long long)nrows * b, slot, emax0);
@@ -1301,11 +1125,11 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
                 if (writer && lu_all) {
                     double* tb = topblk + (t & 1) * 1024;
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) { const int e = tid + 256 * u; cq_st(tb + e, T[(e >> 5) * CQ_P + (e & 31)]); }
+                    for (int u = 0; u < 4; ++u) { const int e = tid + 256 * u; st_agent(tb + e, T[(e >> 5) * CQ_P + (e & 31)]); }
                 }
                 if (writer && tid == 0) stt->pass = t;
                 if (t == 1) FQ_CLK(6);
-                alive = cq_grid_barrier(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
+                alive = grid_barrier<1>(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
                 if (!alive) break;
                 if (t == 1) FQ_CLK(7);
                 tlast = t;
@@ -1320,7 +1144,7 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
                 if (sliced) {
                     double* gs = gsum + (t & 1) * CQ_PART;
                     (void)cq_slice_reduce(pt, nullptr, nblk, blk, gs, tid);
-                    alive = cq_grid_barrier(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
+                    alive = grid_barrier<1>(&stt->fcounter, base + (++nbar) * nblk, &s_flag, tid, spin_limit);
                     if (!alive) break;
                     cq_tail_fused(gs, nullptr, 1, b, t, stt, writer, Gs, Rf, s_out, maxpass, tid, (long long)nrows * b, slot);
                 } else cq_tail_fused(pt, nullptr, nblk, b, t, stt, writer, Gs, Rf, s_out, maxpass, tid, (long long)nrows * b, slot);
@@ -1353,7 +1177,7 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
                 __syncthreads();
                 for (int e = tid; e < 1024; e += 256) {
                     const int i = e >> 5, j = e & 31;
-                    lu[CQ_LU_YTOP + e] = (i < b && j < b && i < nrows) ? cq_ld(Y + (int64_t)i * rs + j * cs) : 0.0;
+                    lu[CQ_LU_YTOP + e] = (i < b && j < b && i < nrows) ? ld_agent(Y + (int64_t)i * rs + j * cs) : 0.0;
                 }
                 __threadfence();
                 __syncthreads();
@@ -1370,7 +1194,7 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
     }
     if (!alive) {                                            // a barrier gave up (or an earlier launch of this call did): poison the output
         if (tid == 0) {
-            cq_sti(&stt->timeout, 1);
+            sti_agent(&stt->timeout, 1);
             // sticky per-stream count (survives the clearing of the state block at the end of the call): the host compares it
             // with the value it saw last (fused_timeouts) and redoes the work with the six-launch chain
             atomicAdd(&cq_stats[slot * 16 + 10], 1ull);
@@ -1391,7 +1215,7 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
 // layout: state | R (1024 + 32) | partial Gram matrices (x 2 for the single-launch form) | block exponents |
 //         reconstruction buffers (one per workgroup for the single-launch form) | top block of the panel (x 2)
 // workspace layout: as for the single-launch form up to 2 x CQ_FUSED_MAXBLK workgroups (whether a launch of more than CQ_FUSED_MAXBLK
-// takes that form is decided per call, see cq_big_admit)
+// takes that form is decided per call, see FusedTallLaunch in fused.hip)
 static inline bool cq_fused_fits(int64_t nblk) { return nblk <= 2 * CQ_FUSED_MAXBLK; }
 int64_t cholqr_ws_bytes(int64_t nrows, int b) {
     (void)b;
@@ -1401,211 +1225,43 @@ int64_t cholqr_ws_bytes(int64_t nrows, int b) {
            align_up(nlu * CQ_LU_DOUBLES * 8, 256) + align_up(2 * 1024 * 8, 256) + align_up(2 * CQ_PART * 8, 256) + 256;
 }
 
-// TN_PANEL_FUSED=0 keeps the six-launch chain for every panel (A/B measurements, cross-checks); read per call: the tests switch it
-static bool cq_fused_enabled() {
-    const char* e = getenv("TN_PANEL_FUSED");
-    return !(e && e[0] == '0');
-}
-
-// statistics slot of a stream (first come, first served; the streams beyond CQ_STAT_SLOTS share the last slot)
-static std::mutex cq_slot_mu;
-static std::map<hipStream_t, int> cq_slot_of;
-static std::vector<int> cq_slot_free;                               // slots of destroyed streams (tn_stream_destroy), handed out again first
-static int cq_slot_next = 0;
-static int cq_stat_slot(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(cq_slot_mu);
-    auto it = cq_slot_of.find(st);
-    if (it != cq_slot_of.end()) return it->second;
-    int s = CQ_STAT_SLOTS;
-    if (!cq_slot_free.empty()) { s = cq_slot_free.back(); cq_slot_free.pop_back(); }
-    else if (cq_slot_next < CQ_STAT_SLOTS) s = cq_slot_next++;
-    cq_slot_of.emplace(st, s);
-    return s;
-}
-int cholqr_stream_slot(hipStream_t st) { return cq_stat_slot(st); }      // (smallqr.hip shares the numbering)
-
-// Co-residency budget of the launches with in-kernel barriers (cq_fused_kernel here, sq_kernel in smallqr.hip): a workgroup of them
-// needs a whole CU and waits only for workgroups of its own launch, so launches in flight cannot deadlock while together they ask
-// for no more CUs than this process may count on.  Nothing about that is assumed: the budget is derived at first use from
-//   * the device (hipDeviceAttributeMultiprocessorCount), or TN_PANEL_CU_BUDGET when several processes share the card (the CUs this
-//     process may count on: half the chip for two tenants ...; 0 keeps every panel on the six-launch chain),
-//   * the number of hardware queues the runtime multiplexes the streams onto (GPU_MAX_HW_QUEUES as the runtime itself reads it at
-//     initialisation; 4 when unset): at most that many kernels of the process are in flight,
-// which gives  maxblk = min(32, budget / queues)  workgroups for an ordinary launch (32 with the package's 8 queues on an MI355X).  A
-// taller panel (up to 2 maxblk workgroups) is admitted only while the budget still holds with it:
-//     2 maxblk B + maxblk (S - B) <= budget,   S = min(streams of this process that have run panels, queues),  B = tall launches in
-// flight (this one included): all four chains of a solve when nothing else runs panels, three with a fifth stream around, none with
-// eight.  In-flight tall launches are tracked with one event per stream (recorded behind the launch, queried before the next
-// admission, all under one mutex that also covers the launch itself).  Streams created with a CU mask (tn_stream_create_masked) and
-// streams on which a launch has ever given up at a barrier (fused_timeouts) are taken off these forms for good.  A panel that is not
-// admitted takes the six-launch chain: the result is the same bit for bit.  TN_PANEL_FUSED_BIG=0: never admit tall panels.
-struct FusedBudget { int cus = 0, queues = 4, maxblk = 0; bool ready = false; };
-static FusedBudget cq_budget_of[16];
-static std::mutex cq_budget_mu;
-static FusedBudget fused_budget() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return FusedBudget(); }
-    std::lock_guard<std::mutex> lk(cq_budget_mu);
-    FusedBudget& b = cq_budget_of[dev];
-    if (!b.ready) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
-        if (const char* e = getenv("TN_PANEL_CU_BUDGET")) { const int v = atoi(e); if (v >= 0 && v < cus) cus = v; }
-        int q = 4;
-        if (const char* e = getenv("GPU_MAX_HW_QUEUES")) { const int v = atoi(e); if (v >= 1) q = v; }
-        b.cus = cus; b.queues = q;
-        b.maxblk = cus / q < CQ_FUSED_MAXBLK ? cus / q : CQ_FUSED_MAXBLK;
-        b.ready = true;
-    }
-    return b;
-}
-static std::map<hipStream_t, bool> cq_stream_off;                  // (guarded by cq_slot_mu)
-void fused_forms_disable(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(cq_slot_mu);
-    cq_stream_off[st] = true;
-}
-static void cq_dirty_mark(int slot);
-// tn_stream_destroy: the stream's slot (statistics, panel state, admission bookkeeping) goes back to the pool, so that the count of
-// live streams the admission of tall panels works with stays a count of LIVE streams
-void fused_stream_released(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(cq_slot_mu);
-    cq_stream_off.erase(st);
-    auto it = cq_slot_of.find(st);
-    if (it == cq_slot_of.end()) return;
-    const int slot = it->second;
-    cq_slot_of.erase(it);
-    if (slot < CQ_STAT_SLOTS) { cq_slot_free.push_back(slot); cq_dirty_mark(slot); }
-}
-static bool cq_stream_is_off(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(cq_slot_mu);
-    return cq_stream_off.count(st) != 0;
-}
-// may a launch of nwg workgroups with in-kernel barriers go out on this stream?
-bool fused_forms_allowed(hipStream_t st, int nwg) {
-    if (!cq_fused_enabled() || cq_stream_is_off(st)) return false;
-    if (cq_stat_slot(st) >= CQ_STAT_SLOTS) return false;
-    return nwg <= fused_budget().maxblk;
-}
-
-struct CqBigTrack {
-    hipEvent_t ev[CQ_STAT_SLOTS + 1] = {};
-    bool pending[CQ_STAT_SLOTS + 1] = {};
-};
-static CqBigTrack cq_big;
-static std::mutex cq_big_mu;
-static bool cq_big_enabled() {                                      // read per call: the tests switch it
-    const char* e = getenv("TN_PANEL_FUSED_BIG");
-    return !(e && e[0] == '0');
-}
-// call with cq_big_mu held
-static bool cq_big_admit(int slot, int nslots) {
-    if (slot >= CQ_STAT_SLOTS) return false;                       // streams without a slot of their own are not tracked
-    const FusedBudget b = fused_budget();
-    if (b.maxblk < 1) return false;
-    int inflight = 0;
-    for (int s = 0; s < CQ_STAT_SLOTS; ++s) {
-        if (s == slot || !cq_big.pending[s]) continue;            // (an earlier tall launch of THIS stream is not concurrent with the new one)
-        if (hipEventQuery(cq_big.ev[s]) == hipSuccess) cq_big.pending[s] = false;
-        else ++inflight;
-    }
-    const int S = nslots < b.queues ? nslots : b.queues;
-    return inflight + 1 <= b.cus / b.maxblk - S;
-}
-static void cq_big_launched(hipStream_t st, int slot) {
-    if (!cq_big.ev[slot] && hipEventCreateWithFlags(&cq_big.ev[slot], hipEventDisableTiming) != hipSuccess) { cq_big.ev[slot] = nullptr; return; }
-    if (hipEventRecord(cq_big.ev[slot], st) == hipSuccess) cq_big.pending[slot] = true;
-}
-
-// ---- time-outs of the launches with in-kernel barriers ----------------------------------------------------------------------
-// A launch that gives up at a barrier poisons its outputs with NaN and adds to a sticky per-stream device counter (cq_stats[10]
-// here, sq_stats[3] in smallqr.hip).  Every caller that has enqueued such launches asks fused_timeouts before it hands results
-// back: one 16-byte read-back and a synchronisation.  A positive answer means: the results of the stream since the previous
-// check are invalid, the stream has been taken off the single-launch forms (the co-residency the spins rely on evidently does
-// not hold: another tenant on the card, a debugger, ...), its barrier state is cleared, and the caller must redo the work -- which
-// now takes the six-launch chain / the blocked path, bit-identical results.  Callers that own many factorisations (tn_compress_mps)
-// defer the check to the end of their call (FusedDeferCheck).
-int smallqr_stats(hipStream_t st, unsigned long long* out4, int reset);
-int smallqr_reset_state(hipStream_t st);
-static thread_local long cq_fused_launches = 0;                    // launches with in-kernel barriers enqueued by this thread since its last check
-static thread_local int cq_defer_depth = 0;
-void fused_note_launch() { ++cq_fused_launches; }
-void fused_defer_push() { ++cq_defer_depth; }
-void fused_defer_pop() { --cq_defer_depth; }
-bool fused_check_deferred() { return cq_defer_depth > 0; }
-bool fused_check_needed() { return cq_fused_launches > 0; }
-static unsigned long long cq_timeouts_seen[CQ_STAT_SLOTS + 1][2];  // last values of the two counters per slot (guarded by cq_slot_mu)
-int fused_timeouts(hipStream_t st, int* count_out) {
-    *count_out = 0;
-    cq_fused_launches = 0;
-    const int slot = cq_stat_slot(st);
-    if (slot >= CQ_STAT_SLOTS) return 0;                           // such streams never take these forms
+// the stream's sticky count of single-launch panels that gave up at a barrier (cq_stats[10]), for fused_timeouts: one 8-byte read-back
+// and a synchronisation
+int cholqr_gaveup_count(hipStream_t st, int slot, unsigned long long* count) {
     unsigned long long* h = (unsigned long long*)pinned_host(64, 7);
     unsigned long long tmp[8];
     if (!h) h = tmp;
     hipError_t e = hipMemcpyFromSymbolAsync(h, HIP_SYMBOL(cq_stats), 8, ((size_t)slot * 16 + 10) * 8, hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) return hip_fail(e, "read panel time-outs");
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync panel time-outs");
-    const unsigned long long a = h[0];
-    unsigned long long sq[4];
-    int rc = smallqr_stats(st, sq, 0);
-    if (rc) return rc;
-    unsigned long long da, db;
-    {
-        std::lock_guard<std::mutex> lk(cq_slot_mu);
-        da = a - cq_timeouts_seen[slot][0];
-        db = sq[3] - cq_timeouts_seen[slot][1];
-        cq_timeouts_seen[slot][0] = a;
-        cq_timeouts_seen[slot][1] = sq[3];
-        if (da + db > 0) cq_stream_off[st] = true;
-    }
-    if (da + db == 0) return 0;
-    *count_out = (int)(da + db > 2147483647ull ? 2147483647ull : da + db);
-    fprintf(stderr, "[libtnpeps] %llu launch(es) with in-kernel barriers gave up on stream %p (workgroups not co-resident: is the device shared? "
-            "see TN_PANEL_CU_BUDGET); the work is redone through the multi-launch forms, which this stream uses from now on\n",
-            (unsigned long long)(da + db), (void*)st);
-    // leave a clean slate: the stream's panel state (sticky flag, barrier counter) and the small-QR barrier state
-    {
-        std::lock_guard<std::mutex> lk(cq_slot_mu);
-        cq_dirty_mark(slot);
-    }
-    if ((rc = smallqr_reset_state(st))) return rc;
+    *count = h[0];
     return 0;
 }
 
 // The panel state of a factorisation lives in a block of its own per stream (a stream's calls do not overlap), NOT in the shared
 // scratch: it is zero when a call starts because the call before it ended by clearing it (the first launch after the last panel --
 // diag_qr_kernel of tn_qr -- zeroes the block), so no memset launch per factorisation.  A call that fails half-way leaves its
-// stream's block marked dirty on the host and the next call clears it with a memset.  Streams beyond CQ_STAT_SLOTS fall back to the
+// stream's block marked dirty on the host and the next call clears it with a memset.  Streams beyond CHOLQR_SLOTS fall back to the
 // state block at the head of the workspace and a memset per call.
-__device__ char cq_state_pool[CQ_STAT_SLOTS * CQ_STATE_BYTES];
-static bool cq_dirty[CQ_STAT_SLOTS];
-static void cq_dirty_mark(int slot) { cq_dirty[slot] = true; }      // the next cholqr_begin on this stream clears the block with a memset
+__device__ char cq_state_pool[CHOLQR_SLOTS * CQ_STATE_BYTES];
+static bool cq_dirty[CHOLQR_SLOTS];
+void cholqr_state_dirty(int slot) { cq_dirty[slot] = true; }
 int cholqr_begin(hipStream_t st, void* ws, void** state_out) {
-    const int slot = cq_stat_slot(st);
-    if (slot >= CQ_STAT_SLOTS) {
+    const int slot = cholqr_stream_slot(st);
+    if (slot >= CHOLQR_SLOTS) {
         *state_out = ws;
         const hipError_t e = hipMemsetAsync(ws, 0, CQ_STATE_BYTES, st);
         return e == hipSuccess ? 0 : hip_fail(e, "memset panel state");
     }
-    static char* bases[16] = {};                                   // a __device__ symbol has one address per device
+    *state_out = device_pool_slot(HIP_SYMBOL(cq_state_pool), CQ_STATE_BYTES, slot);
+    if (!*state_out) { set_error("cholqr_begin: panel state pool not available on the current device"); return 1; }
     static std::mutex mu;
     bool dirty;
-    char* base = nullptr;
     {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { set_error("cholqr_begin: no current device"); return 1; }
         std::lock_guard<std::mutex> lk(mu);
-        if (!bases[dev]) {
-            void* p = nullptr;
-            const hipError_t e = hipGetSymbolAddress(&p, HIP_SYMBOL(cq_state_pool));
-            if (e != hipSuccess) return hip_fail(e, "panel state pool");
-            bases[dev] = (char*)p;
-        }
-        base = bases[dev];
         dirty = cq_dirty[slot];
         cq_dirty[slot] = true;
     }
-    *state_out = base + (size_t)slot * CQ_STATE_BYTES;
     if (dirty) {
         const hipError_t e = hipMemsetAsync(*state_out, 0, CQ_STATE_BYTES, st);
         if (e != hipSuccess) return hip_fail(e, "memset panel state");
@@ -1614,8 +1270,8 @@ int cholqr_begin(hipStream_t st, void* ws, void** state_out) {
 }
 // the launch that clears the state block has been enqueued: the next call on this stream finds it clean
 void cholqr_end_ok(hipStream_t st) {
-    const int slot = cq_stat_slot(st);
-    if (slot < CQ_STAT_SLOTS) cq_dirty[slot] = false;
+    const int slot = cholqr_stream_slot(st);
+    if (slot < CHOLQR_SLOTS) cq_dirty[slot] = false;
 }
 
 // The state block at the head of the workspace must be zero before the first panel of a call (the kernels leave it clean).
@@ -1678,26 +1334,14 @@ int cholqr_panel(hipStream_t st, const double* X, int64_t irs, int64_t ics, doub
     double* lu = reconstruct ? (double*)p : nullptr; p += align_up((int64_t)(fits ? nblk : 1) * CQ_LU_DOUBLES * 8, 256);
     double* topblk = (double*)p; p += align_up(2 * 1024 * 8, 256);
     double* gsum = (double*)p;                                      // 2 x CQ_PART: the summed Gram matrix of the sliced reduction (pass parity)
-    // TN_PANEL_MAXPASS (1 .. CQ_MAXPASS): fewer substitution passes, to drive the Householder fallback in tests
-    static const int maxpass = [] { const char* e = getenv("TN_PANEL_MAXPASS"); const int v = e ? atoi(e) : CQ_MAXPASS; return v >= 1 && v <= CQ_MAXPASS ? v : CQ_MAXPASS; }();
-    const int slot = cq_stat_slot(st);
-    const int maxblk = fused_budget().maxblk;                      // ordinary single-launch panels: at most this many workgroups
+    const int maxpass = panel_maxpass();                           // (TN_PANEL_MAXPASS: fewer passes, to drive the Householder fallback in tests)
+    const int slot = cholqr_stream_slot(st);
+    const int maxblk = fused_maxblk();                             // ordinary single-launch panels: at most this many workgroups
     const bool tall = nblk > maxblk;
     const bool usable = fits && fused_base && nblk <= 2 * maxblk && fused_forms_allowed(st, 1);
-    std::unique_lock<std::mutex> big_lock(cq_big_mu, std::defer_lock);
-    bool admitted = usable;
-    if (usable && tall) {
-        admitted = false;
-        if (cq_big_enabled()) {
-            int nslots;
-            { std::lock_guard<std::mutex> lk(cq_slot_mu); nslots = (int)cq_slot_of.size(); }
-            big_lock.lock();
-            admitted = cq_big_admit(slot, nslots);
-            if (!admitted) big_lock.unlock();
-        }
-    }
-    if (admitted) {
-        static const unsigned spin_limit = [] { const char* e = getenv("TN_PANEL_SPIN_LIMIT"); return e ? (unsigned)strtoul(e, nullptr, 10) : CQ_SPIN_LIMIT; }();
+    FusedTallLaunch tall_launch(st, usable && tall);
+    if (usable && (!tall || tall_launch.admitted)) {
+        static const unsigned spin_limit = panel_spin_limit();     // (the panel step keeps the value of its first single-launch panel)
         fused_note_launch();
         // one launch for the whole chain.  Algorithmic bytes: the panel in, the reflectors (and W, Wq) out -- the tile never
         // leaves LDS in between; flops: Gram + post at launch time, the passes are booked from the device counter (cq_stats[3])
@@ -1705,7 +1349,7 @@ int cholqr_panel(hipStream_t st, const double* X, int64_t irs, int64_t ics, doub
         hipLaunchKernelGGL(cq_fused_kernel, dim3(nblk), dim3(256), 0, st, X, irs, ics, Y, rs, cs, nrows, b, nblk, part, bexp, topblk, stt,
                            *fused_base, seed, lu, Tp, W, wrs, wcs, Wq, maxpass, slot, spin_limit, gsum, active);
         TN_CHECK_LAUNCH("cq_fused_kernel");
-        if (tall) { cq_big_launched(st, slot); big_lock.unlock(); }
+        tall_launch.launched();
         *fused_base += (maxpass + 1) * nblk * (nblk > CQ_SLICE_FROM ? 2 : 1);
         const double e = (double)nrows * b;
         prof_end(st, PROF_PANEL, (2.0 + (reconstruct ? (Wq ? 6.0 : 4.0) : 0.0)) * e * b, (reconstruct ? (Wq ? 32.0 : 24.0) : 16.0) * e);
@@ -1751,25 +1395,25 @@ int cholqr_debug_state(hipStream_t st, const void* ws, int* ints9, double* dev_h
 }
 // st_or_null: the counters of that stream only (as far as it has a slot of its own); NULL with all_streams: the sum over all slots
 int cholqr_stats(unsigned long long* out16, int reset, hipStream_t st_or_null, int all_streams) {
-    static unsigned long long raw[(CQ_STAT_SLOTS + 1) * 16];
+    static unsigned long long raw[(CHOLQR_SLOTS + 1) * 16];
     static std::mutex mu;
     std::lock_guard<std::mutex> lk(mu);
     hipError_t e = hipMemcpyFromSymbol(raw, HIP_SYMBOL(cq_stats), sizeof(raw));
     if (e != hipSuccess) return hip_fail(e, "read panel statistics");
     for (int i = 0; i < 16; ++i) out16[i] = 0;
     if (all_streams) {
-        for (int s = 0; s <= CQ_STAT_SLOTS; ++s)
+        for (int s = 0; s <= CHOLQR_SLOTS; ++s)
             for (int i = 0; i < 16; ++i) out16[i] += raw[s * 16 + i];
         // (word [10], the sticky count of launches that gave up at a barrier, is NOT a statistic: fused_timeouts compares it with the value
         //  it saw last, so a reset keeps it -- zeroing it would turn the next comparison into a huge unsigned difference, or lose a time-out)
         if (reset) {
-            for (int s = 0; s <= CQ_STAT_SLOTS; ++s)
+            for (int s = 0; s <= CHOLQR_SLOTS; ++s)
                 for (int i = 0; i < 16; ++i) if (i != 10) raw[s * 16 + i] = 0;
             if ((e = hipMemcpyToSymbol(HIP_SYMBOL(cq_stats), raw, sizeof(raw))) != hipSuccess) return hip_fail(e, "reset panel statistics");
         }
         return 0;
     }
-    const int slot = cq_stat_slot(st_or_null);
+    const int slot = cholqr_stream_slot(st_or_null);
     for (int i = 0; i < 16; ++i) out16[i] = raw[slot * 16 + i];
     if (reset) {
         unsigned long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};

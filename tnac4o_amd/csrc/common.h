@@ -40,24 +40,6 @@ void* pinned_host(size_t bytes, int slot);
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 
-// Fast reciprocal square root / reciprocal with three Newton steps (full double accuracy to ~1 ulp; the hardware
-// seeds are single-precision accurate).  They sit on the per-column critical path of the panel factorisation.
-static __device__ __forceinline__ double fast_rsqrt(double x) {
-    double r = __builtin_amdgcn_rsq(x);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
-static __device__ __forceinline__ double fast_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    r = r * (2.0 - x * r);
-    r = r * (2.0 - x * r);
-    r = r * (2.0 - x * r);
-    return r;
-}
-
-
 // ---- optional event timing per kernel family (prof.hip) ---------------------------------------------
 enum { PROF_GEMM_128x128 = 0, PROF_GEMM_128x32, PROF_GEMM_32x128, PROF_GEMM_64x64, PROF_SPLITK_REDUCE, PROF_ABSORB,
        PROF_GRAM, PROF_EIG, PROF_ROWS_SMALL, PROF_VECS_SMALL,
@@ -180,6 +162,11 @@ int64_t qr_ws_bytes(int64_t m, int64_t n, int nb);
 
 
 // ---- iterated Cholesky-QR panel orthonormalisation (cholqr.hip), the default panel step -------------------------------
+// the numbers of the iteration, shared with the one-launch factorisation (smallqr.hip)
+constexpr int CQ_MAXPASS = 4;         // substitution passes enqueued per panel (later ones return at once when converged)
+constexpr double CQ_THETA = 1e-10;    // deferral threshold on pivot / squared column norm
+constexpr double CQ_DONE = 5e-15;     // Gram matrix = identity to rounding: converged
+constexpr double CQ_LAST = 1e-8;      // below this one more pass lands at rounding level without another check
 int64_t cholqr_ws_bytes(int64_t nrows, int b);
 int cholqr_reset(hipStream_t st, void* ws);          // zero the state block at the head of ws once per call, before the first panel
 // the stream's own state block (zero on return; see cholqr.hip) -- *state_out goes to the panel calls of this factorisation; the
@@ -194,10 +181,43 @@ int cholqr_orthonormalize(hipStream_t st, const double* X, int64_t irs, int64_t 
 int cholqr_panel(hipStream_t st, const double* X, int64_t irs, int64_t ics, double* Y, int64_t rs, int64_t cs, int64_t nrows, int b, void* ws,
                  int64_t ws_bytes, uint64_t seed, int reconstruct, double* Tp, double* W, int64_t wrs, int64_t wcs, double* Wq, int* fused_base,
                  void* state = nullptr, const int* active = nullptr);       // active (DEVICE, may be null): 0 = every launch of this panel returns at once
-// launches with in-kernel barriers (cq_fused_kernel, sq_kernel): co-residency budget and time-outs, see cholqr.hip
+int cholqr_debug_state(hipStream_t st, const void* ws, int* ints9, double* dev_hist);
+int cholqr_stats(unsigned long long* out16, int reset, hipStream_t st_or_null, int all_streams);
+// one-launch factorisation of m x n, n <= 64 (smallqr.hip): 0 done, 1 shape / stream not taken, else error
+bool smallqr_fits(int64_t m, int64_t n);
+int64_t smallqr_ws_bytes(int64_t m, int64_t n);
+int smallqr_factor(hipStream_t st, const double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R,
+                   int64_t rrs, int64_t rcs, double* nf_out2, void* ws, int64_t ws_bytes);
+
+// ---- host side of the launches with in-kernel barriers (fused.hip): cq_fused_kernel, sq_kernel, svdl_kernel ---------------------
+constexpr int CQ_FUSED_MAXBLK = 32;           // workgroups of an ordinary launch (a tall panel: up to twice that, see FusedTallLaunch)
+constexpr unsigned CQ_SPIN_LIMIT = 1u << 22;  // looks at a barrier's counter before a launch gives up (seconds)
+constexpr int CHOLQR_SLOTS = 64;              // streams with a slot of their own
+int cholqr_stream_slot(hipStream_t st);       // statistics / state slot of a stream (CHOLQR_SLOTS = no slot of its own)
+// address of slot `slot` (slot_bytes each) of the __device__ pool `symbol` (HIP_SYMBOL of the caller's own translation unit) on the
+// current device; nullptr (and no HIP error left behind) when there is no current device or the symbol cannot be resolved
+void* device_pool_slot(const void* symbol, size_t slot_bytes, int slot);
+unsigned panel_spin_limit();                  // TN_PANEL_SPIN_LIMIT (tests: force the barriers to give up), read per call
+int panel_maxpass();                          // TN_PANEL_MAXPASS (1 .. CQ_MAXPASS; tests: drive the Householder fallbacks), read once
+// co-residency budget and time-outs, see fused.hip
+int fused_maxblk();                           // largest ordinary launch the budget of this process allows (<= CQ_FUSED_MAXBLK)
 bool fused_forms_allowed(hipStream_t st, int nwg);
 void fused_forms_disable(hipStream_t st);
 void fused_stream_released(hipStream_t st);
+// admission of one launch of up to 2 fused_maxblk() workgroups (wanted == false: nothing is asked, nothing is held): when `admitted`,
+// the admission lock is held until launched(), which records the launch, or the end of the scope
+struct FusedTallLaunch {
+    FusedTallLaunch(hipStream_t st, bool wanted);
+    ~FusedTallLaunch();
+    FusedTallLaunch(const FusedTallLaunch&) = delete;
+    FusedTallLaunch& operator=(const FusedTallLaunch&) = delete;
+    void launched();
+    bool admitted = false;
+private:
+    hipStream_t st_;
+    int slot_;
+    void release();
+};
 void fused_note_launch();
 bool fused_check_needed();
 bool fused_check_deferred();
@@ -205,14 +225,10 @@ void fused_defer_push();
 void fused_defer_pop();
 struct FusedDeferCheck { FusedDeferCheck() { fused_defer_push(); } ~FusedDeferCheck() { fused_defer_pop(); } };
 int fused_timeouts(hipStream_t st, int* count_out);       // synchronises st; *count_out > 0: redo the work since the last check
-// one-launch factorisation of m x n, n <= 64 (smallqr.hip): 0 done, 1 shape / stream not taken, else error
-bool smallqr_fits(int64_t m, int64_t n);
-int64_t smallqr_ws_bytes(int64_t m, int64_t n);
-int smallqr_factor(hipStream_t st, const double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R,
-                   int64_t rrs, int64_t rcs, double* nf_out2, void* ws, int64_t ws_bytes);
-int cholqr_stream_slot(hipStream_t st);     // statistics / state slot of a stream (CHOLQR_SLOTS = no slot of its own)
-constexpr int CHOLQR_SLOTS = 64;
-int cholqr_debug_state(hipStream_t st, const void* ws, int* ints9, double* dev_hist);
-int cholqr_stats(unsigned long long* out16, int reset, hipStream_t st_or_null, int all_streams);
+// what fused_timeouts needs from the two kernels: their sticky per-stream counts of launches that gave up, and a clean slate afterwards
+int cholqr_gaveup_count(hipStream_t st, int slot, unsigned long long* count);     // (synchronises st)
+void cholqr_state_dirty(int slot);            // the next cholqr_begin on this slot clears the state block with a memset
+int smallqr_stats(hipStream_t st, unsigned long long* out4, int reset);
+int smallqr_reset_state(hipStream_t st);
 
 }  // namespace tn

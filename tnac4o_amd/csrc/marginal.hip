@@ -27,6 +27,7 @@
 // one workgroup per state, then one workgroup divides both tables by T = sum Pl (no negativity rule: the sums stay exact).
 #include "../../include/tnpeps.h"
 #include "common.h"
+#include "devprim.h"
 
 namespace tn {
 
@@ -149,32 +150,6 @@ int env3(hipStream_t st, int side, const double* E, const double* At, const doub
 // ---- cell marginal -----------------------------------------------------------------------------------------------------
 constexpr int64_t CM_QMAX = 16384;       // LDS holds the q entries of the table
 
-__device__ __forceinline__ double cm_block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) red[tid] += red[tid + k];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ double cm_block_min(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) red[tid] = fmin(red[tid], red[tid + k]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // one workgroup: wave w gathers the states s = w, w+4, ..., its lanes split the (l,u) sum
 __global__ __launch_bounds__(256) void cluster_marginal_kernel(const double* __restrict__ X, const double* __restrict__ F,
                                                                const int32_t* __restrict__ dmap, const int32_t* __restrict__ rmap, int q,
@@ -202,18 +177,18 @@ __global__ __launch_bounds__(256) void cluster_marginal_kernel(const double* __r
     __syncthreads();
     double mn = 1.7e308, part = 0.0;
     for (int s = tid; s < q; s += 256) { mn = fmin(mn, sP[s]); part += sP[s]; }
-    const double raw = cm_block_sum(part, red);
-    double mPn = cm_block_min(mn, red);
+    const double raw = block_tree_sum(part, red);
+    double mPn = block_tree_min(mn, red);
     if (mPn < 0.0) {                                   // the rule of tn_calc_pn (reference tnac4o.py:1796-1799)
         const double a = fabs(mPn);
         double cnt = 0.0;
         for (int s = tid; s < q; s += 256)
             if (sP[s] < a) { sP[s] = a; cnt += 1.0; }
-        mPn *= cm_block_sum(cnt, red);
+        mPn *= block_tree_sum(cnt, red);
     }
     part = 0.0;
     for (int s = tid; s < q; s += 256) part += sP[s];
-    const double no = cm_block_sum(part, red);
+    const double no = block_tree_sum(part, red);
     if (no > 0.0) {
         const double inv = 1.0 / no;
         for (int s = tid; s < q; s += 256) P[s] = sP[s] * inv;
@@ -306,13 +281,13 @@ __global__ __launch_bounds__(256) void bond_finish_kernel(const double* __restri
     const int tid = threadIdx.x;
     double part = 0.0;
     for (int64_t e = tid; e < nlq; e += 256) part += Rl[e];
-    const double raw = cm_block_sum(part, red);
+    const double raw = block_tree_sum(part, red);
     double mn = 0.0;
     if (raw > 0.0) {
         const double inv = 1.0 / raw;
         for (int64_t e = tid; e < nlq; e += 256) { const double v = Rl[e] * inv; Pl[e] = v; mn = fmin(mn, v); }
         for (int64_t e = tid; e < nuq; e += 256) { const double v = Ru[e] * inv; Pu[e] = v; mn = fmin(mn, v); }
-        mn = cm_block_min(mn, red);
+        mn = block_tree_min(mn, red);
     } else {                                           // all zeros -> uniform, flag -1 (as cluster_marginal_kernel)
         for (int64_t e = tid; e < nlq; e += 256) Pl[e] = 1.0 / (double)nlq;
         for (int64_t e = tid; e < nuq; e += 256) Pu[e] = 1.0 / (double)nuq;

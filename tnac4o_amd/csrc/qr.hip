@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devprim.h"
 
 namespace tn {
 
@@ -90,11 +91,6 @@ static void compose_swaps(const int* pairs, int npairs, SwapList& sl) {
     sl.n = 0;
     for (int i = 0; i < nc; ++i)
         if (from[i] != cols[i]) { sl.dst[sl.n] = cols[i]; sl.src[sl.n] = from[i]; ++sl.n; }
-}
-
-__device__ __forceinline__ double hash_unit(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return ((double)(x >> 11) * (1.0 / 9007199254740992.0)) - 0.5;
 }
 
 // columns of the panel flagged dead (exactly zero) get deterministic pseudo-random content
@@ -997,8 +993,7 @@ __global__ __launch_bounds__(256) void pivot_select_kernel(const double* __restr
     }
     // (the selections are agent-scope stores: they go through to memory, the publisher only waits for their completion -- no release
     //  fence, which would write back the XCD's L2; the last workgroup reads them with agent-scope loads)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0);
+    publish_wait();
     __syncthreads();
     if (tid == 0) s_last = (atomicAdd(&S->ticket, 1) == nblk - 1) ? 1 : 0;
     __syncthreads();

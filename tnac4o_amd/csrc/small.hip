@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "devprim.h"
 
 namespace tn {
 
@@ -97,12 +98,6 @@ int gram_partial(hipStream_t st, const double* X, int64_t vs, int64_t es, int64_
 // (Two earlier generations, with two barriers per step and with one barrier on four waves, were measured slower and removed.)
 __device__ __forceinline__ double rot_p(double c, double s, double x, double y) { return __fma_rn(-s, y, __dmul_rn(c, x)); }   // c x - s y
 __device__ __forceinline__ double rot_q(double c, double s, double x, double y) { return __fma_rn(s, x, __dmul_rn(c, y)); }    // s x + c y
-__device__ __forceinline__ double rsqrt2n(double x) {      // hardware seed (~2^-26) + two Newton steps: full double accuracy
-    double r = __builtin_amdgcn_rsq(x);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
 
 // Jacobi rotation of a pair (p < q) from g_pp, g_qq, g_pq: the smaller-angle rotation, (c, sn) with G' = R^T G R, R = [[c, sn], [-sn, c]];
 // false (c = 1, sn = 0) when |g_pq| <= tol sqrt(|g_pp g_qq|)  (the rule of eig_small3_kernel's `decide`)
@@ -111,9 +106,9 @@ __device__ __forceinline__ bool eig_decide(double gpp, double gqq, double gpq, d
     const double g2 = gpq * gpq;
     if (g2 > tol * tol * fabs(gpp * gqq)) {
         const double d = gqq - gpp;
-        const double rh = rsqrt2n(d * d + 4.0 * g2);
+        const double rh = rsqrt2(d * d + 4.0 * g2);
         const double c2 = 0.5 + 0.5 * fabs(d) * rh;
-        const double rcv = rsqrt2n(c2);
+        const double rcv = rsqrt2(c2);
         const double sabs = fabs(gpq) * rh * rcv;
         if (sabs <= 1.0 && c2 <= 1.0000000000000002) {
             c = c2 * rcv;
@@ -461,9 +456,9 @@ __device__ __forceinline__ void eig_small3_body(double* pool, const int grp, con
             const double g2 = gpq * gpq;
             if (g2 > tol * tol * fabs(gpp * gqq)) {
                 const double d = gqq - gpp;
-                const double rh = rsqrt2n(d * d + 4.0 * g2);
+                const double rh = rsqrt2(d * d + 4.0 * g2);
                 const double c2 = 0.5 + 0.5 * fabs(d) * rh;
-                const double rcv = rsqrt2n(c2);
+                const double rcv = rsqrt2(c2);
                 const double sabs = fabs(gpq) * rh * rcv;
                 if (sabs <= 1.0 && c2 <= 1.0000000000000002) {
                     c = c2 * rcv;
@@ -808,7 +803,7 @@ int eig_small(hipStream_t st, const double* part, int nchunk, int nvec, int ngro
 // crosses workgroups (agent-scope accesses) is the partial Gram matrices and J -- the vectors travel once in and once out.
 // A form that kept the vectors in memory and ran the GEMM tile body between the barriers was measured first: every K step of those
 // small products is a memory round trip, ~40 us per round around the eigenproblems against ~23 us for the two GEMM launches.
-// The workgroups spin on barriers, so they must be co-resident: the grid is kept within the budget of cholqr.hip (fused_forms_allowed),
+// The workgroups spin on barriers, so they must be co-resident: the grid is kept within the budget of fused.hip (fused_forms_allowed),
 // the spins are bounded, and a launch in which a barrier gave up says so in its status word (the caller redoes the rounds with the
 // three-launch form and takes the stream off the single-launch forms).  The barrier state cleans itself: all workgroups leave sooner
 // or later, the last one resets the counters.
@@ -837,27 +832,8 @@ struct SvdjState { int counter; int exits; int gaveup; int pad; };
 __device__ SvdjState svdj_state_pool[CHOLQR_SLOTS];
 constexpr unsigned SVDJ_MAGIC = 0x53564a31u;
 
-// naps: the pause between two looks at the counter, in units of ~0.4 us.  The wait for the eigenproblems lasts 15-100 us and up to 30
-// workgroups per chain sit in it.
-__device__ __forceinline__ bool svdj_barrier(int* counter, int target, int* s_flag, int tid, unsigned spin_limit, int naps = 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-    if (tid == 0) {
-        atomicAdd(counter, 1);
-        int ok = 1;
-        unsigned spins = 0;
-        while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(2);
-            for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(15);
-            if (++spins > spin_limit) { ok = 0; break; }
-        }
-        *s_flag = ok;
-    }
-    __syncthreads();
-    return *s_flag != 0;
-}
-
+// eig_naps: the `naps` of grid_barrier (devprim.h) for the wait for the eigenproblems, which lasts 15-100 us with up to 30 workgroups
+// per chain sitting in it.
 struct SvdlArgs {
     double* X;
     int64_t pitch, L;
@@ -906,7 +882,7 @@ __global__ __launch_bounds__(512) void svdl_kernel(SvdlArgs a) {
     int nbar = 0, sweeps = 0;
     bool alive = ak != nullptr && ak->magic == SVDJ_MAGIC && ak->nvp == a.nvp && ak->pairs == a.pairs && ak->norms == a.norms && ak->Js == a.Js;
     bool converged = false;
-    auto bar = [&](int naps = 0) -> bool { ++nbar; return svdj_barrier(&a.stt->counter, nbar * nwg, &s_flag, tid, a.spin_limit, naps); };
+    auto bar = [&](int naps = 0) -> bool { ++nbar; return grid_barrier<2>(&a.stt->counter, nbar * nwg, &s_flag, tid, a.spin_limit, naps); };
     const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
     const int ti = wave >> 1, tj0 = (wave & 1) * 2;          // this wave's two 16 x 16 tiles of a 64 x 64 result
     SVL_CLK_INIT;
@@ -1051,20 +1027,6 @@ __global__ __launch_bounds__(512) void svdl_kernel(SvdlArgs a) {
     }
 }
 
-static SvdjState* svdj_state_of(int slot) {
-    static std::mutex mu;
-    static char* base[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!base[dev]) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(svdj_state_pool)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        base[dev] = (char*)p;
-    }
-    return (SvdjState*)base[dev] + slot;
-}
-
 // 0: the launch is in the stream (read norms[nvp .. nvp + 2] back: sweeps, converged, workgroups that gave up); 1: not taken (the
 // caller runs the rounds as separate launches); else an error
 int svd_rounds_fused(hipStream_t st, const SvdRoundsJob& j) {
@@ -1091,10 +1053,9 @@ int svd_rounds_fused(hipStream_t st, const SvdRoundsJob& j) {
     l.relevant2 = j.relevant2; l.fast_thr = fast_thr; l.last_tol = j.last_tol;
     l.inner_first = j.inner_first; l.inner_later = j.inner_later; l.dbg = dbg;
     l.norms = j.norms;
-    l.stt = svdj_state_of(slot);
+    l.stt = (SvdjState*)device_pool_slot(HIP_SYMBOL(svdj_state_pool), sizeof(SvdjState), slot);
     if (!l.stt) return 1;
-    l.spin_limit = 1u << 22;
-    if (const char* e = getenv("TN_PANEL_SPIN_LIMIT")) l.spin_limit = (unsigned)strtoul(e, nullptr, 10);      // tests: force the barriers to give up
+    l.spin_limit = panel_spin_limit();
     l.magic = SVDJ_MAGIC;
     l.eig_naps = eig_naps;
     prof_begin(st, PROF_EIG);

@@ -16,17 +16,17 @@
 // pivots that have lost their digits (row j of R_t = e_j: the substitution leaves the exact residual, the next pass treats it as
 // an ordinary column), exactly zero columns refilled with noise (and their row of R zeroed: A = Q R stays exact).  The
 // substitution is backward stable row by row, so A = Q (R_p ... R_1) holds column-wise to rounding whatever the conditioning;
-// orthogonality is what the passes iterate on.  If SQ_MAXPASS passes do not converge, workgroup 0 redoes the factorisation with
+// orthogonality is what the passes iterate on.  If CQ_MAXPASS passes do not converge, workgroup 0 redoes the factorisation with
 // Householder reflections in global memory (slow, never seen on the contraction path; driven in the tests with TN_PANEL_MAXPASS).
 //
 // Workgroups meet at in-kernel barriers (monotone counter, one polling lane, agent-scope stores / loads: the protocol of
-// cq_fused_kernel, same co-residency budget: at most 32 workgroups per launch).  Bounded spins; a launch that gives up poisons its
-// outputs with NaN and books a time-out (cholqr_timeouts), which the callers check.
+// cq_fused_kernel, grid_barrier in devprim.h, same co-residency budget: at most 32 workgroups per launch).  Bounded spins; a launch that gives up poisons its
+// outputs with NaN and books a time-out (fused_timeouts in fused.hip), which the callers check.
 #include <stdlib.h>
 
-#include <mutex>
 
 #include "common.h"
+#include "devprim.h"
 
 // -DSQ_CLOCKS: thread 0 of workgroup 0 records the 100 MHz wall clock at phase boundaries (diagnostics only: tools/smallqr_clocks.py)
 #ifdef SQ_CLOCKS
@@ -44,41 +44,12 @@ namespace tn {
 typedef double d4s __attribute__((ext_vector_type(4)));
 
 constexpr int SQ_MAXBLK = 32;
-constexpr int SQ_MAXPASS = 4;
-constexpr double SQ_THETA = 1e-10;
-constexpr double SQ_DONE = 5e-15;
-constexpr double SQ_LAST = 1e-8;
 
 struct SqState { int counter; int exits; int pad0; int pad1; };
 __device__ SqState sq_state_pool[CHOLQR_SLOTS];
 // [0] calls  [1] passes applied  [2] Householder fallbacks  [3] launches that gave up at a barrier
 __device__ unsigned long long sq_stats[CHOLQR_SLOTS * 4];
 
-__device__ __forceinline__ double sq_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sq_st(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int sq_ldi(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sq_sti(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sq_publish_wait() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_waitcnt(0); }
-
-__device__ __forceinline__ double sq_readlane(double v, int lane) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, lane);
-    hi = __builtin_amdgcn_readlane(hi, lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double sq_rsqrt2(double x) {
-    double r = __builtin_amdgcn_rsq(x);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
-__device__ __forceinline__ void sq_fnma(double& acc, double a, double b) {
-    asm volatile("v_fma_f64 %0, -%1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ double sq_hash_unit(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return ((double)(x >> 11) * (1.0 / 9007199254740992.0)) - 0.5;
-}
 // value of lane (quad base + SEL) of every quad (TPR = 4) / of lane (pair base + SEL) of every pair (TPR = 2), through the DPP network
 template <int CTRL>
 __device__ __forceinline__ double sq_dpp(double v) {
@@ -92,38 +63,6 @@ __device__ __forceinline__ double sq_group_bcast(double v, int owner) {      // 
     if constexpr (TPR == 1) return v;
     else if constexpr (TPR == 2) return owner == 0 ? sq_dpp<0xA0>(v) : sq_dpp<0xF5>(v);       // quad_perm [0,0,2,2] / [1,1,3,3]
     else return owner == 0 ? sq_dpp<0x00>(v) : owner == 1 ? sq_dpp<0x55>(v) : owner == 2 ? sq_dpp<0xAA>(v) : sq_dpp<0xFF>(v);
-}
-
-__device__ __forceinline__ void sq_block_rows(int64_t nrows, int nblk, int blk, int64_t& r0, int& nr) {
-    const int64_t base = nrows / nblk, rem = nrows % nblk;
-    r0 = blk * base + (blk < rem ? blk : rem);
-    nr = (int)(base + (blk < rem ? 1 : 0));
-}
-
-__device__ __forceinline__ bool sq_grid_barrier(int* counter, int target, int* s_flag, int tid, unsigned spin_limit) {
-    sq_publish_wait();
-    __syncthreads();
-    if (tid == 0) {
-        atomicAdd(counter, 1);
-        int ok = 1;
-        unsigned spins = 0;
-        while (sq_ldi(counter) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > spin_limit) { ok = 0; break; }
-        }
-        *s_flag = ok;
-    }
-    __syncthreads();
-    return *s_flag != 0;
-}
-
-__device__ __forceinline__ double sq_block_sum(double v, double* red, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // Last resort, one workgroup, everything in global memory: Householder QR (dgeqr2) of 2^-emax A in Q's storage, R = its upper
@@ -144,7 +83,7 @@ __device__ void sq_fallback_householder(const double* A, int64_t ars, int64_t ac
     for (int j = 0; j < n; ++j) {
         double s = 0.0;
         for (int64_t r = j + 1 + tid; r < m; r += 256) { const double y = Q[r * rs + j * cs]; s += y * y; }
-        s = sq_block_sum(s, red, tid);
+        s = block_sum(s, red, tid);
         const double alpha = Q[j * rs + j * cs];
         double tau = 0.0;
         if (s > 1e-300) {
@@ -157,7 +96,7 @@ __device__ void sq_fallback_householder(const double* A, int64_t ars, int64_t ac
             for (int c = j + 1; c < n; ++c) {
                 double w = 0.0;
                 for (int64_t r = j + 1 + tid; r < m; r += 256) w += Q[r * rs + j * cs] * Q[r * rs + c * cs];
-                w = sq_block_sum(w, red, tid);
+                w = block_sum(w, red, tid);
                 if (tid == 0) wv[c] = tau * (w + Q[j * rs + c * cs]);
                 __syncthreads();
                 const double tw = wv[c];
@@ -184,7 +123,7 @@ __device__ void sq_fallback_householder(const double* A, int64_t ars, int64_t ac
         for (int c = j + 1; c < n; ++c) {
             double w = 0.0;
             for (int64_t r = j + 1 + tid; r < m; r += 256) w += Q[r * rs + j * cs] * Q[r * rs + c * cs];
-            w = sq_block_sum(w, red, tid);
+            w = block_sum(w, red, tid);
             const double tw = tau * w;
             for (int64_t r = j + 1 + tid; r < m; r += 256) Q[r * rs + c * cs] -= Q[r * rs + j * cs] * tw;
             if (tid == 0) Q[j * rs + c * cs] = -tw;
@@ -240,7 +179,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
     const bool multi = nblk > 1;
     int64_t r0;
     int nr;
-    sq_block_rows(a.m, nblk, blk, r0, nr);
+    block_rows(a.m, nblk, blk, r0, nr);
     int nbar = 0;
     bool alive = true;
     // ---- load: rows r0 .. r0+nr-1 into the tile, scaled by the power of two that brings its largest entry into [0.5, 1).
@@ -324,7 +263,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int gi = ti * 16 + lk + 4 * r, gj = tj * 16 + li;
-                    if (dst) { sq_st(dst + gi * N + gj, acc[r]); if (ti != tj) sq_st(dst + gj * N + gi, acc[r]); }
+                    if (dst) { st_agent(dst + gi * N + gj, acc[r]); if (ti != tj) st_agent(dst + gj * N + gi, acc[r]); }
                     else { Gs[gi * P + gj] = acc[r]; if (ti != tj) Gs[gj * P + gi] = acc[r]; }
                 }
             }
@@ -338,7 +277,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
         int emax = 0;
         if (weights) {
             int e = -100000;
-            for (int i = lane; i < nblk; i += 64) { const int x = sq_ldi(a.bexp + i); e = x > e ? x : e; }
+            for (int i = lane; i < nblk; i += 64) { const int x = ldi_agent(a.bexp + i); e = x > e ? x : e; }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(e, o, 64); e = y > e ? y : e; }
             emax = e;
@@ -355,26 +294,26 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
                         const bool in = b0 + u < nblk;
-                        v[u] = in ? sq_ld(part + (int64_t)(b0 + u) * N * N + e) : 0.0;
-                        xe[u] = (weights && in) ? sq_ldi(a.bexp + b0 + u) : emax;
+                        v[u] = in ? ld_agent(part + (int64_t)(b0 + u) * N * N + e) : 0.0;
+                        xe[u] = (weights && in) ? ldi_agent(a.bexp + b0 + u) : emax;
                     }
 #pragma unroll
                     for (int u = 0; u < 8; ++u) acc = fma(weights ? ldexp(1.0, 2 * (xe[u] - emax)) : 1.0, v[u], acc);
                 }
-                sq_st(gsum + e, acc);
+                st_agent(gsum + e, acc);
             }
         }
-        if (!sq_grid_barrier(&a.stt->counter, (++nbar) * nblk, &s_flag, tid, a.spin_limit)) return false;
+        if (!grid_barrier<1>(&a.stt->counter, (++nbar) * nblk, &s_flag, tid, a.spin_limit)) return false;
 #pragma unroll
         for (int u = 0; u < N * N / 256; ++u) {
             const int e = tid + 256 * u;
-            Gs[(e / N) * P + (e % N)] = sq_ld(gsum + e);
+            Gs[(e / N) * P + (e % N)] = ld_agent(gsum + e);
         }
         __syncthreads();
         return true;
     };
     // decision + Cholesky with deferral of the Gram matrix in Gs.  The distance from the identity is measured by all threads; the
-    // factorisation runs in wave 0 in blocks of 32 rows (the scheme of cq_tail_fused): 32 right-looking steps on the block row
+    // factorisation runs in wave 0 in blocks of 32 rows (the scheme of cq_tail_any in cholqr.hip): 32 right-looking steps on the block row
     // [R11 R12] with lane = column (all N columns at once: 32 registers per lane), then -- N = 64 -- the Schur complement
     // S = G22 - R12^T R12 on the matrix cores and 32 steps on S.  A deferred pivot leaves row j = e_j (R12's row j = 0 with it).
     auto factor = [&](int pass, int emax) {
@@ -392,7 +331,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
         __syncthreads();
         dev = fmax(fmax(red[4], red[5]), fmax(red[6], red[7]));
         int dec = 0;
-        if (pass > 0 && dev <= SQ_DONE) dec = 1;
+        if (pass > 0 && dev <= CQ_DONE) dec = 1;
         else if (pass >= a.maxpass) dec = 2;
         if (tid == 0) {
             s_out[0] = dec; s_out[4] = emax;
@@ -401,12 +340,12 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
         if (dec == 0 && tid < 64) {
             const int k = lane & (N - 1);
             // squared norm of column k before any reduction: zero (underflowing, non-finite) columns are refilled with noise in the
-            // next pass, a pivot below SQ_THETA of it is deferred
+            // next pass, a pivot below CQ_THETA of it is deferred
             const double gd = (k < n) ? Gs[k * P + k] : 1.0;
             const bool zero_k = !(gd > 1e-290) || !(gd < 1e300);
             unsigned long long deadmask = __ballot(zero_k);
             if (N == 32) deadmask &= 0xffffffffull;
-            const double thr_k = zero_k ? 1e308 : SQ_THETA * gd;
+            const double thr_k = zero_k ? 1e308 : CQ_THETA * gd;
             unsigned long long badmask = 0ull;
             // 32 steps on rows row0 .. row0+31: g[i] = entry (row0 + i, column kc) of the reduced matrix, thr of column kc; writes rows
             // row0.. of R (columns >= row0) and returns this lane's diagonal entry (lanes row0 <= kc < row0 + 32)
@@ -415,28 +354,28 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
                 const int kk = kc - row0;                  // column relative to the block (>= 32: the R12 part)
 #pragma unroll
                 for (int j = 0; j < 32; ++j) {
-                    const double d = sq_readlane(g[j], j), thr = sq_readlane(thr_c, j);
+                    const double d = readlane_f64(g[j], j), thr = readlane_f64(thr_c, j);
                     const bool ok = d > thr;
                     badmask |= ok ? 0ull : (1ull << (row0 + j));
-                    const double rinv = sq_rsqrt2(ok ? d : 1.0);
+                    const double rinv = rsqrt2(ok ? d : 1.0);
                     double r = (kk >= j) ? g[j] * (ok ? rinv : 0.0) : 0.0;
                     r = (!ok && kk == j) ? 1.0 : r;
                     if (j == kk) dkk = r;
                     if (store) Rf[(row0 + j) * RP + kc] = r;
                     if (j < 31) {
-                        const double m1 = sq_readlane(r, j + 1);
+                        const double m1 = readlane_f64(r, j + 1);
                         const int i0 = (j + 3) & ~1;
                         double2 mm[16];
                         double m2 = 0.0;
                         if (j + 2 < 32 && ((j + 2) & 1)) m2 = Rf[(row0 + j) * RP + row0 + j + 2];
 #pragma unroll
                         for (int i = i0; i < 32; i += 2) mm[i >> 1] = *reinterpret_cast<const double2*>(&Rf[(row0 + j) * RP + row0 + i]);
-                        sq_fnma(g[j + 1], m1, r);
-                        if (j + 2 < 32 && ((j + 2) & 1)) sq_fnma(g[j + 2], m2, r);
+                        fnma(g[j + 1], m1, r);
+                        if (j + 2 < 32 && ((j + 2) & 1)) fnma(g[j + 2], m2, r);
 #pragma unroll
                         for (int i = i0; i < 32; i += 2) {
-                            sq_fnma(g[i], mm[i >> 1].x, r);
-                            sq_fnma(g[i + 1], mm[i >> 1].y, r);
+                            fnma(g[i], mm[i >> 1].x, r);
+                            fnma(g[i + 1], mm[i >> 1].y, r);
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -489,7 +428,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
                 if (lane < N) Rf[N * RP + k] = fast_rcp(dkk);
             }
             if (lane == 0) {
-                s_out[1] = (pass > 0 && dev <= SQ_LAST && badmask == 0ull) ? 1 : 0;
+                s_out[1] = (pass > 0 && dev <= CQ_LAST && badmask == 0ull) ? 1 : 0;
                 s_out[2] = (int)(unsigned)(deadmask & 0xffffffffull);
                 s_out[3] = (int)(unsigned)(deadmask >> 32);
             }
@@ -519,8 +458,8 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
             const double xj = sq_group_bcast<TPR>(x[lj] * dc, owner);
 #pragma unroll
             for (int p = (j >> 1) / TPR; p < NP; ++p) {
-                sq_fnma(x[2 * p], xj, mc[p].x);
-                sq_fnma(x[2 * p + 1], xj, mc[p].y);
+                fnma(x[2 * p], xj, mc[p].x);
+                fnma(x[2 * p + 1], xj, mc[p].y);
             }
             if (sub == owner) x[lj] = xj;
             __builtin_amdgcn_sched_barrier(0);
@@ -532,7 +471,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
 #pragma unroll
             for (int l = 0; l < XL; ++l) {
                 const int c = 2 * ((l >> 1) * TPR + sub) + (l & 1);
-                if ((deadmask >> c) & 1ull) x[l] = (row < nr) ? sq_hash_unit(seed + (uint64_t)(r0 + row) * 64 + c) : 0.0;
+                if ((deadmask >> c) & 1ull) x[l] = (row < nr) ? hash_unit(seed + (uint64_t)(r0 + row) * 64 + c) : 0.0;
             }
         }
 #pragma unroll
@@ -578,8 +517,8 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
     // ---- pass 0: Gram matrix of the input
     if (multi) {
         block_gram(a.part + (int64_t)blk * N * N);
-        if (tid == 0) sq_sti(a.bexp + blk, ex);
-        alive = sq_grid_barrier(&a.stt->counter, (++nbar) * nblk, &s_flag, tid, a.spin_limit);
+        if (tid == 0) sti_agent(a.bexp + blk, ex);
+        alive = grid_barrier<1>(&a.stt->counter, (++nbar) * nblk, &s_flag, tid, a.spin_limit);
         if (alive) alive = gather_gram(0, true, emax);
     } else {
         block_gram(nullptr);
@@ -613,7 +552,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
             if (fin) { dec = 1; break; }
             if (multi) {
                 block_gram(a.part + ((int64_t)(t & 1) * nblk + blk) * N * N);
-                alive = sq_grid_barrier(&a.stt->counter, (++nbar) * nblk, &s_flag, tid, a.spin_limit);
+                alive = grid_barrier<1>(&a.stt->counter, (++nbar) * nblk, &s_flag, tid, a.spin_limit);
                 int dummy;
                 if (alive) alive = gather_gram(t & 1, false, dummy);
                 if (!alive) break;
@@ -716,7 +655,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
                 __syncthreads();
                 unsigned long long mx = 0ull;
                 for (int e = tid; e < n * n; e += 256) {
-                    const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(sq_ld(a.R + (int64_t)(e / n) * a.rrs + (int64_t)(e % n) * a.rcs)));
+                    const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(ld_agent(a.R + (int64_t)(e / n) * a.rrs + (int64_t)(e % n) * a.rcs)));
                     mx = b > mx ? b : mx;
                 }
                 __shared__ unsigned long long fred[4];
@@ -730,13 +669,13 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
                 if (tid == 0) { a.nf_out2[0] = f; a.nf_out2[1] = inv; }
                 for (int e = tid; e < n * n; e += 256) {
                     double* p = a.R + (int64_t)(e / n) * a.rrs + (int64_t)(e % n) * a.rcs;
-                    *p = sq_ld(p) * inv;
+                    *p = ld_agent(p) * inv;
                 }
             }
             if (tid == 0) { atomicAdd(&a.stats[0], 1ull); atomicAdd(&a.stats[1], (unsigned long long)passes); atomicAdd(&a.stats[2], 1ull); }
         }
     } else {
-        // a barrier gave up: poison the outputs, book the time-out (the host checks the counter: cholqr_timeouts)
+        // a barrier gave up: poison the outputs, book the time-out (the host checks the counter: fused_timeouts)
         const double bad = __longlong_as_double(0x7ff8000000000000LL);
         for (int e = tid; e < nr * n; e += 256) a.Q[(r0 + e / n) * a.qrs + (e % n) * a.qcs] = bad;
         if (blk == 0) {
@@ -747,7 +686,7 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
     }
     SQ_CLK(9);
     // the last workgroup to leave clears the barrier counter for the stream's next launch (a launch that gave up leaves it to the
-    // host: the stream is taken off the single-launch forms and its state is cleared, see cholqr_timeouts)
+    // host: the stream is taken off the single-launch forms and its state is cleared, see fused_timeouts)
     if (multi && tid == 0) {
         __threadfence();
         const int prev = atomicAdd(&a.stt->exits, 1);
@@ -757,32 +696,8 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-static SqState* sq_state_of(int slot) {
-    static std::mutex mu;
-    static char* base[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!base[dev]) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(sq_state_pool)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        base[dev] = (char*)p;
-    }
-    return (SqState*)base[dev] + slot;
-}
-static unsigned long long* sq_stats_of(int slot) {
-    static std::mutex mu;
-    static char* base[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!base[dev]) {
-        void* p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(sq_stats)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        base[dev] = (char*)p;
-    }
-    return (unsigned long long*)base[dev] + 4 * slot;
-}
+static SqState* sq_state_of(int slot) { return (SqState*)device_pool_slot(HIP_SYMBOL(sq_state_pool), sizeof(SqState), slot); }
+static unsigned long long* sq_stats_of(int slot) { return (unsigned long long*)device_pool_slot(HIP_SYMBOL(sq_stats), 4 * sizeof(unsigned long long), slot); }
 
 int64_t smallqr_ws_bytes(int64_t m, int64_t n) {
     const int N = n <= 32 ? 32 : 64;
@@ -823,12 +738,8 @@ int smallqr_factor(hipStream_t st, const double* A, int64_t rs, int64_t cs, int6
     if (!a.stt || !a.stats) return 1;
     a.seed = 0x5bd1e995u + 1315423911ull * (uint64_t)(m * 131 + n);
     a.nblk = nblk;
-    static const int maxpass = [] { const char* e = getenv("TN_PANEL_MAXPASS"); const int v = e ? atoi(e) : SQ_MAXPASS; return v >= 1 && v <= SQ_MAXPASS ? v : SQ_MAXPASS; }();
-    a.maxpass = maxpass;
-    {
-        const char* e = getenv("TN_PANEL_SPIN_LIMIT");                 // tests: force the barriers to give up
-        a.spin_limit = e ? (unsigned)strtoul(e, nullptr, 10) : (1u << 22);
-    }
+    a.maxpass = panel_maxpass();
+    a.spin_limit = panel_spin_limit();
     if (nblk > 1) fused_note_launch();
     prof_begin(st, PROF_PANEL);
     if (N == 32) hipLaunchKernelGGL((sq_kernel<32, 256>), dim3(nblk), dim3(256), 0, st, a);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devprim.h"
 
 namespace tn {
 

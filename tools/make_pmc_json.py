@@ -66,7 +66,7 @@ wb = sum(kern[k]['write_bytes_per_launch'] * kern[k]['dispatches'] for k in ts)
 # substitution pass reads and writes it (16 B), the post launch reads it and writes Y and W (24 B); two passes per panel assumed
 # (the six-launch chain of the 16384 x 1024 QR); the single-launch form of the 4096 x 512 QR moves the panel in and Y, W out (24 B)
 alg = 0.0
-six_launch = any('cq_gram_kernel' in k for k in kern)          # (a lone stream is always admitted to the single-launch form, cq_big_admit)
+six_launch = any('cq_gram_kernel' in k for k in kern)          # (a lone stream is always admitted to the single-launch form, FusedTallLaunch in csrc/fused.hip)
 for p in range(32):
     rows = 16384 - 32 * p
     alg += ((8.0 + 2 * 16.0 + 24.0) if six_launch else 24.0) * rows * 32
