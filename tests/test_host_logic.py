@@ -30,6 +30,26 @@ def test_library_exports_every_declared_symbol():
     assert b'null operand' in buf.value
 
 
+def test_every_switch_the_sources_read_is_in_the_switch_table():
+    """INTEGRATION.md §3 lists every environment switch: the ones the library reads through the readers of csrc/common.h
+    (env_flag_on, env_int, ...) and the ones the Python package takes from os.environ."""
+    from tnac4o_amd import _lib
+    names = set()
+    for f in sorted(os.listdir(_lib.CSRC)):
+        if f.endswith(('.hip', '.h')):
+            text = open(os.path.join(_lib.CSRC, f)).read()
+            assert 'getenv(' not in text or f == 'common.h', '%s reads the environment past the readers of common.h' % f
+            names |= set(re.findall(r'\benv_[a-z0-9_]+\(\s*"(TN_[A-Z0-9_]+)"', text))
+    for f in sorted(os.listdir(_lib.HERE)):
+        if f.endswith('.py'):
+            text = open(os.path.join(_lib.HERE, f)).read()
+            names |= set(re.findall(r'os\.environ(?:\.get\(|\[)\s*[\'"](TN_[A-Z0-9_]+)[\'"]', text))
+    assert {'TN_QR_NBO', 'TN_PANEL_CAPTURE_MIN', 'TN_PANEL_CAPTURE_MAXROWS', 'TN_NATIVE_CHAIN'} <= names      # both kinds of reader are seen
+    table = open(os.path.join(os.path.dirname(_lib.HERE), 'INTEGRATION.md')).read()
+    listed = set(re.findall(r'TN_[A-Z0-9_]+', table))
+    assert names <= listed, sorted(names - listed)
+
+
 def test_product_refuses_cpu_tensors():
     import torch
     from tnac4o_amd import ops

@@ -161,7 +161,8 @@ def build(verbose=False):
 
     with ThreadPoolExecutor(max_workers=int(os.environ.get('TN_BUILD_JOBS', '6'))) as ex:
         objs = list(ex.map(one, SOURCES))
-    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC'] + os.environ.get('TN_EXTRA_HIPCC_FLAGS', '').split() + ['-o', LIB_PATH] + objs
+    # --no-undefined: a declaration of common.h that has drifted from its definition fails here, not when the library is loaded
+    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,--no-undefined'] + os.environ.get('TN_EXTRA_HIPCC_FLAGS', '').split() + ['-o', LIB_PATH] + objs
     if verbose:
         print(' '.join(cmd), flush=True)
     subprocess.run(cmd, check=True)

@@ -16,53 +16,6 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err; }
 
-// implemented in the other translation units
-int absorb(hipStream_t, const double*, const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t,
-           int64_t, int64_t, int64_t);
-int svd_trunc(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*,
-              double*, int64_t, int64_t, int64_t*, double*, int*, int*, void*, int64_t);
-int svd_vals(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*, int*, int*, void*, int64_t);
-int64_t svd_ws_bytes(int64_t, int64_t, int);
-int svd_vals_small_async(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*);
-int svd_vals_small_batched(hipStream_t, const int64_t*, int64_t, double*);
-int nfactor(hipStream_t, const double*, int64_t, double*, void*);
-int scale_by(hipStream_t, double*, int64_t, const double*);
-int normalize_pow2(hipStream_t, double*, int64_t, double*, void*, int64_t);
-int scale_phys(hipStream_t, double*, int64_t, int64_t, int64_t, const double*, int);
-int calc_pn(hipStream_t, const double*, const double*, const double*, const int32_t*, const int32_t*, const int32_t*,
-            const int32_t*, const int32_t*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double*,
-            double*, const double*, double*);
-int merge_groups(hipStream_t, const double*, const double*, const int64_t*, const int64_t*, const int64_t*, int64_t, double, int64_t*, int64_t*,
-                 double*);
-int nfactor_batched(hipStream_t, double*, int64_t, int64_t);
-int peps_factor(hipStream_t, const double*, const double*, const double*, const double*, const double*, const double*, const double*,
-                const int32_t*, const int32_t*, int64_t, int64_t, int64_t, double*);
-int mpo_from_factor(hipStream_t, const double*, const int32_t*, const int32_t*, int64_t, int64_t, int64_t, int64_t, int64_t, double*);
-int env_rr_batched(hipStream_t, const double*, const double*, const double*, const int32_t*, const int32_t*, int64_t, int64_t, int64_t,
-                   int64_t, int64_t, int64_t, int64_t, double*);
-int env_rl_batched(hipStream_t, const double*, const int32_t*, const int32_t*, int64_t, int64_t, int64_t, double*);
-int balance(hipStream_t, const double*, int64_t, int64_t, int64_t, double, double*, int*);
-int64_t site_qr_ws_bytes(int, int64_t, int64_t, int64_t, int64_t, int);
-int site_qr(hipStream_t, int, double*, int64_t, int64_t, int64_t, const double*, int64_t, double*, double*, double, int64_t*, double*, int*,
-            void*, int64_t, double*, int, int64_t*);
-int gram_weights(hipStream_t, const double*, int64_t, double, double*, double*);
-int rows_norm2(hipStream_t, const double*, int64_t, int64_t, double*);
-int bond_deflate(hipStream_t, int, const double*, int64_t, int64_t, const double*, int64_t, double*, double*, int64_t*, double*, void*, int64_t);
-int gather_scale_rows(hipStream_t, const double*, int64_t, int64_t, const int64_t*, const double*, double*, int);
-int64_t rar_ws_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
-int rar(hipStream_t, const double*, const double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double*, void*, int64_t);
-int64_t env_mix_ws_bytes(int, int64_t, int64_t, int64_t, int64_t, int64_t);
-int env_mix(hipStream_t, int, const double*, const double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double*, void*,
-            int64_t);
-int64_t apply_truncation_ws_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
-int apply_truncation(hipStream_t, const double*, int64_t, int64_t, const double*, int64_t, int64_t, int64_t, const double*, int64_t, int64_t,
-                     const double*, int64_t, int64_t, const double*, double*, double*, double*, void*, int64_t);
-int qr_batched(hipStream_t, double*, int64_t, int64_t, int64_t, int64_t, double*, int64_t, int64_t, double*, int64_t, int64_t, int, double,
-               int64_t*, int64_t, int64_t, int64_t, int64_t, void*, int64_t, void* const*, int);
-int svd_trunc_batched(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*,
-                      double*, int64_t, int64_t, int64_t*, double*, int*, int*, int64_t, int64_t, int64_t, int64_t, int64_t, void*, int64_t);
-int svd_vals_batched(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*, int*, int*, int64_t, int64_t, void*, int64_t);
-
 }  // namespace tn
 
 using namespace tn;
@@ -154,8 +107,7 @@ int tn_qr(double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, in
     TN_CHECK_ARG(A && Q && R && ws, "null operand");
     TN_CHECK_ARG(rank_tol >= 0.0 && rank_tol < 1.0, "rank_tol out of range");
     ProfPhase ph(PH_QR);
-    const double dm = (double)m, dn = (double)(n < m ? n : m);
-    prof_note(PROF_QR_NOMINAL, 1, 4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn, 8.0 * (2.0 * dm * dn + dn * dn));
+    prof_note_qr(m, n, 1);
     return qr_factor(ST, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host);
 }
 int64_t tn_qr_ws_bytes(int64_t m, int64_t n, int nb) { return qr_ws_bytes(m, n, nb); }
@@ -214,26 +166,21 @@ int tn_svd_trunc(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n
     const int rc = svd_trunc(ST, C, crs, ccs, k, n, Dmax, tol, U, urs, ucs, S, Vt, vrs, vcs, keep_host, discarded_host, &sweeps,
                              info_host, ws, ws_bytes);
     if (sweeps_host) *sweeps_host = sweeps;
-    // nominal counts of SURVEY.md 8(d) with m = max(k, n), n = min(k, n)
-    const double dm = (double)(k > n ? k : n), dn = (double)(k > n ? n : k);
-    prof_note(PROF_SVD_NOMINAL, 1, 14.0 * dm * dn * dn + 8.0 * dn * dn * dn, 8.0 * (2.0 * dm * dn + dn * dn + dn));
-    prof_note(PROF_SVD_STREAM, sweeps, 0.0, (double)sweeps * (dn - 1.0) * 16.0 * dn * (dm + dn));
+    prof_note_svd(k, n, sweeps);
     return rc;
 }
 int tn_svdvals(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* S_host, int* sweeps_host,
                int* info_host, void* ws, int64_t ws_bytes, void* stream) {
     TN_CHECK_ARG(C && S_host && ws, "null operand");
     ProfPhase ph(PH_SVDVALS);
-    const double dm = (double)(k > n ? k : n), dn = (double)(k > n ? n : k);
-    prof_note(PROF_SVDVALS_NOMINAL, 1, 4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn, 8.0 * (dm * dn + dn));
+    prof_note_svdvals(k, n);
     return svd_vals(ST, C, crs, ccs, k, n, S_host, sweeps_host, info_host, ws, ws_bytes);
 }
 int64_t tn_svd_ws_bytes(int64_t k, int64_t n, int vectors) { return svd_ws_bytes(k, n, vectors); }
 int tn_svdvals_async(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* out66_dev, void* stream) {
     TN_CHECK_ARG(C && out66_dev, "null operand");
     ProfPhase ph(PH_SVDVALS);
-    const double dm = (double)(k > n ? k : n), dn = (double)(k > n ? n : k);
-    prof_note(PROF_SVDVALS_NOMINAL, 1, 4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn, 8.0 * (dm * dn + dn));
+    prof_note_svdvals(k, n);
     return svd_vals_small_async(ST, C, crs, ccs, k, n, out66_dev);
 }
 
@@ -323,8 +270,7 @@ int tn_qr_batched(double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, doubl
     TN_CHECK_ARG(batch == 0 || (A && Q && R && ws), "null operand");
     TN_CHECK_ARG(rank_tol >= 0.0 && rank_tol < 1.0, "rank_tol out of range");
     ProfPhase ph(PH_QR);
-    const double dm = (double)m, dn = (double)(n < m ? n : m);
-    prof_note(PROF_QR_NOMINAL, (double)batch, batch * (4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn), batch * 8.0 * (2.0 * dm * dn + dn * dn));
+    prof_note_qr(m, n, batch);
     return qr_batched(ST, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, rank_tol, keff_host, batch, bsA, bsQ, bsR, ws, ws_bytes,
                       side_streams, nside);
 }

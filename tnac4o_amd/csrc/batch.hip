@@ -11,11 +11,6 @@
 
 namespace tn {
 
-int svd_trunc(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*,
-              double*, int64_t, int64_t, int64_t*, double*, int*, int*, void*, int64_t);
-int svd_vals(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*, int*, int*, void*, int64_t);
-int64_t svd_ws_bytes(int64_t, int64_t, int);
-
 constexpr int MAX_SIDE = 8;
 
 struct ForkJoin {                        // per host thread, created on first use, destroyed with the thread

@@ -25,20 +25,6 @@
 
 namespace tn {
 
-int gemm(hipStream_t st, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t rsa, int64_t csa, const double* B, int64_t rsb,
-         int64_t csb, double beta, double* C, int64_t rsc, int64_t csc, int64_t batch, int64_t bsa, int64_t bsb, int64_t bsc, double* ws, int64_t ws_bytes);
-int64_t gemm_ws_bytes(int64_t M, int64_t N, int64_t K, int64_t batch);
-int calc_pn(hipStream_t st, const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
-            const int32_t* suf, const int32_t* lidx, const int32_t* uidx, int64_t nb, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br,
-            double* P, double* minP, const double* parent_log2p, double* log2p_out);
-int merge_groups(hipStream_t st, const double* E, const double* lp, const int64_t* deg, const int64_t* pos, const int64_t* starts, int64_t ng,
-                 double min_dEng, int64_t* rep_pos, int64_t* degn, double* lpn);
-int env_rr_batched(hipStream_t st, const double* A, const double* RRprev, const double* W, const int32_t* parent, const int32_t* uidx, int64_t nk,
-                   int64_t Dl, int64_t p, int64_t Dr, int64_t bl, int64_t br, int64_t pu, double* out);
-int env_rl_batched(hipStream_t st, const double* T1, const int32_t* par, const int32_t* didx, int64_t nk, int64_t p, int64_t Dr, double* out);
-int mpo_from_factor(hipStream_t st, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nl, int64_t nu, int64_t pd, int64_t br,
-                    double* W);
-
 namespace {
 
 #define BS(call)                   \
@@ -237,14 +223,7 @@ struct Search {
     double* scal = nullptr;             // device scalars: [0] pd_max, [1] globalmin, [2] local max, [3] rest max, [4] min of minP
     int32_t* counter = nullptr;         // device: number of selected items
 
-    int read_i32(const int32_t* dev, int32_t& v) {
-        int32_t* stage = (int32_t*)pinned_host(8, 7);
-        int32_t tmp = 0;
-        BSH(hipMemcpyAsync(stage ? stage : &tmp, dev, 4, hipMemcpyDeviceToHost, st), "beam search: read-back");
-        BSH(hipStreamSynchronize(st), "beam search: synchronise");
-        v = stage ? *stage : tmp;
-        return 0;
-    }
+    int read_i32(const int32_t* dev, int32_t& v) { return read_back(st, &v, dev, 4, PIN_SHARED, "beam search: read-back"); }
     // sorted unique of n int64 keys: number of groups (host), inverse, first members, sorted order, group offsets (any may be NULL)
     int unique(Bump scratch, const int64_t* key, int64_t n, int64_t& ng, int32_t* inv, int32_t* first, int32_t* sidx_out, int64_t* starts) {
         TAKE(skey, int64_t, scratch, n, "sorted keys");
@@ -377,10 +356,7 @@ int tn_beam_search_team(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64
     TN_CHECK_LAUNCH("iota_kernel");
     {   // the root: one branch, all indices 0, log2 p = 0, degeneracy 1; pd_max = -inf, globalmin = 0
         const double h[8] = {NEG_INF, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        double* stage = (double*)pinned_host(64, 7);
-        if (stage) memcpy(stage, h, 64);
-        BSH(hipMemcpyAsync(S.scal, stage ? stage : h, 64, hipMemcpyHostToDevice, st), "beam search: scalars");
-        if (!stage) BSH(hipStreamSynchronize(st), "beam search: synchronise");
+        BS(upload(st, S.scal, h, 64, PIN_SHARED, "beam search: scalars"));
         BSH(hipMemsetAsync(gen[0].vind, 0, (size_t)ncol * cap * 4, st), "beam search: clear");
         BSH(hipMemsetAsync(gen[0].states, 0, (size_t)cap * nsites * 2, st), "beam search: clear");
         BSH(hipMemsetAsync(gen[0].Eng, 0, 8, st), "beam search: clear");
@@ -580,10 +556,7 @@ int tn_beam_search_team(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64
     BSH(hipMemcpyAsync(log2p_out, f.prob, (size_t)nb * 8, hipMemcpyDeviceToDevice, st), "beam search: results");
     BSH(hipMemcpyAsync(deg_out, f.deg, (size_t)nb * 8, hipMemcpyDeviceToDevice, st), "beam search: results");
     double hs[2] = {0.0, 0.0};
-    double* stage = (double*)pinned_host(16, 7);
-    BSH(hipMemcpyAsync(stage ? stage : hs, S.scal, 16, hipMemcpyDeviceToHost, st), "beam search: scalars");
-    BSH(hipStreamSynchronize(st), "beam search: synchronise");
-    if (stage) { hs[0] = stage[0]; hs[1] = stage[1]; }
+    BS(read_back(st, hs, S.scal, 16, PIN_SHARED, "beam search: scalars"));
     *nb_host = nb;
     *pd_max_host = hs[0];
     *globalmin_host = hs[1];

@@ -27,32 +27,6 @@
 
 namespace tn {
 
-// ---- other translation units ----------------------------------------------------------------------------------------------
-int absorb(hipStream_t, const double*, const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t,
-           int64_t, int64_t, int64_t);
-int copy_mat(hipStream_t, const double*, int64_t, int64_t, double*, int64_t, int64_t, int64_t, int64_t);
-int svd_trunc(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double, double*, int64_t, int64_t, double*, double*,
-              int64_t, int64_t, int64_t*, double*, int*, int*, void*, int64_t);
-int svd_vals(hipStream_t, const double*, int64_t, int64_t, int64_t, int64_t, double*, int*, int*, void*, int64_t);
-int64_t svd_ws_bytes(int64_t, int64_t, int);
-int svd_vals_small_batched(hipStream_t, const int64_t*, int64_t, double*);
-int normalize_pow2(hipStream_t, double*, int64_t, double*, void*, int64_t);
-int64_t site_qr_ws_bytes(int, int64_t, int64_t, int64_t, int64_t, int);
-int site_qr(hipStream_t, int, double*, int64_t, int64_t, int64_t, const double*, int64_t, double*, double*, double, int64_t*, double*, int*,
-            void*, int64_t, double*, int, int64_t*);
-int gram_weights(hipStream_t, const double*, int64_t, double, double*, double*);
-int rows_norm2(hipStream_t, const double*, int64_t, int64_t, double*);
-int bond_deflate(hipStream_t, int, const double*, int64_t, int64_t, const double*, int64_t, double*, double*, int64_t*, double*, void*, int64_t);
-int gather_scale_rows(hipStream_t, const double*, int64_t, int64_t, const int64_t*, const double*, double*, int);
-int64_t rar_ws_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
-int rar(hipStream_t, const double*, const double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double*, void*, int64_t);
-int64_t env_mix_ws_bytes(int, int64_t, int64_t, int64_t, int64_t, int64_t);
-int env_mix(hipStream_t, int, const double*, const double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, double*, void*,
-            int64_t);
-int64_t apply_truncation_ws_bytes(int64_t, int64_t, int64_t, int64_t, int64_t);
-int apply_truncation(hipStream_t, const double*, int64_t, int64_t, const double*, int64_t, int64_t, int64_t, const double*, int64_t, int64_t,
-                     const double*, int64_t, int64_t, const double*, double*, double*, double*, void*, int64_t);
-
 // ---- small kernels --------------------------------------------------------------------------------------------------------
 // out (n0, n1, n2, n3) contiguous  <-  in[i0 s0 + i1 s1 + i2 s2 + i3 s3]     (torch's permute(...).contiguous())
 __global__ __launch_bounds__(256) void permute4_kernel(const double* __restrict__ in, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t n0,
@@ -261,7 +235,7 @@ struct PassClock {
     double tr[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};      // truncating passes 2 / 3 / 4: site factorisation | deflation | decomposition | projectors
     double sub[4] = {0, 0, 0, 0};      // inside pass 1: Gram recursion + weights | attach, norms, sort, gather | pivoted factorisation | un-weighting, normalisation
     long calls = 0;
-    PassClock() { const char* e = getenv("TN_CHAIN_PASSES"); on = e && e[0] == '1'; }
+    PassClock() : on(env_flag_set("TN_CHAIN_PASSES")) {}
     ~PassClock() {
         if (!on || !calls) return;
         static const char* nm[8] = {"absorb", "pass 1 (canonise_right, weighted)", "pass 2 (canonise_left, 4 chi)", "variational, 1 sweep",
@@ -414,10 +388,6 @@ public:
         const hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
         return e == hipSuccess ? 0 : hip_fail(e, "device to host copy");
     }
-    int h2d(void* dev, const void* host, size_t bytes) {
-        const hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st);
-        return e == hipSuccess ? 0 : hip_fail(e, "host to device copy");
-    }
 
     // ---- one canonisation step (ops.site_qr + MPS._site_left / _site_right) ----
     // side 0: Q (m x k) row-major, Rm (k x n);  side 1: Q = Q^T (k x m), Rm = R^T (n x k).  Cm == nullptr: no attach, A[n] is consumed.
@@ -509,9 +479,7 @@ public:
         {
             ProfPhase ph(PH_SVD);
             CH(svd_trunc(st, Cp, crs, ccs, k, n, cap, tol, o.U.p, cap, 1, o.S, o.Vt.p, n, 1, &keep, &disc, &sweeps, &info, w, wsb));
-            const double dm = (double)(k > n ? k : n), dn = (double)(k > n ? n : k);
-            prof_note(PROF_SVD_NOMINAL, 1, 14.0 * dm * dn * dn + 8.0 * dn * dn * dn, 8.0 * (2.0 * dm * dn + dn * dn + dn));
-            prof_note(PROF_SVD_STREAM, sweeps, 0.0, (double)sweeps * (dn - 1.0) * 16.0 * dn * (dm + dn));
+            prof_note_svd(k, n, sweeps);
         }
         o.keep = keep;
         o.disc = disc;
@@ -589,7 +557,7 @@ public:
         if (o.disc > 32.0 * CH_EPS) pass_truncated = true;          // this pass has changed the state by more than rounding
         if (trmark) trmark->trlap(pass_id, 2);
         {   // TN_DEFLATE_TRACE=1 (diagnostics): what every truncation kept, next to what tn_bond_deflate would keep of the same bond
-            static const bool trace = [] { const char* e = getenv("TN_DEFLATE_TRACE"); return e && e[0] == '1'; }();
+            static const bool trace = env_flag_set("TN_DEFLATE_TRACE");
             if (trace) {
                 const int64_t k = pass_side == 0 ? C.r : C.c, n = pass_side == 0 ? C.c : C.r;
                 int64_t kk = k;
@@ -638,14 +606,14 @@ public:
     int target_swapped = 0, var1_skipped = 0;
     int64_t attach_fused = 0;                // sites whose absorption went through the factors (never materialised)
     bool gauge_svd_skippable(int64_t Dmax, double tol) const {
-        const int keep_mode = [] { const char* e = getenv("TN_GAUGE_SVD"); return e ? atoi(e) : 0; }();   // 1: all, 2: those of the 2 chi pass (read per call: the tests switch it)
+        const int keep_mode = env_int("TN_GAUGE_SVD", 0);   // 1: all, 2: those of the 2 chi pass (read per call: the tests switch it)
         if (keep_mode == 1 || (keep_mode == 2 && pass_id == 3)) return false;
         return tol <= CH_EPS && std::min(C.r, C.c) <= Dmax;
     }
     // ... what is left to do at such a bond: drop the bond indices that carry nothing (tn_bond_deflate; TN_BOND_DEFLATE=0: keep them all)
     int pass_side = 0;                       // 0: left sweep (C = R, bond = rows of C / columns of A[pC-1]), 1: right sweep (C = R^T, bond = columns of C / rows of A[pC])
     int deflate_bond() {
-        const bool off = [] { const char* e = getenv("TN_BOND_DEFLATE"); return e && e[0] == '0'; }();
+        const bool off = !env_flag_on("TN_BOND_DEFLATE");
         const int64_t k = pass_side == 0 ? C.r : C.c, n = pass_side == 0 ? C.c : C.r;
         if (off || k < 2 || k > 256) return 0;
         T3& site = pass_side == 0 ? A[pC - 1] : A[pC];
@@ -841,7 +809,7 @@ public:
         // one read-back: the scale factors of the Gram matrices, the norm of the state, the 64 partial sums of ||K||_F^2 per bond
         const size_t npack = (size_t)L + 1 + 64 * used.size();
         std::vector<double> pack_pageable;
-        double* pack = (double*)pinned_host(npack * 8, 4);
+        double* pack = (double*)pinned_host(npack * 8, PIN_CHAIN_PACK);
         if (!pack) { pack_pageable.resize(npack); pack = pack_pageable.data(); }
         for (int64_t m = 1; m <= L; ++m) CH(d2h(pack + (m - 1), gfac[m], 8));
         CH(d2h(pack + L, G.p, 8));
@@ -884,7 +852,7 @@ public:
             CH(weighted_sum(st, w.d2, rn, Dl, wv, wsum));
             const size_t nh = 1 + pending.size();
             std::vector<double> host_pageable;
-            double* host = (double*)pinned_host(nh * 8 + (size_t)Dl * 8, 4);
+            double* host = (double*)pinned_host(nh * 8 + (size_t)Dl * 8, PIN_CHAIN_PACK);
             if (!host) { host_pageable.resize(nh + (size_t)Dl); host = host_pageable.data(); }
             CH(d2h(host, wsum, 8));
             for (size_t i = 0; i < pending.size(); ++i) CH(d2h(host + 1 + i, pending[i], 8));
@@ -916,12 +884,7 @@ public:
             // sort order followed by the panel pivoting: perm <- perm[piv]
             std::vector<int64_t> comp((size_t)Dl);
             for (int64_t j = 0; j < Dl; ++j) comp[j] = order[(size_t)o.piv[j]];
-            int64_t* hup = (int64_t*)pinned_host((size_t)Dl * 8, 5);
-            std::vector<int64_t>* keep_alive = nullptr;
-            if (hup) std::copy(comp.begin(), comp.end(), hup);
-            else { keep_alive = new std::vector<int64_t>(comp); hup = keep_alive->data(); }
-            CH(h2d(perm, hup, (size_t)Dl * 8));
-            if (keep_alive) { CH(sync("weighted pass: order upload")); delete keep_alive; }
+            CH(upload(st, perm, comp.data(), (size_t)Dl * 8, PIN_CHAIN_UPLOAD, "weighted pass: order upload"));
             M2 Ct;
             CH(new_m2(Dl, o.k, Ct, "centre (weights removed)"));
             CH(gather_scale_rows(st, o.Rm.p, Dl, o.k, perm, w.d2, Ct.p, 1));
@@ -950,14 +913,7 @@ public:
         CH(scratch(1, wsb, w));
         return env_mix(st, side, Rm.p, Aphi.p, Ac.p, a, s, a2, c, c2, out.p, w, wsb);
     }
-    int read_scalar(const double* dev, double& v) {
-        double* stage = (double*)pinned_host(8, 6);
-        double tmp = 0.0;
-        CH(d2h(stage ? stage : &tmp, dev, 8));
-        CH(sync("overlap"));
-        v = stage ? *stage : tmp;
-        return 0;
-    }
+    int read_scalar(const double* dev, double& v) { return read_back(st, &v, dev, 8, PIN_CHAIN_READ, "overlap"); }
     int update_RL(const std::vector<T3>& phi, int64_t n) {
         M2 nw;
         CH(env_update(0, R[n], phi[n], A[n], nw));
@@ -995,8 +951,7 @@ public:
         int sweeps = 0, info = 0;
         {
             ProfPhase ph(PH_SVDVALS);
-            const double dm = (double)(k > n ? k : n), dn = (double)(k > n ? n : k);
-            prof_note(PROF_SVDVALS_NOMINAL, 1, 4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn, 8.0 * (dm * dn + dn));
+            prof_note_svdvals(k, n);
             CH(svd_vals(st, Cm.p, Cm.c, 1, k, n, S.data(), &sweeps, &info, w, wsb));
         }
         if (info == 0) return 0;
@@ -1093,19 +1048,13 @@ public:
                 CH(new_block(5 * ns + 66 * ns, db, dd, "Schmidt table"));
                 int64_t* ddesc = (int64_t*)dd;
                 double* out66 = dd + 5 * ns;
-                int64_t* hst = (int64_t*)pinned_host(5 * ns * 8, 5);
-                if (hst) std::copy(desc.begin(), desc.end(), hst);
-                CH(h2d(ddesc, hst ? hst : desc.data(), 5 * ns * 8));
-                if (!hst) CH(sync("Schmidt descriptors"));
+                CH(upload(st, ddesc, desc.data(), 5 * ns * 8, PIN_CHAIN_UPLOAD, "Schmidt descriptors"));
                 {
                     ProfPhase ph(PH_SVDVALS);
                     CH(svd_vals_small_batched(st, ddesc, (int64_t)ns, out66));
                 }
                 table.resize(66 * ns);
-                double* stage = (double*)pinned_host(66 * ns * 8, 6);
-                CH(d2h(stage ? stage : table.data(), out66, 66 * ns * 8));
-                CH(sync("Schmidt values"));
-                if (stage) std::copy(stage, stage + 66 * ns, table.begin());
+                CH(read_back(st, table.data(), out66, 66 * ns * 8, PIN_CHAIN_READ, "Schmidt values"));
             }
             for (int64_t bnd = 0; bnd <= L; ++bnd) {
                 if (lazy_row[bnd] < 0) continue;
@@ -1251,7 +1200,7 @@ static int compress_mps_once(int64_t L, const double* const* sites_host, const i
         const bool has = mpo_host && mpo_dims_host && mpo_host[n];
         Dbig_abs = std::max(Dbig_abs, std::max(site_dims_host[3 * n] * (has ? mpo_dims_host[4 * n] : 1), site_dims_host[3 * n + 2] * (has ? mpo_dims_host[4 * n + 2] : 1)));
     }
-    const bool fuse_attach = [] { const char* e = getenv("TN_ATTACH_FUSED"); return !(e && e[0] == '0'); }() && weighted && structured &&
+    const bool fuse_attach = env_flag_on("TN_ATTACH_FUSED") && weighted && structured &&
                              Dbig_abs >= 2 * CH_PASS1_MIN_BOND;
     for (int64_t n = 0; n < L; ++n) {
         const int64_t Dl = site_dims_host[3 * n], p = site_dims_host[3 * n + 1], Dr = site_dims_host[3 * n + 2];
@@ -1324,7 +1273,8 @@ static int compress_mps_once(int64_t L, const double* const* sites_host, const i
         // cannot see the left part's null space, had to keep ~500).  Overlaps and optimised sites only depend on the STATE the target
         // represents, so that copy serves as the target from here on: the environment and projector products shrink with the square of
         // its bonds.  TN_VAR_TARGET=phi keeps the first pass's tensors (A/B, tests).
-        const bool target_phi = [] { const char* e = getenv("TN_VAR_TARGET"); return e && e[0] == 'p'; }();          // (read per call: the tests switch it)
+        const char* e_target = env_str("TN_VAR_TARGET");
+        const bool target_phi = e_target && e_target[0] == 'p';          // (read per call: the tests switch it)
         if (!ch.pass_truncated && !target_phi && tolS / 10 <= CH_EPS) { phi_small = ch.A; target = &phi_small; ch.target_swapped = 1; }
         // ... and then the one variational sweep of this stage has nothing to do: it would optimise every site of the state towards the
         // state itself (overlap 1 - O(L eps)), i.e. return it in another gauge of the same left-canonical form, which the 2 chi pass
@@ -1332,7 +1282,7 @@ static int compress_mps_once(int64_t L, const double* const* sites_host, const i
         // every bond (update_S, mps.py:550-560, compared only with later values of the same length): they are the singular values of
         // the centre matrices the 4 chi pass itself met at those bonds, recorded here the way the sweep records them -- unevaluated
         // (_LazyS).  Needs the lazy bookkeeping; TN_VAR1_SKIP=0 runs the sweep.
-        const bool var1_run = [] { const char* e = getenv("TN_VAR1_SKIP"); return e && e[0] == '0'; }();
+        const bool var1_run = !env_flag_on("TN_VAR1_SKIP");
         if (ch.target_swapped && lazy && !var1_run) {
             for (int64_t b = 1; b <= L; ++b) {
                 if (!ch.pass_C[b].p) continue;

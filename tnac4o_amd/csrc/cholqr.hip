@@ -1228,7 +1228,7 @@ int64_t cholqr_ws_bytes(int64_t nrows, int b) {
 // the stream's sticky count of single-launch panels that gave up at a barrier (cq_stats[10]), for fused_timeouts: one 8-byte read-back
 // and a synchronisation
 int cholqr_gaveup_count(hipStream_t st, int slot, unsigned long long* count) {
-    unsigned long long* h = (unsigned long long*)pinned_host(64, 7);
+    unsigned long long* h = (unsigned long long*)pinned_host(64, PIN_SHARED);
     unsigned long long tmp[8];
     if (!h) h = tmp;
     hipError_t e = hipMemcpyFromSymbolAsync(h, HIP_SYMBOL(cq_stats), 8, ((size_t)slot * 16 + 10) * 8, hipMemcpyDeviceToHost, st);
@@ -1289,10 +1289,10 @@ __global__ __launch_bounds__(256) void cq_capture_kernel(const double* X, int64_
     if (e < nrows * b) out[e] = X[(e / b) * rs + (e % b) * cs];
 }
 static void cq_capture(hipStream_t st, const double* X, int64_t irs, int64_t ics, int64_t nrows, int b, const void* ws) {
-    static const char* dir = getenv("TN_PANEL_CAPTURE");
+    static const char* dir = env_str("TN_PANEL_CAPTURE");
     if (!dir || !dir[0]) return;
-    static const int min_pass = [] { const char* e = getenv("TN_PANEL_CAPTURE_MIN"); return e ? atoi(e) : 4; }();
-    static const int64_t max_rows = [] { const char* e = getenv("TN_PANEL_CAPTURE_MAXROWS"); return e ? atoll(e) : 4096ll; }();
+    static const int min_pass = env_int("TN_PANEL_CAPTURE_MIN", 4);
+    static const int64_t max_rows = env_i64("TN_PANEL_CAPTURE_MAXROWS", 4096);
     static std::mutex mu;
     static int seq = 0;
     CqState h;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 namespace tn {
@@ -30,12 +31,41 @@ inline int hip_fail(hipError_t e, const char* what) {
         if (e__ != hipSuccess) return tn::hip_fail(e__, what); \
     } while (0)
 
-// Thread-local page-locked host buffers for the small read-backs / uploads around host decisions (slot 0..7: 0-1 tn_qr, 2-3 the
-// Jacobi SVD, 4-6 the chain driver; grown on demand,
-// released when the thread exits).  A copy into pageable memory makes hipMemcpyAsync drain the stream on the host first and only
-// then enqueue the transfer (15-20 us of idle device per read-back, 15 k read-backs per sweep); with page-locked memory the
-// transfer is queued right behind the producing kernel.  Returns nullptr if the allocation fails (callers fall back to pageable).
-void* pinned_host(size_t bytes, int slot);
+// ---- environment switches: one reader per kind.  Whether a switch is read once (`static const` at the
+// call site) or on every call (the tests switch it) is the caller's decision; these only parse.
+inline const char* env_str(const char* name) { return getenv(name); }                                             // raw text, NULL when unset
+inline bool env_flag_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }           // on unless it starts with '0'
+inline bool env_flag_set(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }             // off unless it starts with '1'
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline int64_t env_i64(const char* name, int64_t dflt) { const char* e = getenv(name); return e ? (int64_t)atoll(e) : dflt; }
+inline double env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+
+// ---- page-locked staging of the small host copies around host decisions (misc.hip) ------------------------------------
+// Thread-local page-locked host buffers, one per slot (grown on demand, released when the thread exits).  A copy into pageable
+// memory makes hipMemcpyAsync drain the stream on the host first and only then enqueue the transfer (15-20 us of idle device per
+// read-back, 15 k read-backs per sweep); with page-locked memory the transfer is queued right behind the producing kernel.
+// A slot belongs to the code named here; what it holds is valid until that code's next use of it on the same thread.
+enum PinSlot {
+    PIN_QR = 0,             // qr.hip: column norms and the permutation of the pivoted / rank-revealing factorisation
+    PIN_SVD_READ = 2,       // (1 is free)  svd.hip: norms, convergence measures, results of the Jacobi SVD; site.hip: bond_deflate's norms
+    PIN_SVD_UPLOAD = 3,     // svd.hip: tournament schedule, kept values / order (guarded by upload_slot_guard)
+    PIN_CHAIN_PACK = 4,     // chain.hip: the packed statistics of the weighted pass
+    PIN_CHAIN_UPLOAD = 5,   // chain.hip: row order of the weighted pass, Schmidt descriptors
+    PIN_CHAIN_READ = 6,     // chain.hip: overlaps, Schmidt table
+    PIN_SHARED = 7,         // three users, a few words each, none of which keeps the content across a call into another: the mailbox
+                            // ring of the device-side pivoting (qr.hip, which clears it before use for that reason), the count of
+                            // launches that gave up (cholqr_gaveup_count), the scalars of the beam search (beamsearch.hip)
+    PIN_NSLOTS
+};
+void* pinned_host(size_t bytes, PinSlot slot);      // nullptr if the allocation fails (callers fall back to pageable memory)
+// Read-back: `bytes` from `dev` on `st` through the slot (straight into pageable memory when there is none), then synchronise `st`.
+// On return the data is in `host`.  A HIP failure comes back as the library's error code with "memcpy <what>" / "sync <what>".
+int read_back(hipStream_t st, void* host, const void* dev, size_t bytes, PinSlot slot, const char* what);
+// ... for a caller that reads in place: *data points at the staged bytes (or at a pageable buffer of the thread when there is no slot)
+int read_back_staged(hipStream_t st, void** data, const void* dev, size_t bytes, PinSlot slot, const char* what);
+// Upload: stage `bytes` from `host` in the slot and enqueue the copy to `dev` on `st`; `host` may be reused at once.  No
+// synchronisation, unless there is no slot: a pageable source must outlive the copy, so `st` is synchronised then.
+int upload(hipStream_t st, void* dev, const void* host, size_t bytes, PinSlot slot, const char* what);
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
@@ -61,6 +91,10 @@ bool prof_on(int fam);
 void prof_begin(hipStream_t st, int fam);
 void prof_end(hipStream_t st, int fam, double flops, double bytes);
 void prof_note(int fam, double calls, double flops, double bytes);   // counter-only families
+// the nominal counts of the factorisations, booked by every entry point that runs one (formulas: the PROF_*_NOMINAL lines above)
+void prof_note_qr(int64_t m, int64_t n, int64_t batch);              // PROF_QR_NOMINAL: `batch` factorisations of m x n
+void prof_note_svd(int64_t k, int64_t n, int sweeps);                // PROF_SVD_NOMINAL + PROF_SVD_STREAM: one truncated SVD of k x n
+void prof_note_svdvals(int64_t k, int64_t n);                        // PROF_SVDVALS_NOMINAL: the singular values of k x n
 int prof_phase(int phase);                                           // returns the previous phase
 struct ProfPhase {                                                    // scoped phase
     int prev;
@@ -230,5 +264,106 @@ int cholqr_gaveup_count(hipStream_t st, int slot, unsigned long long* count);   
 void cholqr_state_dirty(int slot);            // the next cholqr_begin on this slot clears the state block with a memset
 int smallqr_stats(hipStream_t st, unsigned long long* out4, int reset);
 int smallqr_reset_state(hipStream_t st);
+
+// ---- copies between strided matrices (qr.hip) ------------------------------------------------------------------------------------
+// D (m x n, strides drs/dcs) <- S (m x n, strides srs/scs)
+int copy_mat(hipStream_t st, const double* S, int64_t srs, int64_t scs, double* D, int64_t drs, int64_t dcs, int64_t m, int64_t n);
+
+// ---- one-sided block Jacobi SVD (svd.hip): behind tn_svd_trunc, tn_svdvals* and the chain driver -----------------------------------
+// C is k x n (element strides crs, ccs).  U: k x keep (urs, ucs), Vt: keep x n (vrs, vcs), S: keep values (all DEVICE); keep <= Dmax
+// values above tol x the largest.  keep_out / discarded_out / sweeps_out / info are HOST pointers (info: 0 converged, 1 sweep cap).
+int svd_trunc(hipStream_t st, const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, int64_t Dmax, double tol, double* U,
+              int64_t urs, int64_t ucs, double* S, double* Vt, int64_t vrs, int64_t vcs, int64_t* keep_out, double* discarded_out,
+              int* sweeps_out, int* info, void* ws, int64_t ws_bytes);
+// singular values only, sorted descending, min(k, n) of them (deflated ones reported as 0) into hostS (HOST)
+int svd_vals(hipStream_t st, const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* hostS, int* sweeps_out, int* info,
+             void* ws, int64_t ws_bytes);
+int64_t svd_ws_bytes(int64_t k, int64_t n, int vectors);
+// both dimensions <= 64, no read-back: out (DEVICE, 66 doubles) = 64 values descending (zero padded), executed sweeps, convergence flag
+int svd_vals_small_async(hipStream_t st, const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* out);
+// ... `batch` of them in one launch: desc (DEVICE, 5 int64 per item: address, vector stride, element stride, vectors <= length, length)
+int svd_vals_small_batched(hipStream_t st, const int64_t* desc, int64_t batch, double* out);
+
+// ---- strided-batch forms (batch.hip): item i at base + i * bs*, results as for the single calls ------------------------------------
+// side / nside: up to 8 streams the items are spread over (forked from and joined back into st); ws: batch x qr_ws_bytes, 256-aligned
+int qr_batched(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R,
+               int64_t rrs, int64_t rcs, int nb, double rank_tol, int64_t* keff_host, int64_t batch, int64_t bsA, int64_t bsQ, int64_t bsR,
+               void* ws, int64_t ws_bytes, void* const* side, int nside);
+// the items share ws and run one after the other (each reads its rank / convergence back); host outputs are arrays of `batch`
+int svd_trunc_batched(hipStream_t st, const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, int64_t Dmax, double tol, double* U,
+                      int64_t urs, int64_t ucs, double* S, double* Vt, int64_t vrs, int64_t vcs, int64_t* keep_host, double* discarded_host,
+                      int* sweeps_host, int* info_host, int64_t batch, int64_t bsC, int64_t bsU, int64_t bsS, int64_t bsV, void* ws,
+                      int64_t ws_bytes);
+int svd_vals_batched(hipStream_t st, const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* S_host, int* sweeps_host,
+                     int* info_host, int64_t batch, int64_t bsC, void* ws, int64_t ws_bytes);
+
+// ---- absorption of an MPO site into an MPS site (absorb.hip), K1 ---------------------------------------------------------------
+// out (Dl ba, pnew, Dr bb) = sum_s A (Dl, pold, Dr) W (ba, po, bb, pi); hconj: contracts po (pnew = pi), else pi (pnew = po); strided batch
+int absorb(hipStream_t st, const double* A, const double* W, double* out, int64_t Dl, int64_t pold, int64_t Dr, int64_t ba, int64_t po,
+           int64_t bb, int64_t pi, int hconj, int64_t batch, int64_t bsA, int64_t bsW, int64_t bsO);
+
+// ---- power-of-two normalisation and elementwise scaling (misc.hip) ---------------------------------------------------------------
+// out2 (DEVICE) = [nf, 1 / nf] with nf = 2^floor(log2(max|x|)); slot8: 8 bytes of device scratch
+int nfactor(hipStream_t st, const double* x, int64_t n, double* out2, void* slot8);
+// x /= nfactor(x), out2 as above; scratch: 8 KiB of device memory always suffice (unused for n <= 32768)
+int normalize_pow2(hipStream_t st, double* x, int64_t n, double* out2, void* scratch, int64_t scratch_bytes);
+int scale_by(hipStream_t st, double* x, int64_t n, const double* scalar_dev);                                    // x *= scalar_dev[0]
+int scale_phys(hipStream_t st, double* A, int64_t Dl, int64_t p, int64_t Dr, const double* diag, int inv);       // A[dl, s, dr] *= diag[s] (inv: /=)
+
+// ---- kernels of the branch-and-bound search (beam.hip, env.hip, peps.hip) ------------------------------------------------------
+// conditional probabilities of the q states of the next cluster for nb branches (tnac4o.py:430-453): P (nb x q), minP (nb),
+// log2p_out (may be null) = log2 P + parent_log2p
+int calc_pn(hipStream_t st, const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+            const int32_t* suf, const int32_t* lidx, const int32_t* uidx, int64_t nb, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr,
+            int64_t br, double* P, double* minP, const double* parent_log2p, double* log2p_out);
+// merges the branches of each of ng groups (starts: ng + 1 offsets) that lie within min_dEng of the group's lowest energy
+int merge_groups(hipStream_t st, const double* E, const double* lp, const int64_t* deg, const int64_t* pos, const int64_t* starts, int64_t ng,
+                 double min_dEng, int64_t* rep_pos, int64_t* degn, double* lpn);
+int nfactor_batched(hipStream_t st, double* x, int64_t batch, int64_t len);          // every row of x (batch x len) /= its own nfactor
+// right / left environments of nk branch keys from those of their parents, each normalised by its power-of-two factor
+int env_rr_batched(hipStream_t st, const double* A, const double* RRprev, const double* W, const int32_t* parent, const int32_t* uidx, int64_t nk,
+                   int64_t Dl, int64_t p, int64_t Dr, int64_t bl, int64_t br, int64_t pu, double* out);
+int env_rl_batched(hipStream_t st, const double* T1, const int32_t* par, const int32_t* didx, int64_t nk, int64_t p, int64_t Dr, double* out);
+// diagonal scaling that balances the n x n matrix A (scale_out: n factors, clamped to [1 / max_scale, max_scale] when max_scale > 0)
+int balance(hipStream_t st, const double* A, int64_t rs, int64_t cs, int64_t n, double max_scale, double* scale_out, int* iters_out);
+// F (q, nl, nu): Boltzmann factor of a cluster with its left / upper couplings;  W (nl, pd, br, nu): the MPO site built from it
+int peps_factor(hipStream_t st, const double* Es, const double* E1, const double* E4, const double* Xu, const double* Xl, const double* Xr,
+                const double* Xd, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nl, int64_t nu, double* F);
+int mpo_from_factor(hipStream_t st, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nl, int64_t nu, int64_t pd,
+                    int64_t br, double* W);
+
+// ---- site steps of the boundary-MPS sweeps (site.hip); layouts and formulas at the definitions ----------------------------------
+// attach (C != NULL) + QR + normalisation of one site.  side 0: Q (m x k), R (k x n) row-major; side 1: Q^T, R^T.  keff_host,
+// normalised_host, dropped2_host, pivot_perm_host: HOST; nf_out2: DEVICE [nf, 1 / nf] (may be null: no normalisation)
+int64_t site_qr_ws_bytes(int side, int64_t Dl, int64_t p, int64_t Dr, int64_t kc, int attach);
+int site_qr(hipStream_t st, int side, double* A, int64_t Dl, int64_t p, int64_t Dr, const double* C, int64_t kc, double* Q, double* R,
+            double rank_tol, int64_t* keff_host, double* nf_out2, int* normalised_host, void* ws, int64_t ws_bytes, double* dropped2_host,
+            int frob_exit, int64_t* pivot_perm_host);
+// out (c, s, c2) = RL (c x a) . A (a, s, a2) . RR (a2 x c2)
+int64_t rar_ws_bytes(int64_t c, int64_t a, int64_t s, int64_t a2, int64_t c2);
+int rar(hipStream_t st, const double* RL, const double* A, const double* RR, int64_t c, int64_t a, int64_t s, int64_t a2, int64_t c2, double* out,
+        void* ws, int64_t ws_bytes);
+// mixed environment of A (a, s, a2) and Ac (c, s, c2).  side 0: out (c2 x a2) from R (c x a); side 1: out (a x c) from R (a2 x c2)
+int64_t env_mix_ws_bytes(int side, int64_t a, int64_t s, int64_t a2, int64_t c, int64_t c2);
+int env_mix(hipStream_t st, int side, const double* R, const double* A, const double* Ac, int64_t a, int64_t s, int64_t a2, int64_t c, int64_t c2,
+            double* out, void* ws, int64_t ws_bytes);
+// projectors of a truncation: Al_new (ml x keep) = Al (ml x k0) U, Ar_new (keep x nr) = Vt Ar (k1 x nr), Cdiag = diag(S)
+int64_t apply_truncation_ws_bytes(int64_t ml, int64_t k0, int64_t keep, int64_t k1, int64_t nr);
+int apply_truncation(hipStream_t st, const double* Al, int64_t ml, int64_t k0, const double* U, int64_t urs, int64_t ucs, int64_t keep,
+                     const double* Vt, int64_t vrs, int64_t vcs, const double* Ar, int64_t k1, int64_t nr, const double* S, double* Al_new,
+                     double* Ar_new, double* Cdiag, void* ws, int64_t ws_bytes);
+// bond weights from the Gram matrix G (n x n): d2 (n) = floored diagonal, stats (65) = 64 partial sums of ||K||_F^2 and max G_cc
+int gram_weights(hipStream_t st, const double* G, int64_t n, double floor_rel, double* d2, double* stats);
+int rows_norm2(hipStream_t st, const double* A, int64_t rows, int64_t cols, double* out);                       // out[r] = sum_c A[r, c]^2
+// out[j, :] = sqrt(w2[perm[j]]) A[perm[j], :];  inverse: out[perm[j], :] = A[j, :] / sqrt(w2[perm[j]])
+int gather_scale_rows(hipStream_t st, const double* A, int64_t rows, int64_t cols, const int64_t* perm, const double* w2, double* out, int inverse);
+// drops the bond indices of a centre matrix C (k <= 256) that carry nothing, from C and the neighbouring site Q; *k_out (HOST) = kept
+// indices, nothing is written when none is dropped.  ws: k doubles.  One read-back.
+int bond_deflate(hipStream_t st, int side, const double* C, int64_t k, int64_t n, const double* Q, int64_t m, double* C_out, double* Q_out,
+                 int64_t* k_out, double* dropped2_rel_out, void* ws, int64_t ws_bytes);
+
+// ---- the two small reductions of the weighted first pass (chain.hip), exported as tn_weighted_sum / tn_argsort_desc ------------------
+int weighted_sum(hipStream_t st, const double* a, const double* b, int64_t n, double* w, double* sum);     // w = a * b, sum[0] = sum_i w[i] in a fixed order
+int argsort_desc(hipStream_t st, const double* w, int64_t n, int64_t* perm);                               // stable descending argsort (NaN first)
 
 }  // namespace tn

@@ -13,17 +13,11 @@
 namespace tn {
 
 // TN_PANEL_FUSED=0 keeps the six-launch chain for every panel (A/B measurements, cross-checks); read per call: the tests switch it
-static bool cq_fused_enabled() {
-    const char* e = getenv("TN_PANEL_FUSED");
-    return !(e && e[0] == '0');
-}
+static bool cq_fused_enabled() { return env_flag_on("TN_PANEL_FUSED"); }
 
-unsigned panel_spin_limit() {
-    const char* e = getenv("TN_PANEL_SPIN_LIMIT");
-    return e ? (unsigned)strtoul(e, nullptr, 10) : CQ_SPIN_LIMIT;
-}
+unsigned panel_spin_limit() { return (unsigned)env_i64("TN_PANEL_SPIN_LIMIT", CQ_SPIN_LIMIT); }
 int panel_maxpass() {
-    static const int maxpass = [] { const char* e = getenv("TN_PANEL_MAXPASS"); const int v = e ? atoi(e) : CQ_MAXPASS; return v >= 1 && v <= CQ_MAXPASS ? v : CQ_MAXPASS; }();
+    static const int maxpass = [] { const int v = env_int("TN_PANEL_MAXPASS", CQ_MAXPASS); return v >= 1 && v <= CQ_MAXPASS ? v : CQ_MAXPASS; }();
     return maxpass;
 }
 
@@ -84,9 +78,9 @@ static FusedBudget fused_budget() {
     if (!b.ready) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
-        if (const char* e = getenv("TN_PANEL_CU_BUDGET")) { const int v = atoi(e); if (v >= 0 && v < cus) cus = v; }
-        int q = 4;
-        if (const char* e = getenv("GPU_MAX_HW_QUEUES")) { const int v = atoi(e); if (v >= 1) q = v; }
+        const int budget = env_int("TN_PANEL_CU_BUDGET", -1);
+        if (budget >= 0 && budget < cus) cus = budget;
+        const int hwq = env_int("GPU_MAX_HW_QUEUES", 4), q = hwq >= 1 ? hwq : 4;
         b.cus = cus; b.queues = q;
         b.maxblk = cus / q < CQ_FUSED_MAXBLK ? cus / q : CQ_FUSED_MAXBLK;
         b.ready = true;
@@ -127,10 +121,7 @@ struct CqBigTrack {
 };
 static CqBigTrack cq_big;
 static std::mutex cq_big_mu;
-static bool cq_big_enabled() {                                      // read per call: the tests switch it
-    const char* e = getenv("TN_PANEL_FUSED_BIG");
-    return !(e && e[0] == '0');
-}
+static bool cq_big_enabled() { return env_flag_on("TN_PANEL_FUSED_BIG"); }      // read per call: the tests switch it
 // call with cq_big_mu held
 static bool cq_big_admit(int slot, int nslots) {
     if (slot >= CHOLQR_SLOTS) return false;                        // streams without a slot of their own are not tracked

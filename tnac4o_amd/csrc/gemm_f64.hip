@@ -271,7 +271,6 @@ static void launch_tile(hipStream_t st, const GemmP& g, dim3 grid, bool ak, bool
 // measured slower: it pulls all the partials of a tile through one CU, 22 us against 12 us for the two launches at 64 x 64 x 1024).
 // Larger products are bound by MFMA throughput: big tiles, K split only to fill the chip, chunks of at least 128.
 struct GemmPlan { int bm, bn, s; };
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static GemmPlan plan_gemm(int64_t M, int64_t N, int64_t K, int64_t batch) {
     static const int64_t small_work = (int64_t)1 << env_int("TN_GEMM_SMALLWORK_LOG2", 30);
     // small products: 128 x 128 tiles from this many workgroups on.  Round 5: never (was 128) -- the small products with hundreds of big
@@ -334,7 +333,7 @@ struct GemmTrace {
     bool on;
     std::mutex mu;
     std::map<std::tuple<int64_t, int64_t, int64_t, int64_t, int, int, int>, ShapeStat> tab;
-    GemmTrace() { const char* e = getenv("TN_GEMM_TRACE"); on = e && e[0] == '1'; }
+    GemmTrace() : on(env_flag_set("TN_GEMM_TRACE")) {}
     ~GemmTrace() {
         if (!on || tab.empty()) return;
         std::vector<std::pair<double, std::tuple<int64_t, int64_t, int64_t, int64_t, int, int, int>>> v;
@@ -404,7 +403,7 @@ static int gemm_ex_impl(hipStream_t st, int64_t M, int64_t N, int64_t K, double 
     // 16 separate 32-byte pieces per instruction there.  The transposed product C^T = B^T A^T is the same arithmetic in the same
     // order (element by element: the same K sequence, the same splits) with C^T row-major -- full 128-byte segments.  Not for the
     // block-pair indirection / raw partials of the Jacobi SVD, whose index maps and partial layout are tied to the operand roles.
-    static const bool swap_on = [] { const char* e = getenv("TN_GEMM_SWAP"); return !(e && e[0] == '0'); }();
+    static const bool swap_on = env_flag_on("TN_GEMM_SWAP");
     if (swap_on && rsc == 1 && csc != 1 && N > 1 && !(x && (x->pairs || x->raw_partials)))          // (skip flags are per batch item: they follow)
         return gemm_ex_impl(st, N, M, K, alpha, B, csb, rsb, A, csa, rsa, beta, C, csc, rsc, batch, bsb, bsa, bsc, ws, ws_bytes, x);
     GemmP g;

@@ -31,8 +31,6 @@
 
 namespace tn {
 
-int normalize_pow2(hipStream_t, double*, int64_t, double*, void*, int64_t);
-
 static inline int64_t up256m(int64_t b) { return align_up(b, 256); }
 constexpr int64_t NF_SCRATCH = 8192 + 256;          // normalize_pow2 scratch + the [nf, 1/nf] pair
 

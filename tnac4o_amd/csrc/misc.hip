@@ -1,5 +1,7 @@
 // K6 and small elementwise helpers: power-of-two normalisation factor (reference mps.py:76-85), scaling by its
 // inverse (mps.py:782, 797; tnac4o.py:533, 1781), diagonal operator on the physical leg (mps.py:361-366).
+#include <vector>
+
 #include "common.h"
 
 namespace tn {
@@ -9,9 +11,9 @@ struct PinnedSlot {
     size_t cap = 0;
     ~PinnedSlot() { if (p) (void)hipHostFree(p); }
 };
-void* pinned_host(size_t bytes, int slot) {
-    thread_local PinnedSlot slots[8];
-    if (slot < 0 || slot > 7) return nullptr;
+void* pinned_host(size_t bytes, PinSlot slot) {
+    thread_local PinnedSlot slots[PIN_NSLOTS];
+    if (slot < 0 || slot >= PIN_NSLOTS) return nullptr;
     PinnedSlot& s = slots[slot];
     if (s.cap < bytes) {
         if (s.p) { (void)hipHostFree(s.p); s.p = nullptr; s.cap = 0; }
@@ -22,6 +24,40 @@ void* pinned_host(size_t bytes, int slot) {
     return s.p;
 }
 
+static int copy_fail(hipError_t e, const char* op, const char* what) {
+    set_error("%s %s: %s", op, what, hipGetErrorString(e));
+    return (int)e > 0 ? (int)e : 1;
+}
+static int read_back_to(hipStream_t st, void* target, const void* dev, size_t bytes, const char* what) {
+    hipError_t e;
+    if ((e = hipMemcpyAsync(target, dev, bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return copy_fail(e, "memcpy", what);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return copy_fail(e, "sync", what);
+    return 0;
+}
+int read_back(hipStream_t st, void* host, const void* dev, size_t bytes, PinSlot slot, const char* what) {
+    void* stage = pinned_host(bytes, slot);
+    const int rc = read_back_to(st, stage ? stage : host, dev, bytes, what);
+    if (rc == 0 && stage) memcpy(host, stage, bytes);
+    return rc;
+}
+int read_back_staged(hipStream_t st, void** data, const void* dev, size_t bytes, PinSlot slot, const char* what) {
+    void* p = pinned_host(bytes, slot);
+    if (!p) {
+        thread_local std::vector<char> pageable;
+        pageable.resize(bytes);
+        p = pageable.data();
+    }
+    *data = p;
+    return read_back_to(st, p, dev, bytes, what);
+}
+int upload(hipStream_t st, void* dev, const void* host, size_t bytes, PinSlot slot, const char* what) {
+    void* stage = pinned_host(bytes, slot);
+    if (stage) memcpy(stage, host, bytes);
+    hipError_t e;
+    if ((e = hipMemcpyAsync(dev, stage ? stage : host, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return copy_fail(e, "memcpy", what);
+    if (!stage && (e = hipStreamSynchronize(st)) != hipSuccess) return copy_fail(e, "sync", what);
+    return 0;
+}
 
 // max |x| via atomicMax on the bit pattern (non-negative doubles order like unsigned integers)
 __global__ __launch_bounds__(256) void absmax_bits_kernel(const double* __restrict__ x, int64_t n,

@@ -112,6 +112,21 @@ void prof_note(int fam, double calls, double flops, double bytes) {
     f.bytes += bytes;
 }
 
+// (the two SVD forms: SURVEY.md 8(d) with m = max(k, n), n = min(k, n))
+void prof_note_qr(int64_t m, int64_t n, int64_t batch) {
+    const double dm = (double)m, dn = (double)(n < m ? n : m), b = (double)batch;
+    prof_note(PROF_QR_NOMINAL, b, b * (4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn), b * 8.0 * (2.0 * dm * dn + dn * dn));
+}
+void prof_note_svd(int64_t k, int64_t n, int sweeps) {
+    const double dm = (double)(k > n ? k : n), dn = (double)(k > n ? n : k);
+    prof_note(PROF_SVD_NOMINAL, 1, 14.0 * dm * dn * dn + 8.0 * dn * dn * dn, 8.0 * (2.0 * dm * dn + dn * dn + dn));
+    prof_note(PROF_SVD_STREAM, sweeps, 0.0, (double)sweeps * (dn - 1.0) * 16.0 * dn * (dm + dn));
+}
+void prof_note_svdvals(int64_t k, int64_t n) {
+    const double dm = (double)(k > n ? k : n), dn = (double)(k > n ? n : k);
+    prof_note(PROF_SVDVALS_NOMINAL, 1, 4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn, 8.0 * (dm * dn + dn));
+}
+
 int prof_phase(int phase) {
     if (g_mask == 0) return PH_OTHER;      // profiling off: no thread-local traffic
     ThreadProf& t = mine();

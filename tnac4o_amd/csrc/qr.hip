@@ -697,7 +697,7 @@ __global__ __launch_bounds__(256) void tiny_qr_kernel(const double* __restrict__
 
 // ------------------------------------------------------------------------------------------ driver
 // TN_DEBUG=1: synchronise after each stage and report the first non-finite intermediate (diagnostics only)
-static bool dbg_on() { static int v = -1; if (v < 0) { const char* e = getenv("TN_DEBUG"); v = (e && e[0] == '1') ? 1 : 0; } return v == 1; }
+static bool dbg_on() { static const bool on = env_flag_set("TN_DEBUG"); return on; }
 static void dbg_check(hipStream_t st, const double* p, int64_t rs, int64_t cs, int64_t m, int64_t n, const char* what, int panel, int it) {
     if (!dbg_on()) return;
     std::vector<double> h((size_t)(m * n));
@@ -1190,7 +1190,7 @@ struct QrTrace {
     std::map<std::tuple<int64_t, int64_t, int, int, int>, double> ranks;
     double cat_ms[8] = {0}, cat_rank[8] = {0}, cat_m[8] = {0};
     long cat_calls[8] = {0};
-    QrTrace() { const char* e = getenv("TN_QR_TRACE"); on = e && e[0] == '1'; }
+    QrTrace() : on(env_flag_set("TN_QR_TRACE")) {}
     ~QrTrace() {
         if (!on || tab.empty()) return;
         std::vector<std::pair<double, std::tuple<int64_t, int64_t, int, int, int>>> v;
@@ -1203,7 +1203,7 @@ struct QrTrace {
         for (int c = 0; c < 7; ++c)
             fprintf(stderr, "  [%s] %ld calls, %.1f ms, mean rows %.0f, mean accepted rank %.1f\n", cn[c], cat_calls[c], cat_ms[c],
                     cat_calls[c] ? cat_m[c] / cat_calls[c] : 0.0, cat_calls[c] ? cat_rank[c] / cat_calls[c] : 0.0);
-        static const size_t rows = [] { const char* e = getenv("TN_QR_TRACE_ROWS"); return e ? (size_t)atol(e) : (size_t)60; }();
+        static const size_t rows = (size_t)env_i64("TN_QR_TRACE_ROWS", 60);
         for (size_t i = 0; i < v.size() && i < rows; ++i) {
             auto& k = v[i].second;
             auto& st = tab[k];
@@ -1289,8 +1289,7 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
     TN_CHECK_ARG(ws_bytes >= qr_ws_bytes(m, n, nb), "workspace too small");
     int64_t k = m < n ? m : n;
     {   // tiny matrices: the whole factorisation in one workgroup (TN_QR_TINY=0: the blocked path; read per call: the tests switch it)
-        const char* e_tiny = getenv("TN_QR_TINY");
-        const bool tiny_on = !(e_tiny && e_tiny[0] == '0');
+        const bool tiny_on = env_flag_on("TN_QR_TINY");
         if (tiny_on && nb == 32 && pivot_perm_host == nullptr && m * n <= 4096 && k <= 32) {
             TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(tiny_qr_kernel, dim3(1), dim3(256), 0, st, (const double*)A, rs, cs, (int)m, (int)n, Q, qrs, qcs,
                                R, rrs, rcs));
@@ -1338,21 +1337,19 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
     if (nb == 32 && (rc = cholqr_begin(st, w.panel_ws, &w.cq_state))) return rc;
     int fbase = 0;                            // arrivals booked by the single-launch panel steps of this call (cholqr.hip)
     {   // two-level blocking for the plain factorisation of matrices with several outer blocks (TN_QR_NBO = 0 disables it)
-        const char* e_nbo = getenv("TN_QR_NBO");                      // read per call: the tests switch it
-        const int v_nbo = e_nbo ? atoi(e_nbo) : 256, nbo = (v_nbo == 128 || v_nbo == 256) ? v_nbo : 0;
+        const int v_nbo = env_int("TN_QR_NBO", 256), nbo = (v_nbo == 128 || v_nbo == 256) ? v_nbo : 0;      // read per call: the tests switch it
         if (nbo > 0 && nb == 32 && !(rank_tol > 0.0 && keff_host != nullptr) && k >= 2 * nbo && m >= 4 * nbo) {
             if (keff_host) *keff_host = k;
             return qr_two_level(st, Am, m, n, k, Ym, w, nbo, rs, cs, yrs, ycs, wrs, wcs, Q, qrs, qcs, R, rrs, rcs, &fbase);
         }
     }
-    hipError_t he;
     // device-side panel pivoting (see pivot_select_kernel): the host runs one panel ahead of the verdicts it reads back
-    const bool piv_dev_on = [] { const char* e = getenv("TN_PIVOT_DEVICE"); return !(e && e[0] == '0'); }();      // (read per call: the tests switch it)
+    const bool piv_dev_on = env_flag_on("TN_PIVOT_DEVICE");      // (read per call: the tests switch it)
     const bool piv_dev = pivot && piv_dev_on && n <= PIV_MAXN;
     PivState* pst = (PivState*)w.piv;
     int* pperm = (int*)(w.piv + 1024);
     const int* active = piv_dev ? &pst->h.active : nullptr;
-    PivMail* ring = piv_dev ? (PivMail*)pinned_host(4 * sizeof(PivMail), 7) : nullptr;
+    PivMail* ring = piv_dev ? (PivMail*)pinned_host(4 * sizeof(PivMail), PIN_SHARED) : nullptr;
     if (piv_dev && !ring) { set_error("tn_qr: no page-locked memory for the pivoting verdicts"); return 1; }
     if (piv_dev) for (int i = 0; i < 4; ++i) __atomic_store_n(&ring[i].word, 0ull, __ATOMIC_RELAXED);       // (the slot is shared with other read-backs of this thread: no stale word may look like a stamp)
     thread_local unsigned piv_seq = 0;                        // stamps are unique per host thread (the ring is the thread's own; wrap-around after 2^32 panels is harmless: four entries)
@@ -1409,11 +1406,8 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
         } else if (pivot) {
             TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(colnorm2_kernel, dim3((unsigned)ntr), dim3(256), 0, st, Ap.p, rs, cs, mp, ntr, w.cn));
             TN_CHECK_LAUNCH("colnorm2_kernel");
-            std::vector<double> hcn_pageable;
-            double* hcn = (double*)pinned_host((size_t)ntr * 8, 0);
-            if (!hcn) { hcn_pageable.resize((size_t)ntr); hcn = hcn_pageable.data(); }
-            if ((he = hipMemcpyAsync(hcn, w.cn, (size_t)ntr * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(he, "memcpy norms");
-            if ((he = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(he, "sync norms");
+            double* hcn = nullptr;
+            if ((rc = read_back_staged(st, (void**)&hcn, w.cn, (size_t)ntr * 8, PIN_QR, "norms"))) return rc;
             double fro2 = 0.0;
             for (int64_t j = 0; j < ntr; ++j) fro2 += hcn[j];
             if (p == 0) scale2 = fro2;
@@ -1495,13 +1489,8 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
             TN_CHECK_LAUNCH("colnorm2_kernel");
             // one read-back: the trailing norms, and (first check only) the input norms stored in front of them
             const size_t nread = (size_t)(scale2 < 0.0 ? n + nt : nt);
-            std::vector<double> hcn_pageable;
-            double* hcn = (double*)pinned_host(nread * 8, 0);
-            if (!hcn) { hcn_pageable.resize(nread); hcn = hcn_pageable.data(); }
-            hipError_t e;
-            if ((e = hipMemcpyAsync(hcn, scale2 < 0.0 ? w.cn : w.cn + n, nread * 8, hipMemcpyDeviceToHost, st)) != hipSuccess)
-                return hip_fail(e, "memcpy norms");
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync norms");
+            double* hcn = nullptr;
+            if ((rc = read_back_staged(st, (void**)&hcn, scale2 < 0.0 ? w.cn : w.cn + n, nread * 8, PIN_QR, "norms"))) return rc;
             const double* tr2 = hcn;
             // measure of "what is left" against the input: largest column norm (default) or, frob_exit, the Frobenius norm
             if (scale2 < 0.0) {
@@ -1530,11 +1519,8 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
             if ((rc = piv_verdict(P - 1, stop))) return rc;
         }
         // state block (1024 bytes, for the dropped norm) and permutation are neighbours in the workspace: one copy
-        std::vector<int> hp_pageable;
-        int* hp = (int*)pinned_host(1024 + (size_t)n * 4, 0);
-        if (!hp) { hp_pageable.resize(256 + (size_t)n); hp = hp_pageable.data(); }
-        if ((he = hipMemcpyAsync(hp, w.piv, 1024 + (size_t)n * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(he, "memcpy permutation");
-        if ((he = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(he, "sync permutation");
+        int* hp = nullptr;
+        if ((rc = read_back_staged(st, (void**)&hp, w.piv, 1024 + (size_t)n * 4, PIN_QR, "permutation"))) return rc;
         for (int64_t j = 0; j < n; ++j) pivot_perm_host[j] = hp[256 + j];
         if (((const PivState*)hp)->h.stamp < 0) {
             set_error("tn_qr: the device-side pivot selection of panel %d was not a valid set of columns (TN_PIVOT_DEVICE=0 selects on the host)",
@@ -1569,7 +1555,7 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
     Mat Qm = mat(Q, qrs, qcs);
     // merged reflectors (see apply_merged_T_kernel): from two panels on, unless the small-matrix fold above already took the last one
     // (TN_QR_MERGED_Q=0 keeps the panel-by-panel accumulation; read per call: the tests switch it)
-    const bool merged_q = wform && Q != nullptr && P >= 2 && fold_b == 0 && [] { const char* e = getenv("TN_QR_MERGED_Q"); return !(e && e[0] == '0'); }();
+    const bool merged_q = wform && Q != nullptr && P >= 2 && fold_b == 0 && env_flag_on("TN_QR_MERGED_Q");
     if (merged_q) {
         const int nblk = (int)cdiv(k, QMB);
         TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(zero_above_panels_kernel, dim3(16, (unsigned)nblk), dim3(256), 0, st, w.Y, yrs, ycs, k, nb));

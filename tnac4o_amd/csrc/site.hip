@@ -14,8 +14,6 @@
 
 namespace tn {
 
-int normalize_pow2(hipStream_t, double*, int64_t, double*, void*, int64_t);
-
 static inline int64_t up256(int64_t b) { return align_up(b, 256); }
 
 // ---- attach + QR + nfactor ---------------------------------------------------------------------------------------------
@@ -67,8 +65,7 @@ int site_qr(hipStream_t st, int side, double* A, int64_t Dl, int64_t p, int64_t 
     int nf_done = 0;
     {
         ProfPhase ph(PH_QR);
-        const double dm = (double)d.m, dn = (double)d.k;
-        prof_note(PROF_QR_NOMINAL, 1, 4.0 * dm * dn * dn - 4.0 / 3.0 * dn * dn * dn, 8.0 * (2.0 * dm * dn + dn * dn));
+        prof_note_qr(d.m, d.n, 1);
         if (side == 0)      // M (m x n) row-major; Q (m x k) row-major; R (k x n) row-major
             rc = qr_factor(st, M, d.n, 1, d.m, d.n, Q, d.k, 1, R, d.n, 1, 32, qw, qws, rank_tol, &keff, dropped2_host, frob_exit, pivot_perm_host,
                            nf_out2, &nf_done);
@@ -313,13 +310,8 @@ int bond_deflate(hipStream_t st, int side, const double* C, int64_t k, int64_t n
     else TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(bond_norm2_kernel, dim3((unsigned)k), dim3(256), 0, st, C, 1, k, n, dn));
     TN_CHECK_LAUNCH("bond_norm2_kernel");
     double h[256];
-    {
-        hipError_t e;
-        double* stage = (double*)pinned_host((size_t)k * 8, 2);
-        if ((e = hipMemcpyAsync(stage ? stage : h, dn, (size_t)k * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "memcpy norms");
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync norms");
-        if (stage) memcpy(h, stage, (size_t)k * 8);
-    }
+    const int rcr = read_back(st, h, dn, (size_t)k * 8, PIN_SVD_READ, "norms");
+    if (rcr) return rcr;
     double nmax = 0.0;
     for (int64_t i = 0; i < k; ++i) {
         if (!(h[i] == h[i]) || h[i] > 1.7e308) { set_error("bond_deflate: non-finite centre matrix"); return -2; }

@@ -775,9 +775,9 @@ int eig_small(hipStream_t st, const double* part, int nchunk, int nvec, int ngro
     TN_CHECK_ARG(nvec >= 1 && nvec <= NBMAX, "nvec out of range");
     if (ngroups <= 0) return 0;
     prof_begin(st, PROF_EIG);
-    static const int dbg = [] { const char* e = getenv("TN_EIG_DBG"); return e ? atoi(e) : 0; }();      // timing diagnostics of the third form
+    static const int dbg = env_int("TN_EIG_DBG", 0);      // timing diagnostics of the third form
     // TN_EIG_FAST: largest relative off-diagonal up to which a pair takes the near-diagonal fast path (0 = never; see eig_small3_kernel)
-    static const double fast_thr = [] { const char* e = getenv("TN_EIG_FAST"); return e ? atof(e) : 1e-2; }();
+    static const double fast_thr = env_double("TN_EIG_FAST", 1e-2);
     if (nvec <= 32)
         hipLaunchKernelGGL((eig_small3_kernel<32>), dim3(ngroups), dim3(512), 0, st, part, nchunk, nvec, mode, max_sweeps,
                            dead_thresh, out, dead, nrot, maxoff, relevant2, dbg, 0.0);
@@ -1030,13 +1030,10 @@ __global__ __launch_bounds__(512) void svdl_kernel(SvdlArgs a) {
 // 0: the launch is in the stream (read norms[nvp .. nvp + 2] back: sweeps, converged, workgroups that gave up); 1: not taken (the
 // caller runs the rounds as separate launches); else an error
 int svd_rounds_fused(hipStream_t st, const SvdRoundsJob& j) {
-    {
-        const char* e = getenv("TN_SVD_FUSED");                       // read per call: the tests switch it
-        if (e && e[0] == '0') return 1;
-    }
-    static const int dbg = [] { const char* e = getenv("TN_EIG_DBG"); return e ? atoi(e) : 0; }();
-    static const double fast_thr = [] { const char* e = getenv("TN_EIG_FAST"); return e ? atof(e) : 1e-2; }();
-    static const int eig_naps = [] { const char* e = getenv("TN_SVDJ_NAPS"); return e ? atoi(e) : 2; }();
+    if (!env_flag_on("TN_SVD_FUSED")) return 1;                       // read per call: the tests switch it
+    static const int dbg = env_int("TN_EIG_DBG", 0);
+    static const double fast_thr = env_double("TN_EIG_FAST", 1e-2);
+    static const int eig_naps = env_int("TN_SVDJ_NAPS", 2);
     const int slot = cholqr_stream_slot(st);
     if (slot >= CHOLQR_SLOTS) return 1;
     if (2 * j.w != 64 || j.ng < 1 || j.ng > 32 || j.nr < 1 || j.nvp > 256) return 1;

@@ -716,10 +716,7 @@ bool smallqr_fits(int64_t m, int64_t n) {
 // uses the blocked path), an error code otherwise.
 int smallqr_factor(hipStream_t st, const double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R,
                    int64_t rrs, int64_t rcs, double* nf_out2, void* ws, int64_t ws_bytes) {
-    {
-        const char* e = getenv("TN_QR_SMALL");                        // read per call: the tests switch it
-        if (e && e[0] == '0') return 1;
-    }
+    if (!env_flag_on("TN_QR_SMALL")) return 1;                        // read per call: the tests switch it
     if (!smallqr_fits(m, n) || !Q || !R || ws_bytes < smallqr_ws_bytes(m, n)) return 1;
     const int slot = cholqr_stream_slot(st);
     if (slot >= CHOLQR_SLOTS) return 1;

@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256) void svd_trunc_small_kernel(const double* __re
     }
 }
 
-// Page-locked slot 3 stages the asynchronous uploads of this file (tournament schedule, kept values / order).  An upload is only
+// Page-locked slot PIN_SVD_UPLOAD stages the asynchronous uploads of this file (tournament schedule, kept values / order).  An upload is only
 // guaranteed to have been consumed once ITS stream has passed a synchronisation; a thread that moves on to another stream must not
 // overwrite the slot while the previous stream may still be waiting to read it.
 static int upload_slot_guard(hipStream_t st) {
@@ -494,17 +494,12 @@ int64_t svd_ws_bytes(int64_t k, int64_t n, int vectors) {
 static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, int64_t nv, int64_t L, bool vectors,
                        SvdWs& w, std::vector<double>& hostS, std::vector<int>& hostOrder, int* sweeps_out, int* info,
                        double rel_tol) {
-    hipError_t e;
     int rc;
     TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(vec_norm2_kernel, dim3((unsigned)nv), dim3(256), 0, st, M, vs, es, L, w.norms));
     TN_CHECK_LAUNCH("vec_norm2_kernel");
     std::vector<double> hn(nv);
-    {   // read-backs go through a page-locked staging buffer (see pinned_host): queued right behind the producing kernel
-        double* stage = (double*)pinned_host((size_t)nv * 8, 2);
-        if ((e = hipMemcpyAsync(stage ? stage : hn.data(), w.norms, nv * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "memcpy norms");
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync norms");
-        if (stage) std::memcpy(hn.data(), stage, (size_t)nv * 8);
-    }
+    // read-backs go through a page-locked staging buffer (see read_back): queued right behind the producing kernel
+    if ((rc = read_back(st, hn.data(), w.norms, (size_t)nv * 8, PIN_SVD_READ, "norms"))) return rc;
     double nmax = 0.0;
     for (int64_t i = 0; i < nv; ++i) {
         if (!(hn[i] == hn[i]) || hn[i] > 1.7e308) { set_error("svd: non-finite input"); return -2; }
@@ -516,7 +511,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
         if (hn[i] > thr) live.push_back((int)i);
     if (live.empty()) live.push_back(0);                      // all-zero input: one (zero) vector
     {   // TN_SVD_NORMS=1 (diagnostics): how the input vectors' norms are spread below the largest one
-        static const bool norms_trace = [] { const char* e = getenv("TN_SVD_NORMS"); return e && e[0] == '1'; }();
+        static const bool norms_trace = env_flag_set("TN_SVD_NORMS");
         if (norms_trace) {
             int c[7] = {0, 0, 0, 0, 0, 0, 0};
             const int ex[7] = {-56, -54, -53, -52, -50, -44, -30};
@@ -530,7 +525,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
     // de Rijk ordering: vectors enter the tournament sorted by decreasing norm, so that the blocks are graded (large
     // vectors meet large ones first) -- the classical remedy for the slow start of Jacobi on strongly graded matrices.
     // Only the initial order changes (TN_SVD_SORT=0 keeps the input order for A/B measurements).
-    static const bool sort_live = [] { const char* e = getenv("TN_SVD_SORT"); return !(e && e[0] == '0'); }();
+    static const bool sort_live = env_flag_on("TN_SVD_SORT");
     if (sort_live) std::stable_sort(live.begin(), live.end(), [&](int a, int b) { return hn[a] > hn[b]; });
     const int nvl = (int)live.size();
     const int64_t nvp = align_up(nvl, 2 * SVD_W);
@@ -543,12 +538,8 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
     std::vector<int> hinit(gap + pairs.size(), 0);
     std::copy(live.begin(), live.end(), hinit.begin());
     std::copy(pairs.begin(), pairs.end(), hinit.begin() + gap);
-    {
-        if ((rc = upload_slot_guard(st))) return rc;
-        int* stage = (int*)pinned_host(hinit.size() * 4, 3);
-        if (stage) std::memcpy(stage, hinit.data(), hinit.size() * 4);
-        if ((e = hipMemcpyAsync(w.live, stage ? stage : hinit.data(), hinit.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "memcpy init");
-    }
+    if ((rc = upload_slot_guard(st))) return rc;
+    if ((rc = upload(st, w.live, hinit.data(), hinit.size() * 4, PIN_SVD_UPLOAD, "init"))) return rc;
     const int64_t pitch = L + (vectors ? nv : 0);
     TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(svd_init_kernel, dim3((unsigned)nvp), dim3(256), 0, st, M, vs, es, L, nv, w.live, nvl, w.X,
                        vectors ? w.P : nullptr, pitch));
@@ -559,17 +550,17 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
     std::vector<double> hoff((size_t)nr * ng);
     // a single block pair is diagonalised completely inside eig_small (one round + one verification round);
     // with several pairs two inner sweeps per visit give the fewest total Jacobi steps
-    static const int inner_env = [] { const char* e = getenv("TN_SVD_INNER"); return e ? atoi(e) : 2; }();
+    static const int inner_env = env_int("TN_SVD_INNER", 2);
     // ... in the FIRST outer sweep, where the rotations are large; from the second outer sweep on the off-diagonals a visit meets are
     // small (quadratic convergence), a second inner sweep finds next to nothing and the next outer sweep has to look at the pair again
     // anyway -- measured neutral at L = 2048 (eig_small 481 -> 440 ms per sweep, but 1964 -> 2189 outer sweeps): TN_SVD_INNER_LATER
     // stays at 2
-    static const int inner_later = [] { const char* e = getenv("TN_SVD_INNER_LATER"); return e ? atoi(e) : 2; }();
-    static const bool restrict_conv = [] { const char* e = getenv("TN_SVD_RELEVANT"); return !(e && e[0] == '0'); }();
+    static const int inner_later = env_int("TN_SVD_INNER_LATER", 2);
+    static const bool restrict_conv = env_flag_on("TN_SVD_RELEVANT");
     const double rel4 = 0.25 * rel_tol;
     const double relevant2 = restrict_conv ? nmax * rel4 * rel4 : 0.0;
-    static const double last_tol = [] { const char* e = getenv("TN_SVD_LAST"); return e ? atof(e) : 1e-9; }();
-    static const bool trace = [] { const char* e = getenv("TN_SVD_TRACE"); return e && e[0] == '1'; }();
+    static const double last_tol = env_double("TN_SVD_LAST", 1e-9);
+    static const bool trace = env_flag_set("TN_SVD_TRACE");
     int sweeps = 0;
     bool converged = false;
     std::vector<double> hs(nvp);
@@ -588,10 +579,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
         if (rc != 0 && rc != 1) return rc;
         if (rc == 0) {
             std::vector<double> hb(nvp + 4);
-            double* stage = (double*)pinned_host((size_t)(nvp + 4) * 8, 2);
-            if ((e = hipMemcpyAsync(stage ? stage : hb.data(), w.norms, (nvp + 4) * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "memcpy S");
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync S");
-            if (stage) std::memcpy(hb.data(), stage, (size_t)(nvp + 4) * 8);
+            if ((rc = read_back(st, hb.data(), w.norms, (size_t)(nvp + 4) * 8, PIN_SVD_READ, "S"))) return rc;
             if (hb[nvp + 2] != 0.0) {
                 fprintf(stderr, "[libtnpeps] the one-launch Jacobi rounds of an SVD gave up at a barrier on stream %p (%d workgroup(s); workgroups not "
                         "co-resident: is the device shared? see TN_PANEL_CU_BUDGET); the rounds are redone as separate launches, which this stream "
@@ -630,12 +618,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
                 return rc;
         }
         ++sweeps;
-        {
-            double* stage = (double*)pinned_host(hoff.size() * 8, 2);
-            if ((e = hipMemcpyAsync(stage ? stage : hoff.data(), w.maxoff, hoff.size() * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "memcpy maxoff");
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync sweep");
-            if (stage) std::memcpy(hoff.data(), stage, hoff.size() * 8);
-        }
+        if ((rc = read_back(st, hoff.data(), w.maxoff, hoff.size() * 8, PIN_SVD_READ, "maxoff"))) return rc;
         double worst = 0.0;
         for (double v : hoff) worst = std::max(worst, v);
         if (trace) {
@@ -655,10 +638,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
     if (!fused_done) {
         TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(vec_norm2_kernel, dim3((unsigned)nvp), dim3(256), 0, st, w.X, pitch, 1, L, w.norms));
         TN_CHECK_LAUNCH("vec_norm2_kernel");
-        double* stage = (double*)pinned_host((size_t)nvp * 8, 2);
-        if ((e = hipMemcpyAsync(stage ? stage : hs.data(), w.norms, nvp * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "memcpy S");
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync S");
-        if (stage) std::memcpy(hs.data(), stage, (size_t)nvp * 8);
+        if ((rc = read_back(st, hs.data(), w.norms, (size_t)nvp * 8, PIN_SVD_READ, "S"))) return rc;
     }
     hostOrder.resize(nvp);
     for (int i = 0; i < nvp; ++i) hostOrder[i] = i;
@@ -677,7 +657,7 @@ struct SvdCensus {
     bool on;
     std::mutex mu;
     std::map<std::pair<int64_t, int64_t>, std::tuple<double, long, double>> tab;       // (k, n) -> ms, calls, sweeps
-    SvdCensus() { const char* e = getenv("TN_SVD_CENSUS"); on = e && e[0] == '1'; }
+    SvdCensus() : on(env_flag_set("TN_SVD_CENSUS")) {}
     ~SvdCensus() {
         if (!on || tab.empty()) return;
         std::vector<std::pair<double, std::pair<int64_t, int64_t>>> v;
@@ -730,8 +710,7 @@ static int svd_trunc_impl(hipStream_t st, const double* C, int64_t crs, int64_t 
     const int64_t nv = rows ? k : n, L = rows ? n : k;
     const int64_t vs = rows ? crs : ccs, es = rows ? ccs : crs;
     {   // both dimensions <= 64: the whole truncated SVD in one launch and one read-back (TN_SVD_SMALL=0: the block path; read per call)
-        const char* e_small = getenv("TN_SVD_SMALL");
-        if (k <= 64 && n <= 64 && !(e_small && e_small[0] == '0')) {
+        if (k <= 64 && n <= 64 && env_flag_on("TN_SVD_SMALL")) {
             const double eps = 2.220446049250313e-16;
             const double t = tol > eps ? tol : eps;
             double* res = (double*)ws;
@@ -744,11 +723,8 @@ static int svd_trunc_impl(hipStream_t st, const double* C, int64_t crs, int64_t 
                                    S, Vt, vcs, vrs, U, ucs, urs, res));
             TN_CHECK_LAUNCH("svd_trunc_small_kernel");
             double h[4] = {0.0, 0.0, 0.0, 0.0};
-            double* stage = (double*)pinned_host(sizeof(h), 2);
-            hipError_t e;
-            if ((e = hipMemcpyAsync(stage ? stage : h, res, sizeof(h), hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "memcpy result");
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync result");
-            if (stage) std::memcpy(h, stage, sizeof(h));
+            const int rcr = read_back(st, h, res, sizeof(h), PIN_SVD_READ, "result");
+            if (rcr) return rcr;
             if (!(h[1] == h[1])) { set_error("svd: non-finite input"); return -2; }
             if (keep_out) *keep_out = (int64_t)h[0];
             if (discarded_out) *discarded_out = h[1];
@@ -774,12 +750,10 @@ static int svd_trunc_impl(hipStream_t st, const double* C, int64_t crs, int64_t 
     if (keep_out) *keep_out = keep;
     if (discarded_out) *discarded_out = std::sqrt(d2) / hS[0];
     if (keep == 0) return 0;
-    hipError_t e;
     GatherList gl = {};
     const int byval = keep <= 64 ? 1 : 0;
     double* dS = w.norms;
     const int* dO = (const int*)((const char*)w.norms + (size_t)keep * 8);
-    char* stage = nullptr;
     if (byval) {
         for (int64_t i = 0; i < keep; ++i) { gl.S[i] = hS[(size_t)i]; gl.order[i] = hO[(size_t)i]; }
     } else {
@@ -787,11 +761,8 @@ static int svd_trunc_impl(hipStream_t st, const double* C, int64_t crs, int64_t 
         std::vector<char> hpack((size_t)keep * 12);
         std::memcpy(hpack.data(), hS.data(), (size_t)keep * 8);
         std::memcpy(hpack.data() + (size_t)keep * 8, hO.data(), (size_t)keep * 4);
-        if ((rc = upload_slot_guard(st))) return rc;
-        stage = (char*)pinned_host(hpack.size(), 3);           // (the schedule uploaded from this slot completed several synchronisations ago)
-        if (stage) std::memcpy(stage, hpack.data(), hpack.size());
-        if ((e = hipMemcpyAsync(w.norms, stage ? stage : hpack.data(), hpack.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "memcpy S/order");
-        if (!stage && (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync S/order");      // pageable source: must outlive the copy
+        if ((rc = upload_slot_guard(st))) return rc;              // (the schedule uploaded from this slot completed several synchronisations ago)
+        if ((rc = upload(st, w.norms, hpack.data(), hpack.size(), PIN_SVD_UPLOAD, "S/order"))) return rc;
     }
     // rows: left = U (k x keep), right = Vt.  columns (C^T was factored): left = Vt^T, right = U^T.
     if (rows)
@@ -840,11 +811,8 @@ int svd_vals(hipStream_t st, const double* C, int64_t crs, int64_t ccs, int64_t 
         TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(svd_vals_small_kernel, dim3(1), dim3(256), 0, st, C, vs, es, (int)nv, (int)L, dout));
         TN_CHECK_LAUNCH("svd_vals_small_kernel");
         double h[66];
-        hipError_t e;
-        double* stage = (double*)pinned_host(sizeof(h), 2);
-        if ((e = hipMemcpyAsync(stage ? stage : h, dout, sizeof(h), hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "memcpy S");
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync S");
-        if (stage) std::memcpy(h, stage, sizeof(h));
+        const int rcr = read_back(st, h, dout, sizeof(h), PIN_SVD_READ, "S");
+        if (rcr) return rcr;
         for (int64_t i = 0; i < nv; ++i) {
             if (!(h[i] == h[i]) || h[i] > 1.7e308) { set_error("svd: non-finite input"); return -2; }
             hostS[i] = h[i];
