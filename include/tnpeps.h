@@ -191,6 +191,22 @@ int tn_calc_pn(const double* T1, const double* RR, const double* F, const int32_
                const int32_t* pref, const int32_t* suf, const int32_t* lidx, const int32_t* uidx, int64_t nb,
                int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, double* P, double* minP,
                const double* parent_log2p, double* log2p_out, void* stream);
+/* ---- K8s: one state of the next cell drawn per sample, from the conditional table of the sample's boundary row.  Replaces the
+ * table read-back, cumsum and per-sample np.searchsorted of gibbs_sampling (tnac4o.py:614-622).  Samples with the same boundary row
+ * form a group; one workgroup per group builds the table exactly as tn_calc_pn does (same bits), keeps it in LDS, forms its running
+ * sum there in an order that depends on q alone, and every member finds its state by binary search.
+ *   T1, RR, F, dmap, rmap, q, nl, nu, p, Dr, br   as tn_calc_pn
+ *   pref, suf, lidx, uidx (int32[ng])             the boundary row of every GROUP
+ *   perm (int32), starts (int64[ng + 1])          members of group g: the sample indices perm[starts[g] .. starts[g+1]-1]
+ *   uniforms (double, indexed by sample index)    numbers in [0, 1)
+ * Out, per sample k: child_out[k] (int32) = first s with cum[s] >= uniforms[k] (np.searchsorted, side 'left'), moved forward to the
+ * next s with P[s] > 0 when P[s] = 0, and the last s with P[s] > 0 when uniforms[k] > cum[q-1]; log2p_inout[k] += log2 P[child].
+ * Per group: minP_out[g] as tn_calc_pn's.  Limits (argument error otherwise): tn_calc_pn's, and the table with its running sum in
+ * 150 KiB of LDS: (max(p Dr + Dr br + p br, q) + q) * 8 <= 150 KiB. */
+int tn_sample_pn(const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+                 const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
+                 const double* uniforms, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child_out,
+                 double* log2p_inout, double* minP_out, void* stream);
 /* ---- a12: merge of the branches of a site-step with identical boundary indices (tnac4o.py:481-509).  The candidates arrive sorted by
  * group, in candidate order inside a group: E, log2p, deg, pos (their position in the candidate list), group g = members starts[g] ..
  * starts[g+1]-1 (ngroups + 1 offsets).  Per group: rep_pos_out = position of the FIRST member of minimal energy, deg_out = sum of the
@@ -428,6 +444,24 @@ int tn_beam_search_team(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64
                         int16_t* states_out, double* energy_out, double* log2p_out, int64_t* deg_out, int64_t* nb_host, double* pd_max_host,
                         double* globalmin_host, void* ws, int64_t ws_bytes, void* stream, int rank, int team, tn_beam_exchange_fn exchange,
                         void* exchange_ctx);
+
+/* ---- K8s driver: the sampling walk of gibbs_sampling in C++ (reference tnac4o.py:553-650) ------------------------------------------
+ * tn_gibbs_sample: rows ny = 0 .. Ny-1, sites nx = 0 .. Nx-1 over the cells of tn_beam_search (HOST array), M samples that keep their
+ * slot from start to end (no cut, no merge, no selection), B > every boundary index.  uniforms (DEVICE): Nx*Ny rows of ldu >= M doubles
+ * in [0, 1), row = cell in walk order, column = sample.  Per site-step: T1 = RL . A over the distinct prefixes, the samples grouped by
+ * boundary row, tn_sample_pn on the groups, then states / boundary indices / energies (added up in tn_beam_search's order) of every
+ * sample and the left environments of the new distinct prefixes.  A sample's result depends on its own column of uniforms only.
+ * Results (DEVICE): states_out (M x Nx*Ny int16, lattice order of this rotation), energy_out (M), log2p_out (M) = log2 of the
+ * probability q(x) the configuration was drawn with (the sum of log2 of the conditional probabilities of its cells).
+ * HOST: *globalmin_host smallest conditional-table flag (1 when none is below), *max_groups_host (may be NULL) the largest number of
+ * distinct boundary rows met.  Memory O(M (Nx + Nx*Ny) + distinct rows x environment), never O(M q); the query takes the worst case
+ * (all rows distinct).  Synchronises `stream` twice per site-step (counts) and once per level of right environments.
+ * Limits as tn_beam_search (q <= 32767, Dl * nl <= 2048, p == pd), tn_sample_pn's LDS bound at every cell, M^2 B^2 < 2^63.
+ * Errors: -1 argument, -3 workspace too small; both before any launch. */
+int64_t tn_gibbs_sample_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax, int64_t max_env, int64_t max_t1, int64_t max_w);
+int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const double* uniforms, int64_t ldu,
+                    int16_t* states_out, double* energy_out, double* log2p_out, double* globalmin_host, int64_t* max_groups_host, void* ws,
+                    int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

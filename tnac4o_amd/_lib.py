@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libtnpeps.so')
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['api.hip', 'gemm_f64.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip']
+SOURCES = ['api.hip', 'gemm_f64.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip', 'sampler.hip']
 
 _i64, _f64, _int, _ptr = C.c_int64, C.c_double, C.c_int, C.c_void_p
 
@@ -49,6 +49,7 @@ SIGNATURES = {
     'tn_normalize_pow2': (_int, [_ptr, _i64, _ptr, _ptr, _i64, _ptr]),
     'tn_scale_phys': (_int, [_ptr, _i64, _i64, _i64, _ptr, _int, _ptr]),
     'tn_calc_pn': (_int, [_ptr] * 9 + [_i64] * 7 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    'tn_sample_pn': (_int, [_ptr] * 11 + [_i64, _ptr] + [_i64] * 6 + [_ptr, _ptr, _ptr, _ptr]),
     'tn_merge_groups': (_int, [_ptr] * 5 + [_i64, _f64, _ptr, _ptr, _ptr, _ptr]),
     'tn_nfactor_batched': (_int, [_ptr, _i64, _i64, _ptr]),
     'tn_env_rr_batched': (_int, [_ptr] * 5 + [_i64] * 7 + [_ptr, _ptr]),
@@ -81,6 +82,8 @@ SIGNATURES = {
                        C.POINTER(_f64), _ptr, _i64, _ptr]),
     'tn_beam_search_team': (_int, [_i64, _i64, _ptr, _i64, _int, _f64, _f64, _i64, _ptr, _ptr, _ptr, _ptr, C.POINTER(_i64), C.POINTER(_f64),
                             C.POINTER(_f64), _ptr, _i64, _ptr, _int, _int, _ptr, _ptr]),
+    'tn_gibbs_sample_ws_bytes': (_i64, [_i64] * 7),
+    'tn_gibbs_sample': (_int, [_i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, C.POINTER(_f64), C.POINTER(_i64), _ptr, _i64, _ptr]),
     'tn_env3_ws_bytes': (_i64, [_int] + [_i64] * 8),
     'tn_env3': (_int, [_int] + [_ptr] * 4 + [_i64] * 8 + [_ptr] * 5 + [_i64, _ptr]),
     'tn_cluster_marginal_ws_bytes': (_i64, [_i64] * 5),
@@ -180,13 +183,13 @@ def _stale(L):
 
 # short, non-blocking entry points (see lib())
 SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes', 'tn_absorb', 'tn_nfactor', 'tn_scale_by',
-               'tn_normalize_pow2', 'tn_scale_phys', 'tn_calc_pn', 'tn_nfactor_batched', 'tn_env_rr_batched', 'tn_env_rl_batched',
+               'tn_normalize_pow2', 'tn_scale_phys', 'tn_calc_pn', 'tn_sample_pn', 'tn_nfactor_batched', 'tn_env_rr_batched', 'tn_env_rl_batched',
                'tn_balance', 'tn_merge_groups', 'tn_svdvals_async', 'tn_rar', 'tn_rar_ws_bytes', 'tn_env_mix', 'tn_env_mix_ws_bytes',
                'tn_apply_truncation', 'tn_apply_truncation_ws_bytes', 'tn_site_qr_ws_bytes', 'tn_gram_weights', 'tn_argsort_desc', 'tn_weighted_sum', 'tn_rows_norm2', 'tn_gather_scale_rows', 'tn_peps_factor', 'tn_mpo_from_factor', 'tn_env3', 'tn_env3_ws_bytes',
                'tn_cluster_marginal', 'tn_cluster_marginal_ws_bytes', 'tn_cluster_bond_marginal', 'tn_cluster_bond_marginal_ws_bytes',
                'tn_last_error')
 _lib = None
-ABI_VERSION = 12         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
+ABI_VERSION = 13         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
 
 
 def lib():

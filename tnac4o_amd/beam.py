@@ -270,6 +270,51 @@ def _team_exchange(ws, group):
     return _EXCHANGE_FN(exchange), err
 
 
+class CellTable:
+    """The tn_beam_cell array of a solver whose rhoT is set up (include/tnpeps.h), for the walks of the library (tn_beam_search,
+    tn_gibbs_sample): the PEPS factors on the device, the index and energy tables of tnac4o._update_Eng, the sites of the boundary
+    MPS above every row.  cells: the ctypes array, row-major in the lattice of the current rotation; keep: every tensor a pointer was
+    taken from (the table must outlive the call); qmax / max_env / max_t1 / max_w: the sizes the workspace queries take; misfit: None,
+    or the first limit of the walks that a cell exceeds (text)."""
+
+    def __init__(self, solver):
+        Nx, Ny = solver.Nx, solver.Ny
+        dev = solver.rhoT[0].A[0].device
+        ising = solver.mode == 'Ising'
+        tabs = {(ny, nx): SiteTables(solver, ny, nx, dev) for ny in range(Ny) for nx in range(Nx)}
+        self.cells = (_Cell * (Nx * Ny))()
+        self.keep = [tabs]
+        self.qmax = self.max_env = self.max_t1 = self.max_w = 1
+        self.misfit = None
+        for ny in range(Ny):
+            top = solver.rhoT[ny + 1]
+            for nx in range(Nx):
+                tb = tabs[(ny, nx)]
+                F, dm, rm, pd, br = solver._peps_factor_dev(ny, nx)
+                A = top.A[nx].contiguous()
+                self.keep += [F, dm, rm, A]
+                q, nl, nu = F.shape
+                Dl, p, Dr = A.shape
+                c = self.cells[ny * Nx + nx]
+                c.F, c.dmap, c.rmap = F.data_ptr(), dm.data_ptr(), rm.data_ptr()
+                c.down, c.right, c.Es = tb.down.data_ptr(), tb.right.data_ptr(), tb.Es.data_ptr()
+                c.E1 = tb.E1.data_ptr() if nx > 0 else None
+                c.E4 = tb.E4.data_ptr() if ny > 0 else None
+                c.left_map = tabs[(ny, nx - 1)].right.data_ptr() if (ising and nx > 0) else None
+                c.up_map = tabs[(ny - 1, nx)].down.data_ptr() if (ising and ny > 0) else None
+                c.A = A.data_ptr()
+                c.q, c.nl, c.nu, c.pd, c.br = q, nl, nu, pd, br
+                c.e1cols = tb.E1.shape[1] if tb.E1.dim() == 2 else 1
+                c.e4cols = tb.E4.shape[1] if tb.E4.dim() == 2 else 1
+                c.Dl, c.p, c.Dr = Dl, p, Dr
+                if self.misfit is None and Dl * nl > 2048:
+                    self.misfit = 'Dl x (left PEPS bond) = %d x %d exceeds 2048 at cell (%d, %d)' % (Dl, nl, ny, nx)
+                if self.misfit is None and q > 32767:
+                    self.misfit = '%d states in cell (%d, %d) exceed 32767' % (q, ny, nx)
+                self.qmax, self.max_env = max(self.qmax, q), max(self.max_env, Dl * nl, Dr * br)
+                self.max_t1, self.max_w = max(self.max_t1, p * Dr), max(self.max_w, nl * pd * br * nu)
+
+
 def search_native(solver, M, relative_P_cutoff, min_dEng, beam_group=None):
     """search_ground_state's loop over rows and sites in ONE library call (tn_beam_search, csrc/beamsearch.hip): this function only
     builds the per-cell tables (the PEPS factors on the device, the index and energy tables of tnac4o._update_Eng) and hands over
@@ -282,36 +327,11 @@ def search_native(solver, M, relative_P_cutoff, min_dEng, beam_group=None):
     Nx, Ny = solver.Nx, solver.Ny
     dev = solver.rhoT[0].A[0].device
     maxidx = int(max(np.max(solver.ld), np.max(solver.lr), 2)) - 1
-    ising = solver.mode == 'Ising'
-    tabs = {(ny, nx): SiteTables(solver, ny, nx, dev) for ny in range(Ny) for nx in range(Nx)}
-    cells = (_Cell * (Nx * Ny))()
-    keep = []                                                            # every tensor a pointer was taken from
-    qmax = max_env = max_t1 = max_w = 1
-    for ny in range(Ny):
-        top = solver.rhoT[ny + 1]
-        for nx in range(Nx):
-            tb = tabs[(ny, nx)]
-            F, dm, rm, pd, br = solver._peps_factor_dev(ny, nx)
-            A = top.A[nx].contiguous()
-            keep += [F, dm, rm, A]
-            q, nl, nu = F.shape
-            Dl, p, Dr = A.shape
-            c = cells[ny * Nx + nx]
-            c.F, c.dmap, c.rmap = F.data_ptr(), dm.data_ptr(), rm.data_ptr()
-            c.down, c.right, c.Es = tb.down.data_ptr(), tb.right.data_ptr(), tb.Es.data_ptr()
-            c.E1 = tb.E1.data_ptr() if nx > 0 else None
-            c.E4 = tb.E4.data_ptr() if ny > 0 else None
-            c.left_map = tabs[(ny, nx - 1)].right.data_ptr() if (ising and nx > 0) else None
-            c.up_map = tabs[(ny - 1, nx)].down.data_ptr() if (ising and ny > 0) else None
-            c.A = A.data_ptr()
-            c.q, c.nl, c.nu, c.pd, c.br = q, nl, nu, pd, br
-            c.e1cols = tb.E1.shape[1] if tb.E1.dim() == 2 else 1
-            c.e4cols = tb.E4.shape[1] if tb.E4.dim() == 2 else 1
-            c.Dl, c.p, c.Dr = Dl, p, Dr
-            if Dl * nl > 2048 or q > 32767:
-                return None
-            qmax, max_env = max(qmax, q), max(max_env, Dl * nl, Dr * br)
-            max_t1, max_w = max(max_t1, p * Dr), max(max_w, nl * pd * br * nu)
+    table = CellTable(solver)
+    if table.misfit is not None:
+        return None
+    cells, keep = table.cells, table.keep
+    qmax, max_env, max_t1, max_w = table.qmax, table.max_env, table.max_t1, table.max_w
     L = lib()
     wsb = int(L.tn_beam_search_ws_bytes(Nx, Ny, M, qmax, max_env, max_t1, max_w))
     ws = ops.workspace(wsb, 3)

@@ -8,6 +8,7 @@
 // The negative-probability rule and normalisation of tnac4o.py:1795-1807 are applied in the same kernel.
 #include "common.h"
 #include "devprim.h"
+#include "pn.h"
 
 namespace tn {
 
@@ -19,52 +20,14 @@ __global__ __launch_bounds__(256) void calc_pn_kernel(const double* __restrict__
                                                       int Dr, int br, double* __restrict__ P, double* __restrict__ minP,
                                                       const double* __restrict__ parent_log2p, double* __restrict__ log2p_out) {
     extern __shared__ double lds[];
-    double* sT1 = lds;                  // [p][Dr]
-    double* sRR = sT1 + p * Dr;         // [Dr][br]
-    double* sT2 = sRR + Dr * br;        // [p][br]
-    double* sP = sT2 + p * br;          // [q]
     __shared__ double red[256];
     const int tid = threadIdx.x;
     const int64_t kk = blockIdx.x;
-    const double* t1 = T1 + (int64_t)pref[kk] * p * Dr;
-    const double* rr = RR + (int64_t)suf[kk] * Dr * br;
-    for (int e = tid; e < p * Dr; e += 256) sT1[e] = t1[e];
-    for (int e = tid; e < Dr * br; e += 256) sRR[e] = rr[e];
-    __syncthreads();
-    for (int e = tid; e < p * br; e += 256) {
-        const int d = e / br, r = e % br;
-        double s = 0.0;
-        for (int c = 0; c < Dr; ++c) s += sT1[d * Dr + c] * sRR[c * br + r];
-        sT2[e] = s;
-    }
-    __syncthreads();
-    const int l = lidx[kk], u = uidx[kk];
-    double mn = 1.7e308;
-    for (int s = tid; s < q; s += 256) {
-        const double v = F[((int64_t)s * nl + l) * nu + u] * sT2[dmap[s] * br + rmap[s]];
-        sP[s] = v;
-        mn = fmin(mn, v);
-    }
-    double mPn = block_tree_min(mn, red);
-    if (mPn < 0.0) {                                   // tnac4o.py:1796-1799
-        const double a = fabs(mPn);
-        double cnt = 0.0;
-        for (int s = tid; s < q; s += 256)
-            if (sP[s] < a) { sP[s] = a; cnt += 1.0; }
-        mPn *= block_tree_sum(cnt, red);
-    }
-    double part = 0.0;
-    for (int s = tid; s < q; s += 256) part += sP[s];
-    const double no = block_tree_sum(part, red);
+    double* sP = lds + pn_front_doubles(p, Dr, br);    // [q]
+    const double mPn = pn_table(T1 + (int64_t)pref[kk] * p * Dr, RR + (int64_t)suf[kk] * Dr * br, F, dmap, rmap, lidx[kk], uidx[kk], q, nl, nu, p, Dr,
+                                br, lds, sP, red);
     double* out = P + kk * q;
-    if (no > 0.0) {                                    // tnac4o.py:1800-1803
-        const double inv = 1.0 / no;
-        for (int s = tid; s < q; s += 256) out[s] = sP[s] * inv;
-        mPn *= inv;
-    } else {                                           // all zeros -> uniform, flag -1 (tnac4o.py:1804-1806)
-        for (int s = tid; s < q; s += 256) out[s] = sP[s] + 1.0 / (double)q;
-        mPn = -1.0;
-    }
+    for (int s = tid; s < q; s += 256) out[s] = sP[s];                       // (sP[s] was written by this very thread)
     if (tid == 0) minP[kk] = mPn;
     if (log2p_out) {                                   // tnac4o.py:450-453: log2 of the table plus the parent's log-probability
         const double base = parent_log2p[kk];
@@ -80,7 +43,7 @@ int calc_pn(hipStream_t st, const double* T1, const double* RR, const double* F,
     if (nb <= 0) return 0;
     TN_CHECK_ARG((parent_log2p == nullptr) == (log2p_out == nullptr), "parent_log2p and log2p_out go together");
     TN_CHECK_ARG(q >= 1 && nl >= 1 && nu >= 1 && p >= 1 && Dr >= 1 && br >= 1, "non-positive dimension");
-    const int64_t lds = (p * Dr + Dr * br + p * br + q) * 8;
+    const int64_t lds = (pn_front_doubles(p, Dr, br) + q) * 8;
     TN_CHECK_ARG(lds <= 150 * 1024, "site too large for calc_pn");
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)calc_pn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(calc_pn_kernel, dim3((unsigned)nb), dim3(256), (size_t)lds, st, T1, RR, F, dmap, rmap, pref, suf, lidx,

@@ -10,80 +10,15 @@
 //   * the M survivors = the M largest group log2 p (ties to the smaller group index), kept in group order.
 // Sorting is rocPRIM's radix sort (stable; called directly, no CUDA-compat layer); "unique" = sort, head flags, prefix sum.  Index rows live column-major (a column of
 // boundary indices is contiguous: it is what tn_calc_pn and the keys read).
-#include <string.h>
-
-#include <cstring>
-#include <limits>
-
-#include <rocprim/rocprim.hpp>
-
-#include <algorithm>
-#include <vector>
-
-#include "../../include/tnpeps.h"
-#include "common.h"
+#include "walk.h"
 
 namespace tn {
 
 namespace {
 
-#define BS(call)                   \
-    do {                           \
-        const int rc__ = (call);   \
-        if (rc__) return rc__;     \
-    } while (0)
-#define BSH(call, what)                                   \
-    do {                                                  \
-        const hipError_t e__ = (call);                    \
-        if (e__ != hipSuccess) return hip_fail(e__, what); \
-    } while (0)
-
 constexpr double NEG_INF = -__builtin_huge_val();
 
-// ---- small kernels -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void iota_kernel(int32_t* out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (int32_t)i;
-}
-__global__ __launch_bounds__(256) void fill_i32_kernel(int32_t* out, int64_t n, int32_t v) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = v;
-}
-// key of the suffix vind[:, c:] = (vind[:, c], rank of vind[:, c+1:])
-__global__ __launch_bounds__(256) void suffix_key_kernel(const int32_t* col, const int32_t* suf_prev, int64_t nkeys_prev, int64_t n, int64_t* key) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) key[i] = (int64_t)col[i] * nkeys_prev + suf_prev[i];
-}
-__global__ __launch_bounds__(256) void heads_kernel(const int64_t* skey, int64_t n, int32_t* head) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1 : 0;
-}
-// after the prefix sum of the head flags: inverse (group of every element), first member of every group (stable sort: the head
-// of a group is its smallest original index), offsets of the groups in the sorted order (starts[ng] = n)
-__global__ __launch_bounds__(256) void unique_scatter_kernel(const int32_t* sidx, const int32_t* head, const int32_t* gid, int64_t n, int32_t* inv,
-                                                            int32_t* first, int64_t* starts) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int32_t g = gid[i] - 1;
-    if (inv) inv[sidx[i]] = g;
-    if (head[i]) {
-        if (first) first[g] = sidx[i];
-        if (starts) starts[g] = i;
-    }
-    if (i == n - 1 && starts) starts[g + 1] = n;
-}
-__global__ __launch_bounds__(256) void level_gather_kernel(const int32_t* first, const int32_t* suf_prev, const int32_t* col, int64_t nk, int32_t* parent,
-                                                          int32_t* uidx) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= nk) return;
-    const int32_t f = first[k];
-    parent[k] = suf_prev[f];
-    uidx[k] = col[f];
-}
-__global__ __launch_bounds__(256) void ones_kernel(double* out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = 1.0;
-}
+// ---- small kernels of the search alone (the ones it shares with the sampling walk: walk.h) ----------------------------
 // mask of the kept candidates and the masked copy of the cut ones (tnac4o.py:455-465)
 __global__ __launch_bounds__(256) void cut_flags_kernel(const double* lp, int64_t n, const double* lmax, double log_cut, int32_t* flag, double* rest) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -93,20 +28,9 @@ __global__ __launch_bounds__(256) void cut_flags_kernel(const double* lp, int64_
     flag[i] = keep ? 1 : 0;
     rest[i] = keep ? NEG_INF : lp[i];
 }
-// scal[dst] = max / min (scal[dst], *src)
+// scal[dst] = max (scal[dst], *src)
 __global__ void scalar_max_kernel(double* scal, int dst, const double* src) { scal[dst] = fmax(scal[dst], *src); }
-__global__ void scalar_min_kernel(double* scal, int dst, const double* src) { scal[dst] = fmin(scal[dst], *src); }
 
-struct CellDev {                       // what the expansion of a site-step needs of its cell (device pointers)
-    const int64_t* down;
-    const int64_t* right;
-    const double* Es;
-    const double* E1;
-    const double* E4;
-    const int64_t* left_map;
-    const int64_t* up_map;
-    int64_t q, e1cols, e4cols;
-};
 // one kept candidate = (parent branch, state of the cell): new boundary indices, energy, keys (tnac4o.py:467-479, 1506-1558)
 __global__ __launch_bounds__(256) void expand_kernel(const int32_t* idx, const double* lp, int64_t keep, CellDev c, const int16_t* states, int64_t nsites,
                                                     int64_t pos, int64_t Nx, int has_left, int has_up, const double* Eng, const int32_t* pref,
@@ -117,15 +41,7 @@ __global__ __launch_bounds__(256) void expand_kernel(const int32_t* idx, const d
     const int64_t f = idx[j];
     const int64_t par = f / c.q, ch = f - par * c.q;
     const int64_t dn = c.down[ch], rt = c.right[ch];
-    double dE = 1.0 * c.Es[ch];
-    if (has_left) {
-        const int64_t left = states[par * nsites + pos - 1];
-        dE = dE + c.E1[ch * c.e1cols + (c.left_map ? c.left_map[left] : left)];
-    }
-    if (has_up) {
-        const int64_t up = states[par * nsites + pos - Nx];
-        dE = dE + c.E4[ch * c.e4cols + (c.up_map ? c.up_map[up] : up)];
-    }
+    const double dE = cell_energy(c, ch, states + par * nsites, pos, Nx, has_left, has_up);
     parent_o[j] = (int32_t)par;
     child_o[j] = (int32_t)ch;
     down_o[j] = (int32_t)dn;
@@ -173,37 +89,6 @@ __global__ __launch_bounds__(256) void commit_kernel(const int32_t* sel, const i
         prefc_n[j] = pref[pr];
     }
 }
-__global__ __launch_bounds__(256) void prefix_gather_kernel(const int32_t* nfirst, const int32_t* prefc, const int32_t* col, int64_t npref, int32_t* par,
-                                                           int32_t* didx) {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= npref) return;
-    const int32_t f = nfirst[g];
-    par[g] = prefc[f];
-    didx[g] = col[f];
-}
-// end of a row (tnac4o.py:540-542): the down indices of the row become the up indices of the next, column 0 is the open left edge
-__global__ __launch_bounds__(256) void shift_columns_kernel(const int32_t* vind, int32_t* vind_n, int64_t cap, int64_t ncol, int64_t nb) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nb * ncol) return;
-    const int64_t c = i / nb, b = i % nb;
-    vind_n[c * cap + b] = (c == 0) ? 0 : vind[(c - 1) * cap + b];
-}
-
-struct Bump {
-    char* base = nullptr;
-    int64_t cap = 0, off = 0;
-    template <typename T>
-    T* take(int64_t count) {
-        const int64_t o = align_up(off, 256), bytes = count * (int64_t)sizeof(T);
-        if (o + bytes > cap) return nullptr;
-        off = o + bytes;
-        return (T*)(base + o);
-    }
-};
-#define TAKE(ptr, T, bump, count, what)                                                     \
-    T* ptr = (bump).take<T>(count);                                                         \
-    if (!ptr) { set_error("tn_beam_search: workspace too small (%s)", what); return -3; }
-
 struct Branches {                      // the beam: index rows (column-major), suffix ranks per level, prefix ranks, records
     int32_t* vind;
     int32_t* sufmat;
@@ -214,37 +99,10 @@ struct Branches {                      // the beam: index rows (column-major), s
     int64_t* deg;
 };
 
-struct Search {
-    hipStream_t st;
+struct Search : Walk {
     int64_t Nx, Ny, M, cap, qmax, B;
-    void* cub_tmp = nullptr;
-    size_t cub_bytes = 0;
-    int32_t* iota = nullptr;            // 0 .. cap*qmax-1
     double* scal = nullptr;             // device scalars: [0] pd_max, [1] globalmin, [2] local max, [3] rest max, [4] min of minP
     int32_t* counter = nullptr;         // device: number of selected items
-
-    int read_i32(const int32_t* dev, int32_t& v) { return read_back(st, &v, dev, 4, PIN_SHARED, "beam search: read-back"); }
-    // sorted unique of n int64 keys: number of groups (host), inverse, first members, sorted order, group offsets (any may be NULL)
-    int unique(Bump scratch, const int64_t* key, int64_t n, int64_t& ng, int32_t* inv, int32_t* first, int32_t* sidx_out, int64_t* starts) {
-        TAKE(skey, int64_t, scratch, n, "sorted keys");
-        int32_t* sidx = sidx_out;
-        if (!sidx) { sidx = scratch.take<int32_t>(n); if (!sidx) { set_error("tn_beam_search: workspace too small (sort order)"); return -3; } }
-        TAKE(head, int32_t, scratch, n, "head flags");
-        TAKE(gid, int32_t, scratch, n, "group ids");
-        size_t tb = cub_bytes;
-        BSH(rocprim::radix_sort_pairs(cub_tmp, tb, key, skey, iota, sidx, (int)n, 0, 64, st), "beam search: sort keys");
-        const unsigned nblk = (unsigned)cdiv(n, 256);
-        hipLaunchKernelGGL(heads_kernel, dim3(nblk), dim3(256), 0, st, skey, n, head);
-        TN_CHECK_LAUNCH("heads_kernel");
-        tb = cub_bytes;
-        BSH(rocprim::inclusive_scan(cub_tmp, tb, head, gid, (size_t)n, rocprim::plus<int32_t>(), st), "beam search: scan");
-        hipLaunchKernelGGL(unique_scatter_kernel, dim3(nblk), dim3(256), 0, st, sidx, head, gid, n, inv, first, starts);
-        TN_CHECK_LAUNCH("unique_scatter_kernel");
-        int32_t g = 0;
-        BS(read_i32(gid + (n - 1), g));
-        ng = g;
-        return 0;
-    }
 };
 
 }  // namespace
@@ -308,21 +166,12 @@ int tn_beam_search_team(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64
     hipStream_t st = (hipStream_t)stream;
     const int64_t nsites = Nx * Ny, cap = M, ncol = Nx + 1;
     int64_t qmax = 1, max_env = 1, max_t1 = 1, max_w = 1;
-    for (int64_t i = 0; i < nsites; ++i) {
-        const tn_beam_cell& c = cells[i];
-        TN_CHECK_ARG(c.q >= 1 && c.q <= 32767 && c.nl >= 1 && c.nu >= 1 && c.pd >= 1 && c.br >= 1 && c.Dl >= 1 && c.p >= 1 && c.Dr >= 1, "bad cell");
-        TN_CHECK_ARG(c.p == c.pd, "boundary MPS and PEPS cell disagree on the vertical bond");
-        TN_CHECK_ARG(c.Dl * c.nl <= 2048, "Dl x (left PEPS bond) exceeds 2048 (tn_env_rr): use the Python path");
-        qmax = std::max(qmax, c.q);
-        max_env = std::max(max_env, std::max(c.Dl * c.nl, c.Dr * c.br));
-        max_t1 = std::max(max_t1, c.p * c.Dr);
-        max_w = std::max(max_w, c.nl * c.pd * c.br * c.nu);
-    }
+    WALK_CHECK_CELLS(cells, nsites, qmax, max_env, max_t1, max_w)
     TN_CHECK_ARG(ws_bytes >= tn_beam_search_ws_bytes(Nx, Ny, M, qmax, max_env, max_t1, max_w), "workspace too small");
     TN_CHECK_ARG(M * qmax < ((int64_t)1 << 31), "too many candidates per site-step");
     const int64_t cand = M * qmax;
     Bump bump;
-    bump.base = (char*)ws; bump.cap = ws_bytes;
+    bump.base = (char*)ws; bump.cap = ws_bytes; bump.who = "tn_beam_search";
     Branches gen[2];
     for (int g = 0; g < 2; ++g) {
         gen[g].vind = bump.take<int32_t>(ncol * cap); gen[g].sufmat = bump.take<int32_t>(Nx * cap); gen[g].pref = bump.take<int32_t>(cap);
@@ -373,42 +222,9 @@ int tn_beam_search_team(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64
         Branches& br = gen[cur];
         const tn_beam_cell* row = cells + ny * Nx;
         // ---- right environments of every distinct suffix (tnac4o._setup_RR, tnac4o.py:1768-1784): level j serves site Nx-1-j
-        std::vector<double*> RRs((size_t)Nx, nullptr);
-        std::vector<int64_t> nsuf((size_t)Nx, 1);
-        TAKE(rr0, double, bump, 1, "right edge");
-        hipLaunchKernelGGL(ones_kernel, dim3(1), dim3(256), 0, st, rr0, (int64_t)1);
-        TN_CHECK_LAUNCH("ones_kernel");
-        RRs[0] = rr0;
-        hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, br.sufmat, nb, 0);
-        TN_CHECK_LAUNCH("fill_i32_kernel");
-        int64_t nkeys_prev = 1;
-        for (int64_t nx = Nx - 1; nx >= 1; --nx) {
-            const int64_t lvl = Nx - nx;
-            const tn_beam_cell& c = row[nx];
-            const int32_t* col = br.vind + (nx + 1) * cap;
-            const int32_t* suf_prev = br.sufmat + (lvl - 1) * cap;
-            int32_t* suf_new = br.sufmat + lvl * cap;
-            Bump scratch = bump;                                   // released at the end of the level (a copy: the row keeps bump)
-            TAKE(key, int64_t, scratch, nb, "suffix keys");
-            TAKE(first, int32_t, scratch, nb, "first members");
-            hipLaunchKernelGGL(suffix_key_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, col, suf_prev, nkeys_prev, nb, key);
-            TN_CHECK_LAUNCH("suffix_key_kernel");
-            int64_t nk = 0;
-            BS(S.unique(scratch, key, nb, nk, suf_new, first, nullptr, nullptr));
-            TAKE(parent, int32_t, scratch, nk, "level parents");
-            TAKE(uidx, int32_t, scratch, nk, "level up indices");
-            hipLaunchKernelGGL(level_gather_kernel, dim3((unsigned)cdiv(nk, 256)), dim3(256), 0, st, first, suf_prev, col, nk, parent, uidx);
-            TN_CHECK_LAUNCH("level_gather_kernel");
-            // the level's results live until the end of the row: take them from the row's allocator, past the scratch in use
-            bump.off = scratch.off;
-            TAKE(W, double, bump, c.nl * c.pd * c.br * c.nu, "MPO site");
-            TAKE(RR, double, bump, nk * c.Dl * c.nl, "right environments");
-            BS(mpo_from_factor(st, c.F, c.dmap, c.rmap, c.q, c.nl, c.nu, c.pd, c.br, W));
-            BS(env_rr_batched(st, c.A, RRs[(size_t)lvl - 1], W, parent, uidx, nk, c.Dl, c.p, c.Dr, c.nl, c.br, c.nu, RR));
-            RRs[(size_t)lvl] = RR;
-            nsuf[(size_t)lvl] = nk;
-            nkeys_prev = nk;
-        }
+        std::vector<double*> RRs;
+        std::vector<int64_t> nsuf;
+        BS(S.right_levels(bump, row, Nx, br.vind, br.sufmat, cap, nb, RRs, nsuf));
         hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, br.pref, nb, 0);
         TN_CHECK_LAUNCH("fill_i32_kernel");
         TAKE(RLa, double, bump, cap * max_env, "left environments");
@@ -484,9 +300,7 @@ int tn_beam_search_team(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64
             TAKE(Ec, double, bump, keep, "energies");
             TAKE(pkey, int64_t, bump, keep, "prefix keys");
             TAKE(key, int64_t, bump, keep, "row keys");
-            CellDev cd;
-            cd.down = c.down; cd.right = c.right; cd.Es = c.Es; cd.E1 = c.E1; cd.E4 = c.E4; cd.left_map = c.left_map; cd.up_map = c.up_map;
-            cd.q = q; cd.e1cols = c.e1cols; cd.e4cols = c.e4cols;
+            const CellDev cd = cell_dev(c);
             hipLaunchKernelGGL(expand_kernel, dim3((unsigned)cdiv(keep, 256)), dim3(256), 0, st, idx, LP, keep, cd, b0.states, nsites, pos, Nx, nx > 0 ? 1 : 0,
                                ny > 0 ? 1 : 0, b0.Eng, b0.pref, b0.sufmat + lvl * cap, B, nsuf[(size_t)lvl], parent, child, down, right, vals, Ec, pkey, key);
             TN_CHECK_LAUNCH("expand_kernel");

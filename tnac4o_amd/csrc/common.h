@@ -316,6 +316,12 @@ int scale_phys(hipStream_t st, double* A, int64_t Dl, int64_t p, int64_t Dr, con
 int calc_pn(hipStream_t st, const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
             const int32_t* suf, const int32_t* lidx, const int32_t* uidx, int64_t nb, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr,
             int64_t br, double* P, double* minP, const double* parent_log2p, double* log2p_out);
+// one state of the next cluster drawn per sample from the conditional table of its boundary row, the table kept in LDS (sampler.hip):
+// group g = samples perm[starts[g] .. starts[g+1]-1] sharing (pref, suf, lidx, uidx)[g]; child[k] = the state drawn with uniforms[k],
+// log2p[k] += log2 P[child[k]], minP[g] = the table's flag as calc_pn's
+int sample_pn(hipStream_t st, const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+              const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
+              const double* uniforms, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child, double* log2p, double* minP);
 // merges the branches of each of ng groups (starts: ng + 1 offsets) that lie within min_dEng of the group's lowest energy
 int merge_groups(hipStream_t st, const double* E, const double* lp, const int64_t* deg, const int64_t* pos, const int64_t* starts, int64_t ng,
                  double min_dEng, int64_t* rep_pos, int64_t* degn, double* lpn);

@@ -727,6 +727,32 @@ def calc_pn(T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, parent_log2p=None):
     return P, mP
 
 
+def sample_pn(T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, uniforms, log2p=None):
+    """One state per sample drawn from the conditional table of its boundary row (tn_sample_pn), the table kept in LDS.  pref, suf,
+    lidx, uidx (int32, one entry per GROUP of samples with equal boundary rows); perm (int32) / starts (int64, ngroups + 1 offsets):
+    the sample indices of every group; uniforms (float64, indexed by sample index).  log2p (float64 per sample, updated in place;
+    None: zeros).  Returns (child (int32 per sample), log2p, minP (per group))."""
+    ng = starts.numel() - 1
+    n = uniforms.numel()
+    q, nl, nu = F.shape
+    _, p, Dr = T1.shape
+    br = RR.shape[2]
+    for t in (T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, uniforms):
+        assert t.is_contiguous() and t.is_cuda
+    for t in (pref, suf, lidx, uidx):
+        assert t.dtype == torch.int32 and t.numel() == ng
+    assert perm.dtype == torch.int32 and starts.dtype == torch.int64 and uniforms.dtype == torch.float64
+    if log2p is None:
+        log2p = torch.zeros(n, dtype=torch.float64, device=T1.device)
+    assert log2p.is_contiguous() and log2p.numel() == n and log2p.dtype == torch.float64
+    child = torch.zeros(n, dtype=torch.int32, device=T1.device)
+    mP = torch.empty((ng,), dtype=torch.float64, device=T1.device)
+    check(lib().tn_sample_pn(T1.data_ptr(), RR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), pref.data_ptr(), suf.data_ptr(),
+                             lidx.data_ptr(), uidx.data_ptr(), perm.data_ptr(), starts.data_ptr(), ng, uniforms.data_ptr(), q, nl, nu, p, Dr, br,
+                             child.data_ptr(), log2p.data_ptr(), mP.data_ptr(), _stream()))
+    return child, log2p, mP
+
+
 def merge_groups(E, lp, deg, pos, starts, min_dEng):
     """Per-group merge of a site-step's candidates (tn_merge_groups): members sorted by group, `starts` the ngroups + 1 offsets.
     Returns (rep_pos, deg, log2p) per group, device tensors."""

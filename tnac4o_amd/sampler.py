@@ -1,0 +1,162 @@
+"""Driver of tnac4o.sample_boltzmann: configurations drawn from the Boltzmann distribution by the library's sampling walk
+(tn_gibbs_sample, csrc/sampler.hip), each with log2 of the probability q(x) it was drawn with, and what follows from those numbers.
+
+For a sample x drawn with probability q(x) the number  s(x) = -beta E(x) / ln 2 - log2 q(x)  is an estimate of log2 Z:
+  * exact contraction: q is the Boltzmann distribution and s(x) = log2 Z for every sample;
+  * truncated boundaries: mean s = log2 Z - KL(q || p) / ln 2 <= log2 Z (a variational bound), and mean 2^s is an unbiased estimate
+    of Z (importance weights 2^(s - log2 Z)).  The spread of s over the samples measures what the truncation costs.
+Z runs over the ACTIVE spins of the model: a spin without any term does not appear in the network (it would add exactly 1 to log2 Z).
+
+The host part (estimators, the layout and validation of the uniform numbers, the chunk planner) is plain numpy and runs without a GPU.
+"""
+import ctypes as C
+
+import numpy as np
+
+LN2 = float(np.log(2.0))
+LDS_BYTES = 150 * 1024                                    # the bound tn_sample_pn holds a cell's table and environments to
+
+
+def log2z_estimators(energy, log2q, beta):
+    """(sample_log2Z (M,), log2Z_lower, log2Z_estimate) of sampled energies and log2 q.  lower = mean of the per-sample values;
+    estimate = log2 mean 2^s, evaluated with the maximum taken out (the values are far beyond the range of 2.0**x).  lower <= estimate
+    (Jensen); they coincide when all samples agree."""
+    s = -float(beta) * np.asarray(energy, dtype=np.float64) / LN2 - np.asarray(log2q, dtype=np.float64)
+    if s.ndim != 1 or s.size == 0:
+        raise ValueError('energy and log2q must be vectors of the same, non-zero length')
+    m = float(np.max(s))
+    lower = float(np.mean(s))
+    est = m + float(np.log2(np.mean(np.exp2(s - m))))
+    return s, lower, max(est, lower)                      # (rounding alone can put the estimate an ulp below the mean of equal values)
+
+
+def check_uniforms(uniforms, ncell, M):
+    """The uniform numbers of a walk: None -> np.random.rand(ncell, M) from numpy's global generator (the stream one rand(M) per cell
+    consumes); else a (ncell, M) float64 numpy array or torch tensor of numbers in [0, 1), row = cell in walk order, which is
+    returned as it is.  Anything else: ValueError."""
+    if uniforms is None:
+        return np.random.rand(ncell, M)
+    is_np = isinstance(uniforms, np.ndarray)
+    if not is_np:
+        import torch
+        if not isinstance(uniforms, torch.Tensor):
+            raise ValueError('uniforms must be None, a numpy array or a torch tensor (got %s)' % type(uniforms).__name__)
+    if tuple(uniforms.shape) != (ncell, M):
+        raise ValueError('uniforms must have shape (Ny*Nx, M) = (%d, %d), got %s' % (ncell, M, tuple(uniforms.shape)))
+    if is_np:
+        if uniforms.dtype != np.float64:
+            raise ValueError('uniforms must be float64, got %s' % uniforms.dtype)
+        ok = bool(np.all((uniforms >= 0.0) & (uniforms < 1.0)))
+    else:
+        import torch
+        if uniforms.dtype != torch.float64:
+            raise ValueError('uniforms must be float64, got %s' % uniforms.dtype)
+        ok = bool(((uniforms >= 0.0) & (uniforms < 1.0)).all().item())
+    if not ok:                                            # (a NaN fails both comparisons)
+        raise ValueError('uniforms must lie in [0, 1) (no NaN)')
+    return uniforms
+
+
+def plan_chunk(M, ws_bytes, budget, B=1):
+    """Samples per call of the walk: the largest power of two <= M whose workspace ws_bytes(chunk) fits `budget` bytes and whose row
+    keys fit int64 (chunk^2 B^2 < 2^63).  MemoryError when not even one sample fits."""
+    if M < 1:
+        raise ValueError('M must be positive')
+    c = 1 << (int(M).bit_length() - 1)
+    while c >= 1:
+        if c * c * int(B) * int(B) < 2 ** 63 and ws_bytes(c) <= budget:
+            return c
+        c >>= 1
+    raise MemoryError('the sampling walk needs %d bytes of workspace for a single sample, %d are available' % (ws_bytes(1), budget))
+
+
+def chunk_slices(M, chunk):
+    """[(lo, hi)] covering 0 .. M in steps of at most chunk."""
+    if chunk is None or int(chunk) != chunk or chunk < 1:
+        raise ValueError('chunk must be a positive integer')
+    return [(lo, min(lo + int(chunk), M)) for lo in range(0, M, int(chunk))]
+
+
+def cell_misfit(q, p, Dr, br):
+    """None, or why tn_sample_pn cannot take a cell (its table, the running sum and the environments share the LDS)."""
+    front = p * Dr + Dr * br + p * br
+    need = (max(front, q) + q) * 8
+    if need > LDS_BYTES:
+        return 'the table of %d states, its running sum and the environments need %d bytes of LDS, tn_sample_pn holds %d' % (q, need, LDS_BYTES)
+    return None
+
+
+def sample_native(solver, M, uniforms=None, chunk=None):
+    """The walk of tnac4o.sample_boltzmann over solver.rhoT (which must be set up), in column slices of `uniforms` of at most `chunk`
+    samples: one upload of the uniform numbers and one read-back of states / energies / log2 q per slice.  Stores the results on
+    the solver and returns the energies."""
+    import torch
+    from . import ops
+    from ._lib import lib
+    from .beam import CellTable
+    Nx, Ny = solver.Nx, solver.Ny
+    ncell = Nx * Ny
+    M = int(M)
+    if M < 1:
+        raise ValueError('M must be positive')
+    uniforms = check_uniforms(uniforms, ncell, M)
+    if chunk is not None:
+        chunk_slices(M, chunk)                            # (validates chunk before any device work)
+    dev = solver.rhoT[0].A[0].device
+    B = int(max(np.max(solver.ld), np.max(solver.lr), 2))
+    table = CellTable(solver)
+    if table.misfit is not None:
+        raise NotImplementedError('sample_boltzmann: ' + table.misfit + ' (limit of the sampling walk, tn_gibbs_sample)')
+    for k in range(ncell):
+        c = table.cells[k]
+        why = cell_misfit(c.q, c.p, c.Dr, c.br)
+        if why is not None:
+            raise NotImplementedError('sample_boltzmann: cell (%d, %d): %s' % (k // Nx, k % Nx, why))
+    L = lib()
+
+    def ws_bytes(m):
+        return int(L.tn_gibbs_sample_ws_bytes(Nx, Ny, m, table.qmax, table.max_env, table.max_t1, table.max_w))
+
+    if chunk is None:
+        chunk = plan_chunk(M, ws_bytes, torch.cuda.mem_get_info(dev)[0] // 2, B)
+    elif int(chunk) ** 2 * B * B >= 2 ** 63:
+        raise NotImplementedError('sample_boltzmann: chunk^2 x (boundary index range)^2 exceeds int64 (row keys): use a smaller chunk')
+    slices = chunk_slices(M, chunk)
+    cmax = max(hi - lo for lo, hi in slices)
+    wsb = ws_bytes(cmax)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    d_states = torch.empty((cmax, ncell), dtype=torch.int16, device=dev)
+    d_E = torch.empty(cmax, dtype=torch.float64, device=dev)
+    d_lq = torch.empty(cmax, dtype=torch.float64, device=dev)
+    states = np.empty((M, ncell), dtype=np.int64)
+    energy = np.empty(M)
+    log2q = np.empty(M)
+    globalmin, max_groups = 1.0, 0
+    on_device = not isinstance(uniforms, np.ndarray)
+    if on_device:
+        uniforms = uniforms.to(dev).contiguous()
+    for lo, hi in slices:
+        m = hi - lo
+        if on_device:
+            u_ptr, ldu, u = uniforms.data_ptr() + lo * 8, M, uniforms
+        else:
+            u = torch.as_tensor(np.ascontiguousarray(uniforms[:, lo:hi])).to(dev)
+            u_ptr, ldu = u.data_ptr(), m
+        gmin, mg = C.c_double(0.0), C.c_int64(0)
+        ops.check(L.tn_gibbs_sample(Nx, Ny, C.cast(table.cells, C.c_void_p), m, B, u_ptr, ldu, d_states.data_ptr(), d_E.data_ptr(),
+                                    d_lq.data_ptr(), C.byref(gmin), C.byref(mg), ws.data_ptr(), wsb, ops._stream()))
+        states[lo:hi] = d_states[:m].cpu().numpy()
+        energy[lo:hi] = d_E[:m].cpu().numpy()
+        log2q[lo:hi] = d_lq[:m].cpu().numpy()
+        globalmin, max_groups = min(globalmin, float(gmin.value)), max(max_groups, int(mg.value))
+        del u
+    del ws, table
+    solver.energy = energy
+    solver.degeneracy = 0
+    solver.states = states[:, solver.order]
+    solver.probability = log2q
+    solver.discarded_probability = 0
+    solver.negative_probability = min(globalmin, 0)
+    solver.sample_log2Z, solver.log2Z_lower, solver.log2Z_estimate = log2z_estimators(energy, log2q, solver.beta)
+    solver.sample_max_groups = max_groups
+    return energy

@@ -979,6 +979,32 @@ class tnac4o:
         self.negative_probability = min(globalmin, 0)
         return Eng
 
+    def sample_boltzmann(self, M=2 ** 16, Dmax=32, tolS=1e-15, tolV=1e-10, max_sweeps=20, graduate_truncation=True, uniforms=None,
+                         chunk=None):
+        """Draw M configurations from the Boltzmann distribution with the library's sampling walk (tn_gibbs_sample): the draws of
+        gibbs_sampling -- a seeded run draws the same configurations -- without the host round trips per cell, and with the
+        probability each configuration was drawn with.  Works in the rotation that is set, Ising and RMF.
+        uniforms: None = np.random.rand(Ny*Nx, M) from numpy's global generator (the stream gibbs_sampling's one rand(M) per cell
+        consumes), or a (Ny*Nx, M) float64 array / device tensor of numbers in [0, 1), row = cell in walk order of the current
+        rotation, column = sample; anything else is a ValueError.  chunk: samples per call of the walk (default: the largest power
+        of two <= M whose workspace fits half of the free device memory); sample k's result does not depend on it.
+        Stores energy (M,), states (M, Nx*Ny) in model cell order, degeneracy = 0, probability (M,) = log2 q(x) of every sample,
+        discarded_probability = 0, negative_probability, and the estimates of the partition function that follow from q
+        (tnac4o_amd/sampler.py): sample_log2Z (M,) = -beta energy / ln 2 - probability, the same number log2 Z for every sample when
+        the contraction is exact; log2Z_lower = its mean (<= log2 Z in expectation), log2Z_estimate = log2 mean 2^sample_log2Z.
+        Z is the partition function over the ACTIVE spins: a spin without any term is not part of the network and would add
+        exactly 1 to log2 Z.  Raises NotImplementedError naming the limit when a cell does not fit the walk; there is no host
+        fallback.  Returns the sampled energies."""
+        from . import sampler
+        if int(M) < 1:
+            raise ValueError('M must be positive')
+        uniforms = sampler.check_uniforms(uniforms, self.Nx * self.Ny, int(M))       # (before any device work)
+        if chunk is not None:
+            sampler.chunk_slices(int(M), chunk)
+        self.logger.info('Sampling (library walk) with beta = %.2f', self.beta)
+        self._setup_rhoT(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        return sampler.sample_native(self, int(M), uniforms=uniforms, chunk=chunk)
+
     # ------------------------------------------------------------------------------------ thermal marginals (GPU)
     def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
         """Boltzmann marginal of every cell and magnetisation of every spin at the solver's beta, from both boundary MPS.
