@@ -301,17 +301,10 @@ def test_config5_rmf64_d8_chi128_fullsize():
 
 # ------------------------------------------------------------------------------------------------ a12 on the device
 def _solve_with(mode, make, **kw):
-    saved = os.environ.get('TN_BEAM')
-    os.environ['TN_BEAM'] = mode
-    try:
+    with _beam_order(mode):
         s = make()
         s.search_ground_state(**kw)
         return s
-    finally:
-        if saved is None:
-            os.environ.pop('TN_BEAM', None)
-        else:
-            os.environ['TN_BEAM'] = saved
 
 
 @pytest.mark.parametrize('case', ['L128_1', 'L128_2_rot1', 'L128_3_chi32', 'L512', 'J124', 'rmf', 'L128_nocut', 'L128_M1'])

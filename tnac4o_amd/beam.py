@@ -38,11 +38,10 @@ class SiteTables:
     energy tables of tnac4o._cell_energies (reference tnac4o.py:1469-1489, 1506-1558)."""
 
     def __init__(self, solver, ny, nx, dev):
-        q = int(solver.N[ny][nx])
-        st = np.arange(q)
-        self.q = q
-        self.down = torch.as_tensor(np.asarray(solver._ind_bond_down(st, ny, nx), dtype=np.int64)).to(dev)
-        self.right = torch.as_tensor(np.asarray(solver._ind_bond_right(st, ny, nx), dtype=np.int64)).to(dev)
+        self.q = int(solver.N[ny][nx])
+        down, right, _, _ = solver._cell_maps(ny, nx)
+        self.down = torch.as_tensor(np.asarray(down, dtype=np.int64)).to(dev)
+        self.right = torch.as_tensor(np.asarray(right, dtype=np.int64)).to(dev)
         Es, E1, E4 = solver._cell_energies(ny, nx)
         self.Es = torch.as_tensor(np.ascontiguousarray(Es, dtype=np.float64)).to(dev)
         self.E1 = torch.as_tensor(np.ascontiguousarray(E1, dtype=np.float64)).to(dev)
@@ -100,13 +99,6 @@ def search_device(solver, M, relative_P_cutoff, min_dEng, beam_group=None):
         # ---- right environments of every distinct suffix (tnac4o._setup_RR, tnac4o.py:1768-1784); sufidx[j] = rank of the branch's
         # suffix vind[:, Nx-j+1:] among the keys of level j (level j serves site nx = Nx-1-j)
         nb = prob.numel()
-        site = {}
-
-        def cell(nx):                                                   # F, dmap, rmap and the MPO site of a cell, built once per row
-            if nx not in site:
-                F, dm, rm, pd, br = solver._peps_factor_dev(ny, nx)
-                site[nx] = (F, dm, rm, pd, br)
-            return site[nx]
         RRs = [torch.ones((1, 1, 1), dtype=f64, device=dev)]
         sufidx = [torch.zeros(nb, dtype=i64, device=dev)]
         nkeys_prev = 1
@@ -114,20 +106,8 @@ def search_device(solver, M, relative_P_cutoff, min_dEng, beam_group=None):
             nk, inv, first = unique_keys(vind[:, nx + 1] * nkeys_prev + sufidx[-1])
             parent = sufidx[-1][first]                                  # the key's own suffix [1:] in the previous level
             uidx = vind[first, nx + 1]
-            F, dm, rm, pd, br_ = cell(nx)
-            W = ops.mpo_from_factor(F, dm, rm, pd, br_)
-            bl, p, br, pu = W.shape
-            A = top.A[nx]
-            Dl, _, Dr = A.shape
-            if Dl * bl <= 2048:
-                RR = ops.env_rr(A.contiguous(), RRs[-1], W, _i32(parent), _i32(uidx))
-            else:
-                RRg = RRs[-1][parent]
-                T = ops.bmm(A.view(1, Dl * p, Dr), RRg)
-                Wt = W.permute(3, 1, 2, 0).reshape(pu, p * br, bl).contiguous()
-                RR = ops.bmm(T.view(-1, Dl, p * br), Wt[uidx])
-                ops.nfactor_batched_(RR)
-            RRs.append(RR)
+            W = solver._mpo_site_dev(ny, nx)
+            RRs.append(ops.env_rr_any(top.A[nx].contiguous(), RRs[-1], W, _i32(parent), _i32(uidx)))
             sufidx.append(inv)
             nkeys_prev = nk
         nsuf = [int(r.shape[0]) for r in RRs]
@@ -138,7 +118,7 @@ def search_device(solver, M, relative_P_cutoff, min_dEng, beam_group=None):
             tb = tab(ny, nx)
             q, nb = tb.q, prob.numel()
             pos = ny * Nx + nx
-            F, dmap, rmap, _, _ = cell(nx)
+            F, dmap, rmap, _, _ = solver._peps_factor_dev(ny, nx)
             AT = top.A[nx]
             Dl, p, Dr = AT.shape
             T1 = ops.mm(RL, AT.view(Dl, p * Dr)).view(-1, p, Dr)
@@ -221,13 +201,8 @@ def search_device(solver, M, relative_P_cutoff, min_dEng, beam_group=None):
             pref = ninv
         vind = torch.cat([torch.zeros((vind.shape[0], 1), dtype=i64, device=dev), vind[:, :-1]], dim=1)      # tnac4o.py:540-542
 
-    solver.energy = Eng.cpu().numpy()
-    solver.degeneracy = int(deg[0].item())
-    solver.states = states.cpu().numpy().astype(solver.indtype)[:, solver.order]
-    solver.probability = prob.cpu().numpy()
-    solver.discarded_probability = float(pd_max.item())
-    solver.negative_probability = min(float(globalmin.item()), 0)
-    return solver.energy
+    return solver._store_result(Eng.cpu().numpy(), states.cpu().numpy().astype(solver.indtype), prob.cpu().numpy(), int(deg[0].item()),
+                                float(pd_max.item()), float(globalmin.item()))
 
 
 # ---------------------------------------------------------------------------------------------------------------- native driver
@@ -358,11 +333,6 @@ def search_native(solver, M, relative_P_cutoff, min_dEng, beam_group=None):
         raise NoCandidate('tn_beam_search: no candidate survives the cut-off')
     ops.check(rc)
     n = int(nb.value)
-    solver.energy = Eng[:n].cpu().numpy()
-    solver.degeneracy = int(deg[0].item())
-    solver.states = states[:n].cpu().numpy().astype(solver.indtype)[:, solver.order]
-    solver.probability = prob[:n].cpu().numpy()
-    solver.discarded_probability = float(pdm.value)
-    solver.negative_probability = min(float(gmin.value), 0)
     del keep
-    return solver.energy
+    return solver._store_result(Eng[:n].cpu().numpy(), states[:n].cpu().numpy().astype(solver.indtype), prob[:n].cpu().numpy(),
+                                int(deg[0].item()), float(pdm.value), float(gmin.value))

@@ -782,6 +782,18 @@ def env_rr(A, RRprev, W, parent, uidx):
     return out
 
 
+def env_rr_any(A, RRprev, W, parent, uidx):
+    """env_rr for bonds of any width: tn_env_rr_batched (gather, both contractions and nfactor in one launch) where its
+    Dl x bl <= 2048 accumulators hold the result, else the same contraction as two batched GEMMs."""
+    Dl, p, Dr = A.shape
+    bl, _, br, pu = W.shape
+    if Dl * bl <= 2048:
+        return env_rr(A, RRprev, W, parent, uidx)
+    T = bmm(A.view(1, Dl * p, Dr), RRprev[parent.long()])                 # (nk, Dl p, br)
+    Wt = W.permute(3, 1, 2, 0).reshape(pu, p * br, bl).contiguous()
+    return nfactor_batched_(bmm(T.view(-1, Dl, p * br), Wt[uidx.long()]))     # (nk, Dl, bl)
+
+
 def env_rl(T1, par, didx):
     """Left environments of the new distinct prefixes: rows (par[k], didx[k]) of T1 (npref, p, Dr), nfactor-normalised."""
     _, p, Dr = T1.shape

@@ -151,12 +151,7 @@ def sample_native(solver, M, uniforms=None, chunk=None):
         globalmin, max_groups = min(globalmin, float(gmin.value)), max(max_groups, int(mg.value))
         del u
     del ws, table
-    solver.energy = energy
-    solver.degeneracy = 0
-    solver.states = states[:, solver.order]
-    solver.probability = log2q
-    solver.discarded_probability = 0
-    solver.negative_probability = min(globalmin, 0)
+    solver._store_result(energy, states, log2q, 0, 0, globalmin)
     solver.sample_log2Z, solver.log2Z_lower, solver.log2Z_estimate = log2z_estimators(energy, log2q, solver.beta)
     solver.sample_max_groups = max_groups
     return energy

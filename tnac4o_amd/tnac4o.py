@@ -75,6 +75,24 @@ def _unique_rows(a):
     return a[first], inv
 
 
+def _rank_in(keys, rows):
+    """Rank of every row of `rows` among the sorted unique rows `keys` (each of them must occur there)."""
+    _, inv = _unique_rows(np.vstack([keys, rows]))
+    return inv[len(keys):]
+
+
+def _read_back(tensors):
+    """Host arrays with the shapes of a list of float64 device tensors, through ONE device-to-host copy."""
+    flat = torch.cat([t.reshape(-1) for t in tensors]).cpu().numpy()
+    offs = np.cumsum([0] + [int(t.numel()) for t in tensors])
+    return [flat[lo:hi].reshape(tuple(t.shape)).copy() for t, lo, hi in zip(tensors, offs[:-1], offs[1:])]
+
+
+def _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps):
+    """The options of a boundary sweep, as _setup_rhoT / _setup_rhoB take them."""
+    return dict(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+
+
 def _merge_groups(inv, Eng, prob, deg, min_dEng, canonical=True):
     """The merge of branches with identical boundary indices (tnac4o.py:481-509), vectorised: per group the
     representative is the first minimal-energy member, the degeneracy is summed over members within min_dEng of the minimum
@@ -108,6 +126,43 @@ def _merge_groups(inv, Eng, prob, deg, min_dEng, canonical=True):
         else:
             probn[k] = np.mean(prob[same])
     return indn, degn, probn, order, starts
+
+
+class _RowWalk:
+    """The environments of one row of a host walk (host path of search_ground_state, gibbs_sampling; tnac4o.py:434-436,
+    528-542): right environments of every distinct suffix of the boundary rows `vind` at the start of the row, left
+    environments of the distinct prefixes carried from site to site."""
+
+    def __init__(self, solver, vind, ny):
+        self.solver, self.ny = solver, ny
+        self.levels = solver._setup_RR(vind, ny)
+        self.top = solver.rhoT[ny + 1]
+        self.pkeys = np.zeros((1, 0), dtype=vind.dtype)                      # distinct prefixes, sorted
+        self.RL = torch.ones((1, 1), dtype=torch.float64, device=self.top.A[0].device)      # (nprefix, Dl)
+
+    def site(self, nx, vind):
+        """What ops.calc_pn takes at site nx for the boundary rows vind: (T1, RR, F, dmap, rmap, pref, suf) with pref / suf the
+        rank of each row's prefix / suffix among the rows of T1 / RR."""
+        F, dmap, rmap, _, _ = self.solver._peps_factor_dev(self.ny, nx)
+        AT = self.top.A[nx]
+        Dl, p, Dr = AT.shape
+        # every prefix's left environment through the top site in one GEMM: T1[prefix, d, chi']
+        self.T1 = ops.mm(self.RL, AT.view(Dl, p * Dr)).view(-1, p, Dr)
+        skeys, RR = self.levels[len(self.levels) - nx - 1]
+        return self.T1, RR, F, dmap, rmap, _rank_in(self.pkeys, vind[:, :nx]), _rank_in(skeys, vind[:, nx + 2:])
+
+    def advance(self, nx, vind):
+        """Left environments of the distinct prefixes vind[:, :nx+1] once site nx is decided: rows of T1 (tnac4o.py:528-535)."""
+        nkeys, _ = _unique_rows(vind[:, :nx + 1])
+        par = _rank_in(self.pkeys, nkeys[:, :nx])
+        self.RL = ops.env_rl(self.T1, _dev_i32(par), _dev_i32(nkeys[:, nx]))
+        self.pkeys = nkeys
+
+    @staticmethod
+    def end_row(vind):
+        """The row's lower bonds become the next row's upper ones (tnac4o.py:540-542)."""
+        vind[:, 1:] = vind[:, :-1]
+        vind[:, 0] = 0
 
 
 def model_marginals(P_rot, order, ind0=None, L=None):
@@ -368,17 +423,29 @@ class tnac4o:
         self._divide_couplings()
 
     # ------------------------------------------------------------------------------------ local tables (host)
+    def _cell_maps(self, ny, nx):
+        """dmap[s], rmap[s], pd, br of a cell: the index every cell state s puts on the bond to the row below / to the cell on
+        the right, and the dimensions of those two bonds (tnac4o.py:1469-1489, 1598-1607)."""
+        if self.mode == 'Ising':
+            bt = _bits(self.sN[ny][nx])
+            rmap = bt[:, self.ir[ny][nx]] @ (2 ** np.arange(self.sr[ny][nx]))
+            dmap = bt[:, self.id[ny][nx]] @ (2 ** np.arange(self.sd[ny][nx]))
+            br, pd = 2 ** self.sr[ny][nx], 2 ** self.sd[ny][nx]
+        else:
+            q = int(self.N[ny][nx])
+            s = np.arange(q)
+            br, pd = int(self.lr[ny, nx]), int(self.ld[ny, nx])
+            rmap = s % br if br > 1 else np.zeros(q, dtype=int)
+            dmap = s % pd if pd > 1 else np.zeros(q, dtype=int)
+        return dmap, rmap, int(pd), int(br)
+
     def _ind_bond_down(self, st, ny, nx):
         """tnac4o.py:1469-1478."""
-        if self.mode == 'Ising':
-            return _bits(self.sN[ny][nx])[st][:, self.id[ny][nx]] @ (2 ** np.arange(self.sd[ny][nx]))
-        return np.mod(st, self.ld[ny, nx])
+        return self._cell_maps(ny, nx)[0][st]
 
     def _ind_bond_right(self, st, ny, nx):
         """tnac4o.py:1480-1489."""
-        if self.mode == 'Ising':
-            return _bits(self.sN[ny][nx])[st][:, self.ir[ny][nx]] @ (2 ** np.arange(self.sr[ny][nx]))
-        return np.mod(st, self.lr[ny, nx])
+        return self._cell_maps(ny, nx)[1][st]
 
     def _cell_energies(self, ny, nx):
         """Es[s], Ese1[s,l], Ese4[s,u] (Ising tnac4o.py:1570-1581, RMF 1613-1635)."""
@@ -419,46 +486,28 @@ class tnac4o:
     def _peps_factor(self, ny, nx):
         """F[s,l,u], dmap[s], rmap[s], pd, br with T[s,l,d,r,u] = F[s,l,u][d=dmap[s]][r=rmap[s]]
         (tnac4o.py:1562-1672; same floating-point evaluation order as the reference)."""
-        b = self.beta
-        Es, E1, E4 = self._cell_energies(ny, nx)
-        Es, E1, E4 = b * (np.min(Es) - Es), b * (np.min(E1) - E1), b * (np.min(E4) - E4)
+        Es, E1, E4 = self._scaled_energies(ny, nx)
         F = np.exp((Es[:, None, None] + E1[:, :, None]) + E4[:, None, :])
         nl, nu = F.shape[1], F.shape[2]
         F = F * self.Xu[ny][nx][:nu][None, None, :]
         F = F * self.Xl[ny][nx][:nl][None, :, None]
-        q = F.shape[0]
-        if self.mode == 'Ising':
-            bt = _bits(self.sN[ny][nx])
-            rmap = bt[:, self.ir[ny][nx]] @ (2 ** np.arange(self.sr[ny][nx]))
-            dmap = bt[:, self.id[ny][nx]] @ (2 ** np.arange(self.sd[ny][nx]))
-            br, pd = 2 ** self.sr[ny][nx], 2 ** self.sd[ny][nx]
-        else:
-            s = np.arange(q)
-            br, pd = int(self.lr[ny, nx]), int(self.ld[ny, nx])
-            rmap = s % br if br > 1 else np.zeros(q, dtype=int)
-            dmap = s % pd if pd > 1 else np.zeros(q, dtype=int)
+        dmap, rmap, pd, br = self._cell_maps(ny, nx)
         F = F * self.Xr[ny][nx][rmap][:, None, None]
         F = F * self.Xd[ny][nx][dmap][:, None, None]
-        return F, np.asarray(dmap, dtype=np.int64), np.asarray(rmap, dtype=np.int64), int(pd), int(br)
+        return F, np.asarray(dmap, dtype=np.int64), np.asarray(rmap, dtype=np.int64), pd, br
+
+    def _scaled_energies(self, ny, nx):
+        """The three energy tables of a cell as the PEPS factor exponentiates them: beta (min E - E), each table shifted by
+        its own minimum (tnac4o.py:1570-1583)."""
+        b = self.beta
+        Es, E1, E4 = self._cell_energies(ny, nx)
+        return b * (np.min(Es) - Es), b * (np.min(E1) - E1), b * (np.min(E4) - E4)
 
     def _site_tables(self, ny, nx):
         """Host side of K7: the three beta-scaled, min-shifted energy tables and the index maps of a cell (O(q) work;
         tnac4o.py:1570-1583, 1598-1607).  The exponentials, gauge products and the sum over s run on the GPU."""
-        b = self.beta
-        Es, E1, E4 = self._cell_energies(ny, nx)
-        Es, E1, E4 = b * (np.min(Es) - Es), b * (np.min(E1) - E1), b * (np.min(E4) - E4)
-        q = Es.shape[0]
-        if self.mode == 'Ising':
-            bt = _bits(self.sN[ny][nx])
-            rmap = bt[:, self.ir[ny][nx]] @ (2 ** np.arange(self.sr[ny][nx]))
-            dmap = bt[:, self.id[ny][nx]] @ (2 ** np.arange(self.sd[ny][nx]))
-            br, pd = 2 ** self.sr[ny][nx], 2 ** self.sd[ny][nx]
-        else:
-            s = np.arange(q)
-            br, pd = int(self.lr[ny, nx]), int(self.ld[ny, nx])
-            rmap = s % br if br > 1 else np.zeros(q, dtype=int)
-            dmap = s % pd if pd > 1 else np.zeros(q, dtype=int)
-        return Es, np.ascontiguousarray(E1), np.ascontiguousarray(E4), dmap, rmap, int(pd), int(br)
+        Es, E1, E4 = self._scaled_energies(ny, nx)
+        return (Es, np.ascontiguousarray(E1), np.ascontiguousarray(E4)) + self._cell_maps(ny, nx)
 
     def _peps_factors_dev(self, cells):
         """[(F, dmap, rmap, pd, br)] as device tensors for a list of cells (K7, tn_peps_factor).  The seven small float tables of ALL the
@@ -527,31 +576,28 @@ class tnac4o:
     # ------------------------------------------------------------------------------------ sweeps (GPU)
     def _setup_rhoT(self, graduate_truncation=True, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20):
         """Top boundary MPS of every row, built bottom-up (tnac4o.py:1674-1695)."""
-        Ny = self.Ny
-        self.rhoT = [None] * (Ny + 1)
-        self.rhoT_overlap = [1] * (Ny + 1)
-        self.rhoT_discarded = [0] * (Ny + 1)
-        self.rhoT[Ny] = mps.MPS(d=1, L=self.Nx, Dmax=1, initial='X')
-        for ny in range(Ny - 1, -1, -1):
-            psi = self.rhoT[ny + 1].copy()
-            self.rhoT_overlap[ny] = psi.apply_mpo_compress(self._row_mpo(ny), Hconj=True, Dmax=Dmax, tolS=tolS, tolV=tolV,
-                                                           max_sweeps=max_sweeps, graduate_truncation=graduate_truncation)
-            self.rhoT_discarded[ny] = max(psi.discarded)
-            self.rhoT[ny] = psi
+        self._setup_boundary('rhoT', _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps))
 
     def _setup_rhoB(self, graduate_truncation=True, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20):
         """Bottom boundary MPS, built top-down (tnac4o.py:1697-1718)."""
-        Ny = self.Ny
-        self.rhoB = [None] * (Ny + 1)
-        self.rhoB_overlap = [1] * (Ny + 1)
-        self.rhoB_discarded = [0] * (Ny + 1)
-        self.rhoB[0] = mps.MPS(d=1, L=self.Nx, Dmax=1, initial='X')
-        for ny in range(Ny):
-            psi = self.rhoB[ny].copy()
-            self.rhoB_overlap[ny + 1] = psi.apply_mpo_compress(self._row_mpo(ny), Hconj=False, Dmax=Dmax, tolS=tolS, tolV=tolV,
-                                                               max_sweeps=max_sweeps, graduate_truncation=graduate_truncation)
-            self.rhoB_discarded[ny + 1] = max(psi.discarded)
-            self.rhoB[ny + 1] = psi
+        self._setup_boundary('rhoB', _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps))
+
+    def _setup_boundary(self, name, options):
+        """The boundary MPS `name` of every row with their overlaps and discarded weights (name, name_overlap, name_discarded):
+        'rhoT' starts below the last row and absorbs the conjugated row MPOs upwards, 'rhoB' starts above the first row and
+        absorbs the row MPOs downwards."""
+        Ny, up = self.Ny, name == 'rhoT'
+        rho, overlap, discarded = [None] * (Ny + 1), [1] * (Ny + 1), [0] * (Ny + 1)
+        setattr(self, name, rho)
+        setattr(self, name + '_overlap', overlap)
+        setattr(self, name + '_discarded', discarded)
+        rho[Ny if up else 0] = mps.MPS(d=1, L=self.Nx, Dmax=1, initial='X')
+        for ny in (range(Ny - 1, -1, -1) if up else range(Ny)):
+            src, dst = (ny + 1, ny) if up else (ny, ny + 1)
+            psi = rho[src].copy()
+            overlap[dst] = psi.apply_mpo_compress(self._row_mpo(ny), Hconj=up, **options)
+            discarded[dst] = max(psi.discarded)
+            rho[dst] = psi
 
     # ------------------------------------------------------------------------------------ preconditioning
     def precondition(self, mode='balancing', steps=2, beta_cond=(), Dmax_cond=(), max_scale=1024,
@@ -587,12 +633,9 @@ class tnac4o:
         (tnac4o.py:1857-1865)."""
         if not pending:
             return
-        flat = torch.cat([torch.cat([sc, o1, o2]) for (_, _, sc, o1, o2) in pending]).cpu().numpy()
-        off = 0
-        for (ny, nx, sc, _, _) in pending:
-            k = sc.numel()
-            scale, o1, o2 = flat[off:off + k], float(flat[off + k]), float(flat[off + k + 1])
-            off += k + 2
+        host = _read_back([t for p in pending for t in p[2:]])
+        for k, (ny, nx, _, _, _) in enumerate(pending):
+            scale, o1, o2 = host[3 * k], float(host[3 * k + 1][0]), float(host[3 * k + 2][0])
             if o1 < overlaps[0, ny - 1]:
                 overlaps[0, ny - 1] = o1
                 overlaps[1, ny - 1] = max(o1, o2)
@@ -604,7 +647,7 @@ class tnac4o:
                              max_scale=1024):
         """tnac4o.py:1824-1918 ('ud' direction; the 'lr' branch is dead code in the reference)."""
         max_scale = 2.0 ** np.floor(np.log2(np.sqrt(max_scale)))
-        kw = dict(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        kw = _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps)
         self._setup_rhoT(**kw)
         self._setup_rhoB(**kw)
         overlaps = np.ones((2, self.Ny - 1))
@@ -652,22 +695,10 @@ class tnac4o:
         for nx in range(self.Nx - 1, 0, -1):
             keys, _ = _unique_rows(vind[:, nx + 1:])
             pkeys, prr = levels[-1]
-            _, pinv = _unique_rows(np.vstack([pkeys, keys[:, 1:]]))          # parent rows: match suffix[1:] to pkeys
-            parent = pinv[len(pkeys):]
-            # pkeys are sorted-unique, so their own inverse is the identity: parent indexes rows of prr directly
+            # parent rows: suffix[1:] among pkeys, which are sorted-unique, so the rank indexes rows of prr directly
+            parent = _rank_in(pkeys, keys[:, 1:])
             W = self._mpo_site_dev(ny, nx)                                   # (bl, p, br, pu)
-            bl, p, br, pu = W.shape
-            A = top.A[nx]
-            Dl, _, Dr = A.shape
-            if Dl * bl <= 2048:              # K9: gather + both contractions + nfactor in one launch
-                RR = ops.env_rr(A.contiguous(), prr, W, _dev_i32(parent), _dev_i32(keys[:, 0]))
-            else:                            # very wide bonds: the same contraction as two batched GEMMs
-                RRg = prr[torch.as_tensor(parent, device=dev)]                   # (nk, Dr, br)
-                T = ops.bmm(A.view(1, Dl * p, Dr), RRg)                          # (nk, Dl p, br)
-                Wt = W.permute(3, 1, 2, 0).reshape(pu, p * br, bl).contiguous()
-                Wsel = Wt[torch.as_tensor(keys[:, 0].astype(np.int64), device=dev)]
-                RR = ops.bmm(T.view(-1, Dl, p * br), Wsel)                       # (nk, Dl, bl)
-                ops.nfactor_batched_(RR)
+            RR = ops.env_rr_any(top.A[nx].contiguous(), prr, W, _dev_i32(parent), _dev_i32(keys[:, 0]))
             levels.append((keys, RR))
         return levels
 
@@ -729,7 +760,6 @@ class tnac4o:
         if self.mode == 'Ising':
             rows, cols = self.J.nonzero()
             self.J[rows, cols] += (np.random.rand(len(rows)) * 2 - 1) * amplitude
-            self._divide_couplings()
         else:
             fun = {}
             for key, val in self.J['fun'].items():
@@ -737,7 +767,7 @@ class tnac4o:
                 if fun[key].ndim == 1:
                     fun[key] += (np.random.rand(fun[key].shape[0]) * 2 - 1) * amplitude
             self.J['fun'] = fun
-            self._divide_couplings()
+        self._divide_couplings()
 
     def decode_low_energy_states(self, max_dEng=0., max_states=1024):
         """Turn the recorded excitation forest into explicit states, lowest energies first (tnac4o.py:1360-1389).
@@ -765,7 +795,7 @@ class tnac4o:
         rank ends with the complete, identical result."""
         from . import parallel
         self.logger.info('Searching ground state with beta = %.2f', self.beta)
-        kw_sweep = dict(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        kw_sweep = _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps)
         # the PEPS factor of a cell (K7) serves the row MPO of the sweep and, unchanged, the conditional tables of the search: kept
         # between the two for the duration of this call (134 MB at L = 2048) instead of being rebuilt
         self._factor_keep = {}
@@ -808,26 +838,13 @@ class tnac4o:
         states = np.zeros((1, Nx * Ny), dtype=self.indtype)
         Eng, prob, deg = np.zeros(1), np.zeros(1), np.ones(1, dtype=int)
         pd_max, globalmin = -np.inf, 0.0
-        dev = self.rhoT[0].A[0].device
 
         for ny in range(Ny):
             self.logger.info('Row %d / %d', ny + 1, Ny)
-            levels = self._setup_RR(vind, ny)
-            top = self.rhoT[ny + 1]
-            pkeys = np.zeros((1, 0), dtype=vind.dtype)                       # distinct prefixes, sorted
-            RL = torch.ones((1, 1), dtype=torch.float64, device=dev)         # (nprefix, Dl)
+            walk = _RowWalk(self, vind, ny)
             for nx in range(Nx):
                 q, nb = int(self.N[ny][nx]), prob.size
-                F, dmap, rmap, _, _ = self._peps_factor_dev(ny, nx)
-                AT = top.A[nx]
-                Dl, p, Dr = AT.shape
-                # every prefix's left environment through the top site in one GEMM: T1[prefix, d, chi']
-                T1 = ops.mm(RL, AT.view(Dl, p * Dr)).view(-1, p, Dr)
-                _, pref = _unique_rows(np.vstack([pkeys, vind[:, :nx]]))
-                pref = pref[len(pkeys):]
-                skeys, RR = levels[Nx - nx - 1]
-                _, suf = _unique_rows(np.vstack([skeys, vind[:, nx + 2:]]))
-                suf = suf[len(skeys):]
+                T1, RR, F, dmap, rmap, pref, suf = walk.site(nx, vind)
                 def pn_slice(lo, hi):                                        # K8 on the branches lo..hi-1
                     if not canonical:
                         return ops.calc_pn(T1, RR, F, dmap, rmap, _dev_i32(pref[lo:hi]), _dev_i32(suf[lo:hi]),
@@ -899,26 +916,25 @@ class tnac4o:
                 if sel is not None:
                     vind, states, prob, Eng, deg = vind[sel], states[sel], prob[sel], Eng[sel], deg[sel]
 
-                # left environments of the new distinct prefixes: rows of T1 (tnac4o.py:528-535)
-                nkeys, _ = _unique_rows(vind[:, :nx + 1])
-                _, par = _unique_rows(np.vstack([pkeys, nkeys[:, :nx]]))
-                par = par[len(pkeys):]
-                RL = ops.env_rl(T1, _dev_i32(par), _dev_i32(nkeys[:, nx]))
-                pkeys = nkeys
+                walk.advance(nx, vind)
                 globalmin = min(globalmin, minprob)
 
             if recorder is not None and hasattr(recorder, 'end_row'):
                 recorder.end_row()
-            vind[:, 1:] = vind[:, :-1]                                       # tnac4o.py:540-542
-            vind[:, 0] = 0
+            walk.end_row(vind)
 
-        self.energy = Eng
-        self.degeneracy = deg[0]
+        return self._store_result(Eng, states, prob, deg[0], pd_max, globalmin)
+
+    def _store_result(self, energy, states, probability, degeneracy, discarded, globalmin):
+        """The result attributes of a walk (search or sampling): `states` arrive in the cell order of the current rotation and
+        are stored in model order; globalmin is the smallest conditional probability met.  Returns the energies."""
+        self.energy = energy
+        self.degeneracy = degeneracy
         self.states = states[:, self.order]
-        self.probability = prob
-        self.discarded_probability = pd_max
+        self.probability = probability
+        self.discarded_probability = discarded
         self.negative_probability = min(globalmin, 0)
-        return Eng
+        return energy
 
     def gibbs_sampling(self, M=2 ** 10, graduate_truncation=True, Dmax=32, tolS=1e-15, tolV=1e-10, max_sweeps=20):
         """Draw M configurations from the Boltzmann distribution, cell by cell from the conditional probabilities of the
@@ -932,26 +948,13 @@ class tnac4o:
         states = np.zeros((M, Nx * Ny), dtype=np.int64)
         Eng = np.zeros(M)
         globalmin = 1.0
-        dev = self.rhoT[0].A[0].device
         for ny in range(Ny):
             self.logger.info('Row %d / %d', ny + 1, Ny)
-            levels = self._setup_RR(vind, ny)
-            top = self.rhoT[ny + 1]
-            pkeys = np.zeros((1, 0), dtype=vind.dtype)
-            RL = torch.ones((1, 1), dtype=torch.float64, device=dev)
+            walk = _RowWalk(self, vind, ny)
             for nx in range(Nx):
-                q = int(self.N[ny][nx])
-                F, dmap, rmap, _, _ = self._peps_factor_dev(ny, nx)
-                AT = top.A[nx]
-                Dl, p, Dr = AT.shape
-                T1 = ops.mm(RL, AT.view(Dl, p * Dr)).view(-1, p, Dr)
                 # distinct boundary configurations only (the reference's `seen` dictionary, :601-612)
                 uvind, uinv = _unique_rows(vind)
-                _, pref = _unique_rows(np.vstack([pkeys, uvind[:, :nx]]))
-                pref = pref[len(pkeys):]
-                skeys, RR = levels[Nx - nx - 1]
-                _, suf = _unique_rows(np.vstack([skeys, uvind[:, nx + 2:]]))
-                suf = suf[len(skeys):]
+                T1, RR, F, dmap, rmap, pref, suf = walk.site(nx, uvind)
                 P, mP = ops.calc_pn(T1, RR, F, dmap, rmap, _dev_i32(pref), _dev_i32(suf), _dev_i32(uvind[:, nx]),
                                     _dev_i32(uvind[:, nx + 1]))
                 newprob = P.cpu().numpy()[uinv]
@@ -963,21 +966,10 @@ class tnac4o:
                 vind[:, nx] = self._ind_bond_down(indc, ny, nx)
                 vind[:, nx + 1] = self._ind_bond_right(indc, ny, nx)
                 Eng += self._update_Eng(states, ny, nx)
-                nkeys, _ = _unique_rows(vind[:, :nx + 1])                    # left environments (:628-636)
-                _, par = _unique_rows(np.vstack([pkeys, nkeys[:, :nx]]))
-                par = par[len(pkeys):]
-                RL = ops.env_rl(T1, _dev_i32(par), _dev_i32(nkeys[:, nx]))
-                pkeys = nkeys
+                walk.advance(nx, vind)                                       # left environments (:628-636)
                 globalmin = min(globalmin, minprob)
-            vind[:, 1:] = vind[:, :-1]
-            vind[:, 0] = 0
-        self.energy = Eng
-        self.degeneracy = 0
-        self.states = states[:, self.order]
-        self.probability = np.zeros(1)
-        self.discarded_probability = 0
-        self.negative_probability = min(globalmin, 0)
-        return Eng
+            walk.end_row(vind)
+        return self._store_result(Eng, states, np.zeros(1), 0, 0, globalmin)
 
     def sample_boltzmann(self, M=2 ** 16, Dmax=32, tolS=1e-15, tolV=1e-10, max_sweeps=20, graduate_truncation=True, uniforms=None,
                          chunk=None):
@@ -1014,7 +1006,7 @@ class tnac4o:
         RMF), `marginals_negative` (<= 0, the negative-probability measure of search_ground_state) and `marginal_row_log2`
         (Ny, Nx) in the rotated frame: log2 of each row's contraction, the same for every cell of a row.  Leaves the search
         results, gauges and rotation alone; rebuilds rhoT and rhoB."""
-        kw = dict(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        kw = _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps)
         self.logger.info('Marginals with beta = %.2f', self.beta)
         self._setup_rhoT(**kw)
         self._setup_rhoB(**kw)
@@ -1027,16 +1019,18 @@ class tnac4o:
             self.marginals, self.magnetization = model_marginals(P_rot, self.order)[0], None
         return self.marginals
 
-    def _marginal_pass(self):
-        """Cell marginals of the rotated lattice from rhoT / rhoB as they stand.  Per row: right environments (and their
-        half-products) from the right end, then the left sweep with each cell's marginal.  One read-back at the end.
-        Returns (list of per-cell vectors, row-major; minP (Ny*Nx,); log2 row contractions (Ny, Nx))."""
-        Nx, Ny = self.Nx, self.Ny
+    def _open_cell_pass(self, kernel):
+        """Every row of the rotated lattice contracted between rhoB[ny] and rhoT[ny+1] as they stand, with one cell left open at
+        a time.  Per row: the right environments with their half-products and running log2 factors from the right end (tn_env3),
+        then the left sweep, calling kernel(HL, HR, F, dmap, rmap, log2L, log2R) -> device tensors at every cell; a cell's HR is
+        dropped once its kernel is enqueued.  One read-back at the end.  Returns, for each output of the kernel, the list of the
+        cells' host arrays (row-major)."""
+        Nx = self.Nx
         dev = self.rhoT[0].A[0].device
         one = torch.ones((1, 1, 1), dtype=torch.float64, device=dev)
         zero = torch.zeros(1, dtype=torch.float64, device=dev)
-        Ps, mPs, lzs = [], [], []
-        for ny in range(Ny):
+        outs = []
+        for ny in range(self.Ny):
             top, bot = self.rhoT[ny + 1].A, self.rhoB[ny].A
             fac = self._peps_factors_dev([(ny, nx) for nx in range(Nx)])
             Ws = [ops.mpo_from_factor(F, dm, rm, pd, br) for (F, dm, rm, pd, br) in fac]
@@ -1052,20 +1046,18 @@ class tnac4o:
             for nx in range(Nx):
                 F, dm, rm, _, _ = fac[nx]
                 ELn, lgLn, HL = ops.env3(0, EL, At[nx], Ws[nx], Ab[nx], lgL, keep_half=True)
-                P, mP, lz = ops.cluster_marginal(HL, HR[nx], F, dm, rm, lgL, lgRs[nx + 1])
+                outs.append(kernel(HL, HR[nx], F, dm, rm, lgL, lgRs[nx + 1]))
                 HR[nx] = None
-                Ps.append(P)
-                mPs.append(mP)
-                lzs.append(lz)
                 EL, lgL = ELn, lgLn
-        flat = torch.cat(Ps + mPs + lzs).cpu().numpy()
-        sizes = [int(p.numel()) for p in Ps]
-        offs = np.concatenate([[0], np.cumsum(sizes)])
-        P_rot = [flat[offs[i]:offs[i + 1]].copy() for i in range(len(Ps))]
-        n = len(Ps)
-        minP = flat[offs[-1]:offs[-1] + n].copy()
-        log2z = flat[offs[-1] + n:offs[-1] + 2 * n].reshape(Ny, Nx).copy()
-        return P_rot, minP, log2z
+        n = len(outs)
+        host = _read_back([t for kind in zip(*outs) for t in kind])
+        return [host[k:k + n] for k in range(0, len(host), n)]
+
+    def _marginal_pass(self):
+        """Cell marginals of the rotated lattice from rhoT / rhoB as they stand: _open_cell_pass with tn_cluster_marginal per cell.
+        Returns (list of per-cell vectors, row-major; minP (Ny*Nx,); log2 row contractions (Ny, Nx))."""
+        P_rot, minP, log2z = self._open_cell_pass(ops.cluster_marginal)
+        return P_rot, np.concatenate(minP), np.concatenate(log2z).reshape(self.Ny, self.Nx)
 
     # ------------------------------------------------------------------------------------ thermal correlations (GPU)
     def calculate_correlations(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
@@ -1078,7 +1070,7 @@ class tnac4o:
         Both store `energy_mean` (<E> in the convention of `energy`), `correlations_negative` (<= 0, the smallest table entry)
         and `correlation_row_log2` (Ny, Nx) in the rotated frame (log2 of each row's contraction, as marginal_row_log2).
         Leaves the search results, marginals, gauges and rotation alone; rebuilds rhoT and rhoB."""
-        kw = dict(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        kw = _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps)
         self.logger.info('Correlations with beta = %.2f', self.beta)
         self._setup_rhoT(**kw)
         self._setup_rhoB(**kw)
@@ -1107,47 +1099,10 @@ class tnac4o:
         return Em
 
     def _correlation_pass(self):
-        """Bond tables of the rotated lattice from rhoT / rhoB as they stand: the environments and half-products of
-        _marginal_pass, tn_cluster_bond_marginal per cell, one read-back at the end.  Returns (Pl list (q, bl), Pu list (q, pu),
-        row-major over cells; minB (Ny*Nx,); log2 row contractions (Ny, Nx))."""
-        Nx, Ny = self.Nx, self.Ny
-        dev = self.rhoT[0].A[0].device
-        one = torch.ones((1, 1, 1), dtype=torch.float64, device=dev)
-        zero = torch.zeros(1, dtype=torch.float64, device=dev)
-        Pls, Pus, mBs, lzs = [], [], [], []
-        for ny in range(Ny):
-            top, bot = self.rhoT[ny + 1].A, self.rhoB[ny].A
-            fac = self._peps_factors_dev([(ny, nx) for nx in range(Nx)])
-            Ws = [ops.mpo_from_factor(F, dm, rm, pd, br) for (F, dm, rm, pd, br) in fac]
-            At = [a.contiguous() for a in top]
-            Ab = [a.contiguous() for a in bot]
-            ER, lgR, HR = one, zero, [None] * Nx
-            lgRs = [None] * (Nx + 1)
-            lgRs[Nx] = zero
-            for nx in range(Nx - 1, -1, -1):
-                ER, lgR, HR[nx] = ops.env3(1, ER, At[nx], Ws[nx], Ab[nx], lgR, keep_half=True)
-                lgRs[nx] = lgR
-            EL, lgL = one, zero
-            for nx in range(Nx):
-                F, dm, rm, _, _ = fac[nx]
-                ELn, lgLn, HL = ops.env3(0, EL, At[nx], Ws[nx], Ab[nx], lgL, keep_half=True)
-                Pl, Pu, mB, lz = ops.cluster_bond_marginal(HL, HR[nx], F, dm, rm, lgL, lgRs[nx + 1])
-                HR[nx] = None
-                Pls.append(Pl)
-                Pus.append(Pu)
-                mBs.append(mB)
-                lzs.append(lz)
-                EL, lgL = ELn, lgLn
-        flat = torch.cat([t.reshape(-1) for t in Pls + Pus] + mBs + lzs).cpu().numpy()
-        out, off = [], 0
-        for t in Pls + Pus:
-            n = int(t.numel())
-            out.append(flat[off:off + n].reshape(tuple(t.shape)).copy())
-            off += n
-        n = len(Pls)
-        minB = flat[off:off + n].copy()
-        log2z = flat[off + n:off + 2 * n].reshape(Ny, Nx).copy()
-        return out[:n], out[n:], minB, log2z
+        """Bond tables of the rotated lattice from rhoT / rhoB as they stand: _open_cell_pass with tn_cluster_bond_marginal per
+        cell.  Returns (Pl list (q, bl), Pu list (q, pu), row-major over cells; minB (Ny*Nx,); log2 row contractions (Ny, Nx))."""
+        Pl, Pu, minB, log2z = self._open_cell_pass(ops.cluster_bond_marginal)
+        return Pl, Pu, np.concatenate(minB), np.concatenate(log2z).reshape(self.Ny, self.Nx)
 
     # ------------------------------------------------------------------------------------ output
     def binary_states(self, number=-1):
