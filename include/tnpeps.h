@@ -178,6 +178,11 @@ int tn_peps_factor(const double* Es, const double* E1, const double* E4, const d
                    void* stream);
 int tn_mpo_from_factor(const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nl, int64_t nu, int64_t pd,
                        int64_t br, double* W, void* stream);
+/* The same sum with operator weights on the cell's states, for the in-line correlation functions below:
+ *   Wops[0] = W (bit for bit);   Wops[a][l,d,r,u] = sum_{s: dmap[s]=d, rmap[s]=r} O[a-1][s] F[s,l,u],  a = 1 .. nop
+ * O (nop, q) row-major (may be NULL when nop = 0), Wops (1 + nop, nl, pd, br, nu).  One launch.  q <= 8192. */
+int tn_mpo_from_factor_ops(const double* F, const int32_t* dmap, const int32_t* rmap, const double* O, int64_t nop, int64_t q, int64_t nl,
+                           int64_t nu, int64_t pd, int64_t br, double* Wops, void* stream);
 
 /* ---- K8: conditional probabilities of one cell for a batch of branches.  Replaces the per-branch loop
  * tnac4o.py:444-448 around _calculate_Pn (:1786-1807), including the negative-probability rule.
@@ -336,6 +341,27 @@ int64_t tn_cluster_bond_marginal_ws_bytes(int64_t q, int64_t bl, int64_t pd, int
 int tn_cluster_bond_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
                              int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* Pl,
                              double* Pu, double* minB, double* log2z, void* ws, int64_t ws_bytes, void* stream);
+/* In-line two-point functions (tnac4o.calculate_correlation_function): a STACK of left environments of one row, E (nE, bl, Dt, Db).
+ * Slot 0 is the plain environment of tn_env3; every other slot has an operator inserted at an earlier cell.
+ *   tn_env3_stack: the left step of the whole stack through (At, Wops, Ab), Wops (1 + nop, bl, pd, br, pu) from
+ *   tn_mpo_from_factor_ops.  out (nE + nop, br, Dt2, Db2): slots 0 .. nE-1 are the input slots stepped through Wops[0], slot nE + a
+ *   is slot 0 stepped through Wops[1 + a] (nop = 0: pure propagation).  ALL slots are divided by the nfactor of slot 0 (a power of
+ *   two, so ratios between slots are untouched); *log2nf_out = *log2nf_in (0 when null) + its log2, as tn_env3.
+ *   half_out (may be null; nE, bl, pd, Dt2, Db): the first products HL of the input slots, what tn_stack_cell_law consumes.
+ *   The workspace query takes own_half = 1 when half_out is null (the first products then live in the workspace), else 0.
+ *   2 + min(br, pu) GEMM launches (3 + with nop > 0) whatever nE; no atomics, the result does not depend on the workspace.
+ *   tn_stack_cell_law: closes every slot at one cell with the right half-product HR (pu, br, Dt2, Db) of tn_env3 (K = Dt2 Db):
+ *   D (nE, q)[e,s] = sum_{l,u} F[s,l,u] X_e[l,dmap[s],u,rmap[s]],  X_e = HL[e] . HR^T.   Raw: no negativity rule, no division;
+ *   D[0,:] / sum(D[0,:]) is the cell law, sum(D[0,:]) the raw row total.  dmap / rmap entries out of range contribute 0.
+ * No counterpart in the reference. */
+int64_t tn_env3_stack_ws_bytes(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db,
+                               int64_t Db2, int own_half);
+int tn_env3_stack(const double* E, const double* At, const double* Wops, const double* Ab, int64_t nE, int64_t nop, int64_t Dt, int64_t pd,
+                  int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out,
+                  double* log2nf_out, double* half_out, void* ws, int64_t ws_bytes, void* stream);
+int64_t tn_stack_cell_law_ws_bytes(int64_t nE, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K);
+int tn_stack_cell_law(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nE,
+                      int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, double* D, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- measurement: bracket every launch of the selected kernel families with HIP events on the launch stream.
  * family ids: 0-3 gemm_kernel<128,128> / <128,32> / <32,128> / <64,64> (all operand layouts), 4 splitk_reduce,

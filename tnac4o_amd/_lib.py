@@ -51,6 +51,7 @@ SIGNATURES = {
     'tn_calc_pn': (_int, [_ptr] * 9 + [_i64] * 7 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     'tn_sample_pn': (_int, [_ptr] * 11 + [_i64, _ptr] + [_i64] * 6 + [_ptr, _ptr, _ptr, _ptr]),
     'tn_merge_groups': (_int, [_ptr] * 5 + [_i64, _f64, _ptr, _ptr, _ptr, _ptr]),
+    'tn_mpo_from_factor_ops': (_int, [_ptr] * 4 + [_i64] * 6 + [_ptr, _ptr]),
     'tn_nfactor_batched': (_int, [_ptr, _i64, _i64, _ptr]),
     'tn_env_rr_batched': (_int, [_ptr] * 5 + [_i64] * 7 + [_ptr, _ptr]),
     'tn_env_rl_batched': (_int, [_ptr] * 3 + [_i64] * 3 + [_ptr, _ptr]),
@@ -90,6 +91,10 @@ SIGNATURES = {
     'tn_cluster_marginal': (_int, [_ptr] * 5 + [_i64] * 6 + [_ptr] * 6 + [_i64, _ptr]),
     'tn_cluster_bond_marginal_ws_bytes': (_i64, [_i64] * 6),
     'tn_cluster_bond_marginal': (_int, [_ptr] * 5 + [_i64] * 6 + [_ptr] * 7 + [_i64, _ptr]),
+    'tn_env3_stack_ws_bytes': (_i64, [_i64] * 10 + [_int]),
+    'tn_env3_stack': (_int, [_ptr] * 4 + [_i64] * 10 + [_ptr] * 5 + [_i64, _ptr]),
+    'tn_stack_cell_law_ws_bytes': (_i64, [_i64] * 6),
+    'tn_stack_cell_law': (_int, [_ptr] * 5 + [_i64] * 7 + [_ptr, _ptr, _i64, _ptr]),
     'tn_profile_enable': (None, [C.c_uint]),
     'tn_profile_reset': (None, []),
     'tn_profile_sample': (None, [C.c_uint]),
@@ -187,6 +192,7 @@ SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes
                'tn_balance', 'tn_merge_groups', 'tn_svdvals_async', 'tn_rar', 'tn_rar_ws_bytes', 'tn_env_mix', 'tn_env_mix_ws_bytes',
                'tn_apply_truncation', 'tn_apply_truncation_ws_bytes', 'tn_site_qr_ws_bytes', 'tn_gram_weights', 'tn_argsort_desc', 'tn_weighted_sum', 'tn_rows_norm2', 'tn_gather_scale_rows', 'tn_peps_factor', 'tn_mpo_from_factor', 'tn_env3', 'tn_env3_ws_bytes',
                'tn_cluster_marginal', 'tn_cluster_marginal_ws_bytes', 'tn_cluster_bond_marginal', 'tn_cluster_bond_marginal_ws_bytes',
+               'tn_mpo_from_factor_ops', 'tn_env3_stack', 'tn_env3_stack_ws_bytes', 'tn_stack_cell_law', 'tn_stack_cell_law_ws_bytes',
                'tn_last_error')
 _lib = None
 ABI_VERSION = 13         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()

@@ -239,6 +239,12 @@ int tn_mpo_from_factor(const double* F, const int32_t* dmap, const int32_t* rmap
     ProfPhase ph(PH_BUILD);
     return mpo_from_factor(ST, F, dmap, rmap, q, nl, nu, pd, br, W);
 }
+int tn_mpo_from_factor_ops(const double* F, const int32_t* dmap, const int32_t* rmap, const double* O, int64_t nop, int64_t q, int64_t nl,
+                           int64_t nu, int64_t pd, int64_t br, double* Wops, void* stream) {
+    TN_CHECK_ARG(F && dmap && rmap && Wops, "null operand");
+    ProfPhase ph(PH_BUILD);
+    return mpo_from_factor_ops(ST, F, dmap, rmap, O, nop, q, nl, nu, pd, br, Wops);
+}
 int tn_nfactor_batched(double* x, int64_t batch, int64_t len, void* stream) {
     TN_CHECK_ARG(x, "null operand");
     return nfactor_batched(ST, x, batch, len);

@@ -337,6 +337,9 @@ int peps_factor(hipStream_t st, const double* Es, const double* E1, const double
                 const double* Xd, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nl, int64_t nu, double* F);
 int mpo_from_factor(hipStream_t st, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nl, int64_t nu, int64_t pd,
                     int64_t br, double* W);
+// Wops (1 + nop, nl, pd, br, nu): plane 0 = W, plane a = the same sum with F[s,l,u] weighted by O[a-1][s]  (O: nop x q)
+int mpo_from_factor_ops(hipStream_t st, const double* F, const int32_t* dmap, const int32_t* rmap, const double* O, int64_t nop, int64_t q,
+                        int64_t nl, int64_t nu, int64_t pd, int64_t br, double* Wops);
 
 // ---- site steps of the boundary-MPS sweeps (site.hip); layouts and formulas at the definitions ----------------------------------
 // attach (C != NULL) + QR + normalisation of one site.  side 0: Q (m x k), R (k x n) row-major; side 1: Q^T, R^T.  keff_host,

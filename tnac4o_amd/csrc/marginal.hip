@@ -330,6 +330,171 @@ int cluster_bond_marginal(hipStream_t st, const double* HL, const double* HR, co
     return 0;
 }
 
+// ---- in-line two-point functions: a stack of left environments (tnac4o.calculate_correlation_function) -----------------
+// A stack E (nE, bl, Dt, Db) holds the plain left environment in slot 0 and, in the others, left environments with an operator
+// inserted at an earlier cell.  One step carries all of them through the plain site Wops[0] and opens nop new slots, slot 0
+// through the operator-weighted sites Wops[1 .. nop] (tn_mpo_from_factor_ops).  The three products of the left step of env3:
+//   HL[(e,l)][(d,t'), b] = At^T . E[(e,l)]                          ONE launch, batch (e,l):  M = pd Dt2, N = Db, K = Dt
+//   Y [e][r][(t',b), u]  = HL[e]^T[(t',b),(l,d)] . W0[(l,d), r, u]
+//        r and u lie on both sides of (t',b) in Y (the last product needs (b,u) together) and the batch index is taken by e, so
+//        one of them is walked on the host: min(br, pu) launches, batch e, M = Dt2 Db, N = pu (or br), K = bl pd
+//   Y [nE+a][r]          = HL[0]^T . Wq[a][r]                       ONE launch, batch (a,r), after the op planes are permuted to
+//        Wq[a][r][(l,d)][u] (nop bl pd br pu doubles, the only copy): there the batch index is free, HL[0] is shared
+//   out[(e,r,t'), b']    = Y[(e,r,t'), (b,u)] . Ab[(b,u), b']        ONE launch:  M = (nE + nop) br Dt2, N = Db2, K = Db pu
+// Every slot is divided by the power-of-two nfactor of slot 0 (exact), whose log2 is added to the running total: ratios between
+// slots carry no factor.  No step depends on the number of slots through anything but the batch counts.
+struct Env3StackPlan {
+    int64_t half, y, wq;                  // doubles: first products, second products, permuted operator planes
+    int64_t g1, g2, g2o, g3;              // split-K scratch of the GEMMs
+    bool walk_u;                          // the middle product walks u (pu < br) instead of r
+};
+
+static Env3StackPlan env3_stack_plan(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu,
+                                     int64_t Db, int64_t Db2) {
+    Env3StackPlan p;
+    p.half = nE * bl * pd * Dt2 * Db;
+    p.y = (nE + nop) * br * Dt2 * Db * pu;
+    p.wq = nop * br * bl * pd * pu;
+    p.walk_u = pu < br;
+    p.g1 = gemm_ws_bytes(pd * Dt2, Db, Dt, nE * bl);
+    p.g2 = gemm_ws_bytes(Dt2 * Db, p.walk_u ? br : pu, bl * pd, nE);
+    p.g2o = nop > 0 ? gemm_ws_bytes(Dt2 * Db, pu, bl * pd, nop * br) : 0;
+    p.g3 = gemm_ws_bytes((nE + nop) * br * Dt2, Db2, Db * pu, 1);
+    return p;
+}
+
+static int64_t env3_stack_gemm_ws(const Env3StackPlan& p) {
+    int64_t g = p.g1 > p.g2 ? p.g1 : p.g2;
+    g = g > p.g2o ? g : p.g2o;
+    return g > p.g3 ? g : p.g3;
+}
+
+static int64_t env3_stack_ws(const Env3StackPlan& p, bool own_half) {
+    return (own_half ? up256m(p.half * 8) : 0) + up256m(p.y * 8) + up256m(p.wq * 8) + up256m(env3_stack_gemm_ws(p)) + NF_SCRATCH;
+}
+
+// Wops[1 + a][l][d][r][u] -> Wq[a][r][(l,d)][u]
+__global__ __launch_bounds__(256) void mpo_ops_by_r_kernel(const double* __restrict__ Wops, int64_t nop, int64_t nld, int br, int pu,
+                                                           double* __restrict__ Wq) {
+    const int64_t plane = nld * br * pu, n = nop * plane;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int64_t a = e / plane, rem = e - a * plane, ld = rem / (br * pu);
+        const int ru = (int)(rem - ld * br * pu), r = ru / pu, u = ru - r * pu;
+        Wq[((a * br + r) * nld + ld) * pu + u] = Wops[plane + e];
+    }
+}
+
+static bool stack_dims_ok(int64_t nE, int64_t nop) { return nE >= 1 && nop >= 0; }
+
+int64_t env3_stack_ws_bytes(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db,
+                            int64_t Db2, int own_half) {
+    if (!stack_dims_ok(nE, nop) || !dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2)) return 0;
+    return env3_stack_ws(env3_stack_plan(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2), own_half != 0);
+}
+
+int env3_stack(hipStream_t st, const double* E, const double* At, const double* Wops, const double* Ab, int64_t nE, int64_t nop, int64_t Dt,
+               int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out,
+               double* log2nf_out, double* half_out, void* ws, int64_t ws_bytes) {
+    TN_CHECK_ARG(E && At && Wops && Ab && out && log2nf_out && ws, "null operand");
+    TN_CHECK_ARG(stack_dims_ok(nE, nop), "the stack needs at least the plain slot and a non-negative operator count");
+    TN_CHECK_ARG(dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2), "non-positive dimension");
+    const Env3StackPlan p = env3_stack_plan(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2);
+    TN_CHECK_ARG(ws_bytes >= env3_stack_ws(p, half_out == nullptr), "workspace too small");
+    char* w = (char*)ws;
+    double* H = half_out;
+    if (!H) { H = (double*)w; w += up256m(p.half * 8); }
+    double* Y = (double*)w;
+    w += up256m(p.y * 8);
+    double* Wq = (double*)w;
+    w += up256m(p.wq * 8);
+    double* g = (double*)w;
+    w += up256m(env3_stack_gemm_ws(p));
+    double* nf2 = (double*)w;
+    void* scratch = w + 256;
+    const int64_t KD = Dt2 * Db, LD = bl * pd, slotY = br * KD * pu, slotO = br * Dt2 * Db2;
+    int rc;
+    // HL[(e,l)][(d,t'), b] = At^T[(d,t'), t] . E[(e,l)][t, b]
+    if ((rc = gemm(st, pd * Dt2, Db, Dt, 1.0, At, 1, pd * Dt2, E, Db, 1, 0.0, H, Db, 1, nE * bl, 0, Dt * Db, pd * KD, p.g1 > 0 ? g : nullptr,
+                   p.g1))) return rc;
+    // Y[e][r][(t',b), u] = HL[e]^T[(t',b), (l,d)] . W0[(l,d), r, u]
+    if (p.walk_u) {
+        for (int64_t u = 0; u < pu; ++u)
+            if ((rc = gemm(st, KD, br, LD, 1.0, H, 1, KD, Wops + u, br * pu, pu, 0.0, Y + u, pu, KD * pu, nE, LD * KD, 0, slotY,
+                           p.g2 > 0 ? g : nullptr, p.g2))) return rc;
+    } else {
+        for (int64_t r = 0; r < br; ++r)
+            if ((rc = gemm(st, KD, pu, LD, 1.0, H, 1, KD, Wops + r * pu, br * pu, 1, 0.0, Y + r * KD * pu, pu, 1, nE, LD * KD, 0, slotY,
+                           p.g2 > 0 ? g : nullptr, p.g2))) return rc;
+    }
+    if (nop > 0) {
+        int64_t nbk = cdiv(p.wq, 256);
+        if (nbk > 1024) nbk = 1024;
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(mpo_ops_by_r_kernel, dim3((unsigned)nbk), dim3(256), 0, st, Wops, nop, LD, (int)br, (int)pu, Wq));
+        TN_CHECK_LAUNCH("mpo_ops_by_r_kernel");
+        // Y[nE + a][r][(t',b), u] = HL[0]^T[(t',b), (l,d)] . Wq[a][r][(l,d), u]
+        if ((rc = gemm(st, KD, pu, LD, 1.0, H, 1, KD, Wq, pu, 1, 0.0, Y + nE * slotY, pu, 1, nop * br, 0, LD * pu, KD * pu,
+                       p.g2o > 0 ? g : nullptr, p.g2o))) return rc;
+    }
+    // out[(e,r,t'), b'] = Y[(e,r,t'), (b,u)] . Ab[(b,u), b']
+    if ((rc = gemm(st, (nE + nop) * br * Dt2, Db2, Db * pu, 1.0, Y, Db * pu, 1, Ab, Db2, 1, 0.0, out, Db2, 1, 1, 0, 0, 0, p.g3 > 0 ? g : nullptr,
+                   p.g3))) return rc;
+    if ((rc = normalize_pow2(st, out, slotO, nf2, scratch, 8192))) return rc;
+    if ((rc = scale_by(st, out + slotO, (nE + nop - 1) * slotO, nf2 + 1))) return rc;
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(log2_acc_kernel, dim3(1), dim3(64), 0, st, nf2, log2nf_in, log2nf_out));
+    TN_CHECK_LAUNCH("log2_acc_kernel");
+    return 0;
+}
+
+// ---- closing every slot of a stack at one cell -------------------------------------------------------------------------
+//   X[e][l,d,u,r] = sum_K HL[e][(l,d),K] HR[(u,r),K]                 ONE launch:  M = nE bl pd, N = pu br, K = Dt2 Db
+//   D[e][s] = sum_{l,u} F[s,l,u] X[e][l,dmap[s],u,rmap[s]]           raw: no negativity rule, no division
+// One wave per (slot, state), the four waves of a workgroup take four slots of one state (they share the row of F).  Lane i adds
+// the products i, i + 64, ... of the (l,u) plane in that order, then the lanes are added in a butterfly: the order of every sum
+// depends on bl pu alone.  X is read once in all (a chimera cell sends every (d,r) to one state), at the stride of its r index.
+__global__ __launch_bounds__(256) void stack_gather_kernel(const double* __restrict__ X, const double* __restrict__ F,
+                                                           const int32_t* __restrict__ dmap, const int32_t* __restrict__ rmap, int q, int nE,
+                                                           int nl, int pd, int br, int nu, double* __restrict__ D) {
+    const int s = blockIdx.x, lane = threadIdx.x & 63;
+    const int e = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (e >= nE) return;                                   // whole wave leaves together
+    const int d = dmap[s], r = rmap[s], nlu = nl * nu;
+    double acc = 0.0;
+    if (d >= 0 && d < pd && r >= 0 && r < br) {
+        const double* f = F + (int64_t)s * nlu;
+        const double* x = X + (int64_t)e * nl * pd * nu * br;
+        for (int i = lane; i < nlu; i += 64) {
+            const int l = i / nu, u = i - l * nu;
+            acc += f[i] * x[(((int64_t)l * pd + d) * nu + u) * br + r];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) D[(int64_t)e * q + s] = acc;
+}
+
+int64_t stack_cell_law_ws_bytes(int64_t nE, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
+    if (!dims_ok(nE, bl, pd, br, pu, K, 1, 1)) return 0;
+    return up256m(nE * bl * pd * pu * br * 8) + up256m(gemm_ws_bytes(nE * bl * pd, pu * br, K, 1));
+}
+
+int stack_cell_law(hipStream_t st, const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
+                   int64_t nE, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, double* D, void* ws, int64_t ws_bytes) {
+    TN_CHECK_ARG(HL && HR && F && dmap && rmap && D && ws, "null operand");
+    TN_CHECK_ARG(dims_ok(q, nE, bl, pd, br, pu, K, 1), "non-positive dimension");
+    TN_CHECK_ARG(q < (int64_t)1 << 31 && cdiv(nE, 4) <= 65535 && bl * pu < (int64_t)1 << 31, "too many states or slots for one launch");
+    TN_CHECK_ARG(ws_bytes >= stack_cell_law_ws_bytes(nE, bl, pd, br, pu, K), "workspace too small");
+    double* X = (double*)ws;
+    const int64_t gb = gemm_ws_bytes(nE * bl * pd, pu * br, K, 1);
+    double* g = (double*)((char*)ws + up256m(nE * bl * pd * pu * br * 8));
+    int rc;
+    // X[(e,l,d), (u,r)] = HL[(e,l,d), K] . HR[(u,r), K]^T
+    if ((rc = gemm(st, nE * bl * pd, pu * br, K, 1.0, HL, K, 1, HR, 1, K, 0.0, X, pu * br, 1, 1, 0, 0, 0, gb > 0 ? g : nullptr, gb))) return rc;
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(stack_gather_kernel, dim3((unsigned)q, (unsigned)cdiv(nE, 4)), dim3(256), 0, st, X, F, dmap,
+                                                     rmap, (int)q, (int)nE, (int)bl, (int)pd, (int)br, (int)pu, D));
+    TN_CHECK_LAUNCH("stack_gather_kernel");
+    return 0;
+}
+
 }  // namespace tn
 
 using namespace tn;
@@ -365,6 +530,27 @@ int tn_cluster_bond_marginal(const double* HL, const double* HR, const double* F
                              double* Pu, double* minB, double* log2z, void* ws, int64_t ws_bytes, void* stream) {
     return cluster_bond_marginal((hipStream_t)stream, HL, HR, F, dmap, rmap, q, bl, pd, br, pu, K, log2L, log2R, Pl, Pu, minB, log2z, ws,
                                  ws_bytes);
+}
+
+int64_t tn_env3_stack_ws_bytes(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db,
+                               int64_t Db2, int own_half) {
+    return env3_stack_ws_bytes(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2, own_half);
+}
+
+int tn_env3_stack(const double* E, const double* At, const double* Wops, const double* Ab, int64_t nE, int64_t nop, int64_t Dt, int64_t pd,
+                  int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out,
+                  double* log2nf_out, double* half_out, void* ws, int64_t ws_bytes, void* stream) {
+    return env3_stack((hipStream_t)stream, E, At, Wops, Ab, nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2, log2nf_in, out, log2nf_out, half_out, ws,
+                      ws_bytes);
+}
+
+int64_t tn_stack_cell_law_ws_bytes(int64_t nE, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
+    return stack_cell_law_ws_bytes(nE, bl, pd, br, pu, K);
+}
+
+int tn_stack_cell_law(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nE,
+                      int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, double* D, void* ws, int64_t ws_bytes, void* stream) {
+    return stack_cell_law((hipStream_t)stream, HL, HR, F, dmap, rmap, q, nE, bl, pd, br, pu, K, D, ws, ws_bytes);
 }
 
 }  // extern "C"

@@ -914,3 +914,63 @@ def cluster_bond_marginal(HL, HR, F, dmap, rmap, log2L=None, log2R=None):
                                          log2R.data_ptr() if log2R is not None else None, Pl.data_ptr(), Pu.data_ptr(), mB.data_ptr(),
                                          lz.data_ptr(), ws.data_ptr(), wsb, _stream()))
     return Pl, Pu, mB, lz
+
+
+# ---- in-line two-point functions: stacks of left environments (csrc/marginal.hip) -----------------------------------------
+def mpo_from_factor_ops(F, dmap, rmap, pd, br, O=None):
+    """Wops (1 + nop, bl, pd, br, pu): plane 0 the row-MPO site of mpo_from_factor (bit for bit), plane 1 + a the same sum with
+    the cell's states weighted by row a of O (nop, q) (tn_mpo_from_factor_ops).  O None: nop = 0."""
+    q, nl, nu = F.shape
+    nop = 0 if O is None else int(O.shape[0])
+    if nop:
+        _need_gpu(O)
+        assert O.is_contiguous() and tuple(O.shape) == (nop, q), (O.shape, q)
+    Wops = torch.empty((1 + nop, nl, pd, br, nu), dtype=torch.float64, device=F.device)
+    check(lib().tn_mpo_from_factor_ops(F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), O.data_ptr() if nop else None, nop, q, nl, nu, pd, br,
+                                       Wops.data_ptr(), _stream()))
+    return Wops
+
+
+def env3_stack(E, At, Wops, Ab, log2nf_in=None, keep_half=False):
+    """The left step of a stack of environments E (nE, bl, Dt, Db), slot 0 the plain one (tn_env3_stack).  Wops (1 + nop, bl, pd,
+    br, pu) from mpo_from_factor_ops.  Returns (out (nE + nop, br, Dt2, Db2), log2nf): the input slots stepped through Wops[0],
+    then slot 0 stepped through Wops[1 .. nop]; every slot divided by the nfactor of slot 0, whose log2 is added to log2nf_in.
+    With keep_half also the first products HL (nE, bl, pd, Dt2, Db) of the input slots, what stack_cell_law consumes."""
+    Dt, pd, Dt2 = At.shape
+    nw, bl, pd2, br, pu = Wops.shape
+    Db, pu2, Db2 = Ab.shape
+    nE, nop = int(E.shape[0]), nw - 1
+    assert pd2 == pd and pu2 == pu, (At.shape, Wops.shape, Ab.shape)
+    assert tuple(E.shape) == (nE, bl, Dt, Db) and nE >= 1, (E.shape, (bl, Dt, Db))
+    for t in (E, At, Wops, Ab):
+        _need_gpu(t)
+        assert t.is_contiguous()
+    dev = At.device
+    out = torch.empty((nE + nop, br, Dt2, Db2), dtype=torch.float64, device=dev)
+    lg = torch.empty(1, dtype=torch.float64, device=dev)
+    half = torch.empty((nE, bl, pd, Dt2, Db), dtype=torch.float64, device=dev) if keep_half else None
+    wsb = _ws_query('tn_env3_stack_ws_bytes', nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2, 0 if keep_half else 1)
+    ws = workspace(wsb, 1)
+    check(lib().tn_env3_stack(E.data_ptr(), At.data_ptr(), Wops.data_ptr(), Ab.data_ptr(), nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2,
+                              log2nf_in.data_ptr() if log2nf_in is not None else None, out.data_ptr(), lg.data_ptr(),
+                              half.data_ptr() if half is not None else None, ws.data_ptr(), wsb, _stream()))
+    return (out, lg, half) if keep_half else (out, lg)
+
+
+def stack_cell_law(HL, HR, F, dmap, rmap):
+    """Every slot of a stack closed at one cell (tn_stack_cell_law): HL (nE, bl, pd, Dt2, Db) from env3_stack, HR (pu, br, Dt2, Db)
+    from env3.  Returns D (nE, q), raw: D[e, s] = sum_{l,u} F[s,l,u] X_e[l, dmap[s], u, rmap[s]] with X_e = HL[e] . HR^T."""
+    nE, bl, pd, Dt2, Db = HL.shape
+    pu, br, Dt2b, Dbb = HR.shape
+    q, nl, nu = F.shape
+    assert (Dt2b, Dbb) == (Dt2, Db) and (nl, nu) == (bl, pu), (HL.shape, HR.shape, F.shape)
+    for t in (HL, HR, F, dmap, rmap):
+        assert t.is_contiguous() and t.is_cuda
+    assert dmap.dtype == torch.int32 and rmap.dtype == torch.int32 and dmap.numel() == q and rmap.numel() == q
+    D = torch.empty((nE, q), dtype=torch.float64, device=HL.device)
+    K = Dt2 * Db
+    wsb = _ws_query('tn_stack_cell_law_ws_bytes', nE, bl, pd, br, pu, K)
+    ws = workspace(wsb, 1)
+    check(lib().tn_stack_cell_law(HL.data_ptr(), HR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, nE, bl, pd, br, pu, K,
+                                  D.data_ptr(), ws.data_ptr(), wsb, _stream()))
+    return D

@@ -255,6 +255,66 @@ def model_correlations(Pl_rot, Pu_rot, order, Nx, Ny, J0=None, ind=None, ir=None
     return pairs, np.array([C[(int(i), int(j))] for i, j in pairs], dtype=np.float64)
 
 
+def model_line_correlations(tables, order, Nx, ind=None, Nc=None, Nx_model=None):
+    """Two-point functions along lattice lines in the model frame from tables of a (possibly rotated) lattice (host side of
+    calculate_correlation_function).  tables: {(c1, c2): M} for pairs of different cells c = ny*Nx + nx of the rotated lattice (row-major,
+    Nx columns) that share a row or a column there; model cell k sits at rotated cell order[k] and keeps its state encoding, so
+    rotated spin c*Nc + a is model spin order_i[c]*Nc + a.  The cell distance of a pair is the same in both frames.
+      Ising (ind, the rotated frame's active spins per cell, and Nc): M[a, b] = <sigma_i sigma_j> of i = ind[c1][a], j = ind[c2][b];
+      returns (line_pairs (n, 2) int64 of model spins i < j, sorted; line_distance (n,) int64; C (n,)).
+      RMF (ind None, Nx_model): M = P[s1, s2]; returns {(y1, x1, y2, x2): P} in model coordinates, the cell that comes first in
+      the model's row-major order first (M transposed where the rotation swaps the two)."""
+    order = np.asarray(order, dtype=np.int64)
+    order_i = np.empty_like(order)
+    order_i[order] = np.arange(order.size)
+
+    def distance(c1, c2):
+        (y1, x1), (y2, x2) = divmod(c1, Nx), divmod(c2, Nx)
+        if c1 == c2 or (y1 != y2 and x1 != x2):
+            raise ValueError('cells %d and %d of the rotated lattice are not two cells of one line' % (c1, c2))
+        return abs(y1 - y2) + abs(x1 - x2)
+
+    if ind is None:
+        out = {}
+        for (c1, c2), M in tables.items():
+            distance(c1, c2)
+            k1, k2 = int(order_i[c1]), int(order_i[c2])
+            M = np.asarray(M, dtype=np.float64)
+            if k1 > k2:
+                k1, k2, M = k2, k1, M.T
+            out[divmod(k1, Nx_model) + divmod(k2, Nx_model)] = np.ascontiguousarray(M)
+        return out
+    rows = []
+    for (c1, c2), M in tables.items():
+        dist = distance(c1, c2)
+        s1, s2 = np.asarray(ind[c1 // Nx][c1 % Nx], dtype=np.int64), np.asarray(ind[c2 // Nx][c2 % Nx], dtype=np.int64)
+        M = np.asarray(M, dtype=np.float64).reshape(s1.size, s2.size)
+        for a, i in enumerate(s1):
+            for b, j in enumerate(s2):
+                mi, mj = int(order_i[i // Nc]) * Nc + int(i % Nc), int(order_i[j // Nc]) * Nc + int(j % Nc)
+                rows.append((min(mi, mj), max(mi, mj), dist, float(M[a, b])))
+    rows.sort(key=lambda t: t[:2])
+    pairs = np.array([t[:2] for t in rows], dtype=np.int64).reshape(-1, 2)
+    return pairs, np.array([t[2] for t in rows], dtype=np.int64), np.array([t[3] for t in rows], dtype=np.float64)
+
+
+def _plan_line_groups(nops, reach, cap):
+    """Start cells 0 .. len(nops)-1 of one line cut into consecutive groups [(k0, k1)] so that a stack that carries the plain slot and
+    the nops[k] slots of the group's start cells k within `reach` cells back, the step's own insertions included, never holds more
+    than `cap` slots.  One (possibly empty) group at least.  MemoryError when one start cell alone does not fit."""
+    def peak(k0, k1):
+        return 1 + max(sum(nops[max(k0, m - reach):m + 1]) for m in range(k0, k1))
+    groups, k0 = [], 0
+    for k in range(len(nops)):
+        if 1 + nops[k] > cap:
+            raise MemoryError('the stack of one start cell has %d slots, the slot budget holds %d' % (1 + nops[k], max(int(cap), 0)))
+        if peak(k0, k + 1) > cap:
+            groups.append((k0, k))
+            k0 = k
+    groups.append((k0, len(nops)))
+    return groups
+
+
 def load(file_name):
     """Load a solution written by `tnac4o.save` -- by this package or by the reference (same .npy pickle of a dict,
     tnac4o.py:31-75).  Couplings are not stored, so the returned instance only carries the results (energy, states, ...)
@@ -1103,6 +1163,158 @@ class tnac4o:
         cell.  Returns (Pl list (q, bl), Pu list (q, pu), row-major over cells; minB (Ny*Nx,); log2 row contractions (Ny, Nx))."""
         Pl, Pu, minB, log2z = self._open_cell_pass(ops.cluster_bond_marginal)
         return Pl, Pu, np.concatenate(minB), np.concatenate(log2z).reshape(self.Ny, self.Nx)
+
+
+    # ------------------------------------------------------------------------------------ in-line two-point functions (GPU)
+    def calculate_correlation_function(self, max_distance=None, lines='both', Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20,
+                                       graduate_truncation=True, slot_budget=None):
+        """Two-point functions at the solver's beta between cells of one lattice row or column at every cell distance 1 ..
+        max_distance (None: the whole line), from both boundary MPS: an operator is inserted into the left environment of the row
+        network <rhoB[ny]| row ny |rhoT[ny+1]> at one cell, carried through ordinary environment steps and closed at another
+        (tn_env3_stack / tn_stack_cell_law, all carried environments in one stack): exact up to the truncation of the boundaries.
+        lines: 'rows' = pairs of cells in one row of the current frame, 'columns' = the same after rotate_graph(1), 'both'.
+        slot_budget: bytes the stack and its products may take (default: half of the free device memory); a smaller budget walks
+        the start cells in several left sweeps and changes the result by rounding only.
+          Ising: stores `line_pairs` (n, 2) int64, the model spins i < j (sorted) of every pair of active spins in two different cells of
+          one line within max_distance, `line_distance` (n,) their cell distance, `line_correlations` (n,) = <sigma_i sigma_j> with
+          sigma = +1 where binary_states writes 1 (returned), and `line_magnetization` (L,) from the same networks (0 for inactive
+          spins): the connected part is line_correlations - m[i] m[j].
+          RMF: stores and returns `line_pair_marginals`, {(y1, x1, y2, x2) in model coordinates, first cell first in row-major order:
+          P[s1, s2]}.
+        Both store `line_negative` (<= 0: RMF the smallest joint entry, Ising min(0, min(1 - |C|))) and `line_row_log2` (Ny, Nx), log2
+        of each row's contraction at every cell in the frame of the rows pass (of the columns pass for lines='columns').  Leaves the
+        frame, rotation, order, gauges, boundaries, search results and the outputs of the other thermal calls alone."""
+        if lines not in ('rows', 'columns', 'both'):
+            raise ValueError("lines must be 'rows', 'columns' or 'both'")
+        if max_distance is not None and (int(max_distance) != max_distance or max_distance < 1):
+            raise ValueError('max_distance must be a positive integer or None')
+        kw = _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps)
+        self.logger.info('Correlation functions with beta = %.2f', self.beta)
+        names = ('rhoT', 'rhoT_overlap', 'rhoT_discarded', 'rhoB', 'rhoB_overlap', 'rhoB_discarded', 'Xu', 'Xd', 'Xl', 'Xr', 'overlaps_ud')
+        saved = {k: getattr(self, k) for k in names if hasattr(self, k)}
+        ising = self.mode == 'Ising'
+        parts, law_frame = [], None
+        try:
+            for turned in ((True, False) if lines == 'both' else (lines == 'columns',)):       # columns first: rows end in the caller's frame
+                if turned:
+                    self.rotate_graph(1)
+                try:
+                    self._setup_rhoT(**kw)
+                    self._setup_rhoB(**kw)
+                    laws, joints, log2z = self._line_pass(max_distance, slot_budget)
+                    if ising:
+                        tables = {key: M @ self._line_operators(*divmod(key[1], self.Nx)).T for key, M in joints.items()}
+                        parts.append(model_line_correlations(tables, self.order, self.Nx, ind=self.ind, Nc=self.Nc))
+                    else:
+                        parts.append(model_line_correlations(joints, self.order, self.Nx, Nx_model=self.Nx_model))
+                    law_frame = (laws, self.order.copy(), log2z)
+                finally:
+                    if turned:
+                        self.rotate_graph(3)
+        finally:
+            for k in names:
+                if k in saved:
+                    setattr(self, k, saved[k])
+                elif hasattr(self, k):
+                    delattr(self, k)
+        laws, order, self.line_row_log2 = law_frame
+        if ising:
+            pairs = np.concatenate([p[0] for p in parts])
+            dist, C = np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
+            idx = np.lexsort((pairs[:, 1], pairs[:, 0]))
+            self.line_pairs, self.line_distance, self.line_correlations = pairs[idx], dist[idx], C[idx]
+            self.line_magnetization = model_marginals(laws, order, self.ind0, self.L)[1]
+            self.line_pair_marginals = None
+            self.line_negative = min(0.0, float(np.min(1.0 - np.abs(C)))) if C.size else 0.0
+            return self.line_correlations
+        self.line_pair_marginals = {}
+        for p in parts:
+            self.line_pair_marginals.update(p)
+        self.line_pairs = self.line_distance = self.line_correlations = self.line_magnetization = None
+        self.line_negative = min([0.0] + [float(P.min()) for P in self.line_pair_marginals.values()])
+        return self.line_pair_marginals
+
+    def _line_operators(self, ny, nx):
+        """Operator table O (nop, q) on the states of a cell of the rotated lattice: Ising one row sigma_a(s) per active spin (+1 where
+        binary_states writes 1), RMF the q state indicators (the closing then yields the joint law)."""
+        if self.mode == 'Ising':
+            return np.ascontiguousarray(_spins(self.sN[ny][nx]).T, dtype=np.float64)
+        return np.eye(int(self.N[ny][nx]))
+
+    def _line_slot_bytes(self, ny):
+        """Bytes one slot of the stack of row ny takes at its widest cell: the environment before and after the step, its two
+        products and the closing's X (what slot_budget is divided by)."""
+        need, bl = 0, 1
+        for nx in range(self.Nx):
+            (Dt, pd, Dt2), (Db, pu, Db2), br = self.rhoT[ny + 1].A[nx].shape, self.rhoB[ny].A[nx].shape, self._cell_maps(ny, nx)[3]
+            need = max(need, 8 * (bl * Dt * Db + br * Dt2 * Db2 + bl * pd * Dt2 * Db + br * Dt2 * Db * pu + bl * pd * pu * br))
+            bl = br
+        return need
+
+    def _line_pass(self, max_distance=None, slot_budget=None):
+        """Every row of the rotated lattice contracted between rhoB[ny] and rhoT[ny+1] as they stand, with an operator of one cell
+        inserted and another cell left open.  Per row: the right environments with their half-products as _open_cell_pass keeps
+        them, then the left sweep with a stack of environments (slot 0 plain): at every cell the stack is stepped (tn_env3_stack,
+        which opens one slot per operator of the cell), every carried slot is closed on the step's first products
+        (tn_stack_cell_law), and the slots whose start cell falls max_distance cells back are dropped.  slot_budget (bytes) caps the
+        stack: the start cells are cut into groups walked in successive left sweeps from the plain environments the first one
+        keeps.  One read-back per row.  Returns (laws, joints, log2z): laws[c] (q,) the law of cell c = ny*Nx + nx from slot 0,
+        joints {(c1, c2): (nop_c1, q_c2)} = <O_a(c1) [s_c2 = s]> for c1 left of c2 in a row, log2z (Ny, Nx) as _marginal_pass."""
+        Nx, Ny = self.Nx, self.Ny
+        reach = max(Nx - 1, 1) if max_distance is None else max(1, min(int(max_distance), Nx - 1))
+        if slot_budget is None:
+            slot_budget = torch.cuda.mem_get_info()[0] // 2
+        dev = self.rhoT[0].A[0].device
+        one = torch.ones((1, 1, 1, 1), dtype=torch.float64, device=dev)
+        zero = torch.zeros(1, dtype=torch.float64, device=dev)
+        laws, joints, log2z = [None] * (Nx * Ny), {}, np.zeros((Ny, Nx))
+        for ny in range(Ny):
+            fac = self._peps_factors_dev([(ny, nx) for nx in range(Nx)])
+            At = [a.contiguous() for a in self.rhoT[ny + 1].A]
+            Ab = [a.contiguous() for a in self.rhoB[ny].A]
+            ER, lgR, HR = one[0], zero, [None] * Nx
+            lgRs = [None] * (Nx + 1)
+            lgRs[Nx] = zero
+            for nx in range(Nx - 1, -1, -1):
+                F, dm, rm, pd, br = fac[nx]
+                ER, lgR, HR[nx] = ops.env3(1, ER, At[nx], ops.mpo_from_factor(F, dm, rm, pd, br), Ab[nx], lgR, keep_half=True)
+                lgRs[nx] = lgR
+            Os = [self._line_operators(ny, nx) for nx in range(Nx)]
+            nops = [int(O.shape[0]) for O in Os]
+            Od = [_dev_f64(O) if O.shape[0] else None for O in Os]
+            groups = _plan_line_groups(nops[:Nx - 1], reach, int(slot_budget) // self._line_slot_bytes(ny))
+            plain = [None] * (Nx + 1)
+            plain[0] = (one, zero)
+            recs = []
+            for g, (k0, k1) in enumerate(groups):
+                first = g == 0                                   # the first sweep runs to the end of the row and keeps the plain slots
+                start, stop = (0, Nx - 1) if first else (k0, min(Nx - 1, k1 - 1 + reach))
+                (E, lgL), starts = plain[start], []
+                for nx in range(start, stop + 1):
+                    F, dm, rm, pd, br = fac[nx]
+                    insert = k0 <= nx < k1 and nops[nx] > 0
+                    Wops = ops.mpo_from_factor_ops(F, dm, rm, pd, br, Od[nx] if insert else None)
+                    out, lg, HL = ops.env3_stack(E, At[nx], Wops, Ab[nx], lgL, keep_half=True)
+                    recs.append((nx, tuple(starts), first, ops.stack_cell_law(HL, HR[nx], F, dm, rm), lgL, lgRs[nx + 1]))
+                    if first:
+                        plain[nx + 1] = (out[:1].clone() if out.shape[0] > 1 else out, lg)
+                    if insert:
+                        starts.append(nx)
+                    gone = sum(nops[k] for k in starts if k < nx + 1 - reach)
+                    starts = [k for k in starts if k >= nx + 1 - reach]
+                    E, lgL = (out if gone == 0 else torch.cat([out[:1], out[1 + gone:]])), lg
+            host = _read_back([t for rec in recs for t in rec[3:]])
+            for i, (nx, starts, first, _, _, _) in enumerate(recs):
+                D, lgl, lgr = host[3 * i:3 * i + 3]
+                T = D[0].sum()
+                if first:
+                    laws[ny * Nx + nx] = D[0] / T
+                    log2z[ny, nx] = np.log2(T) + lgl[0] + lgr[0]
+                e = 1
+                for k in starts:
+                    joints[(ny * Nx + k, ny * Nx + nx)] = D[e:e + nops[k]] / T
+                    e += nops[k]
+        return laws, joints, log2z
 
     # ------------------------------------------------------------------------------------ output
     def binary_states(self, number=-1):
