@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 12 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 14 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -488,6 +488,23 @@ int64_t tn_gibbs_sample_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax
 int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const double* uniforms, int64_t ldu,
                     int16_t* states_out, double* energy_out, double* log2p_out, double* globalmin_host, int64_t* max_groups_host, void* ws,
                     int64_t ws_bytes, void* stream);
+
+/* ---- K9: weighted histogram of the pairwise distances of a set of packed rows (no counterpart in the reference: the overlap
+ * distribution of the samples, tnac4o.calculate_overlap_distribution) ---------------------------------------------------------------
+ * tn_pair_hist: rows (DEVICE) = M rows of uint64 words at a stride of ldr words.  lanes16 = 0: a row is nbits bits, bit i in word i / 64
+ * at position i % 64, nwords = ceil(nbits / 64), dist(a, b) = popcount(a XOR b).  lanes16 = 1: a row is nbits 16-bit lanes, four per
+ * word (lane i in word i / 4 at bits 16 (i % 4) ..), nwords = ceil(nbits / 4), dist = the number of lanes that differ.  Whatever lies
+ * beyond nbits in the last word is masked; the words nwords .. ldr-1 of a row are never read.  weights (DEVICE, M uint32; NULL = all 1).
+ * hist_out (DEVICE, 16-byte aligned, nbits + 1 bins of two uint64: lo, hi): hist_out[d] = sum_{a<b} w_a w_b [dist(a, b) = d] as the
+ * exact integer lo + 2^64 hi -- an integer function of the inputs, so bit-identical for every grid size, tile order and run (integer
+ * atomics with an exact carry inside a workgroup, one slab per workgroup in ws, summed with carry).  Every bin is written; M < 2 gives
+ * zeros.  ws: 16-byte aligned, tn_pair_hist_ws_bytes (which reads TN_PAIR_HIST_WGS as the call does; 0 for a shape the call refuses).
+ * Asynchronous on `stream`.  Limits: M < 2^31; nbits <= 9183 (the histogram at 16 bytes per bin and 16.5 KiB of staging must fit the
+ * 160 KiB of LDS).  Errors: -1 argument (M < 0, nbits out of range -- the message names the limit --, null rows / hist_out / ws,
+ * ldr < nwords), -3 workspace too small; both before any launch. */
+int64_t tn_pair_hist_ws_bytes(int64_t M, int64_t nbits, int lanes16);
+int tn_pair_hist(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, int lanes16, uint64_t* hist_out, void* ws,
+                 int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

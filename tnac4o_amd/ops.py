@@ -974,3 +974,29 @@ def stack_cell_law(HL, HR, F, dmap, rmap):
     check(lib().tn_stack_cell_law(HL.data_ptr(), HR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, nE, bl, pd, br, pu, K,
                                   D.data_ptr(), ws.data_ptr(), wsb, _stream()))
     return D
+
+
+def pair_hist(rows, nbits, weights=None, lanes16=False):
+    """Weighted histogram of the pairwise distances of packed rows (tn_pair_hist): rows (M, ld) int64 / uint64 device tensor whose
+    first ceil(nbits / 64) words (lanes16: ceil(nbits / 4)) hold a row of nbits bits (lanes16: nbits 16-bit lanes), layout of
+    tnac4o_amd/overlap.py; weights None (all 1) or (M,) uint32 values in an int32 / uint32 device tensor.  Returns the (nbits + 1, 2)
+    int64 device tensor of the limbs (lo, hi) of hist[d] = sum_{a<b} w_a w_b [dist(a, b) = d], exact integers (read them as unsigned)."""
+    if not rows.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % rows.device)
+    if rows.dim() != 2 or rows.element_size() != 8 or rows.is_floating_point() or rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise TypeError('rows: a 2-d tensor of 64-bit integer words with unit stride along a row')
+    M, ld = int(rows.shape[0]), int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    nbits = int(nbits)
+    nwords = -(-nbits // (4 if lanes16 else 64))
+    if rows.shape[1] < nwords:
+        raise ValueError('rows hold %d words, %d bits take %d' % (rows.shape[1], nbits, nwords))
+    if weights is not None:
+        if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous() or weights.numel() != M:
+            raise TypeError('weights: a contiguous device tensor of M 32-bit integers')
+    L = lib()
+    wsb = int(L.tn_pair_hist_ws_bytes(M, nbits, int(bool(lanes16))))        # (not cached: it follows TN_PAIR_HIST_WGS)
+    ws = workspace(max(wsb, 16), 1)
+    out = torch.empty((max(nbits, 0) + 1, 2), dtype=torch.int64, device=rows.device)
+    check(L.tn_pair_hist(rows.data_ptr() if M else ws.data_ptr(), M, nbits, max(ld, nwords), weights.data_ptr() if weights is not None else None,
+                         int(bool(lanes16)), out.data_ptr(), ws.data_ptr(), wsb, _stream()))
+    return out

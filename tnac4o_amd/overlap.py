@@ -1,0 +1,237 @@
+"""Replica-overlap distributions of a set of configurations (host side of tnac4o.calculate_overlap_distribution).
+
+Plain numpy, importable without a GPU; the only device work is the pair histogram tn_pair_hist (ops.pair_hist), which the driver at the
+end of this module calls once.  Row layouts of the library: a row of n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at
+position i % 64; a row of n 16-bit lanes is ceil(n / 4) words, lane i in word i // 4 at bits 16 (i % 4) .. 16 (i % 4) + 15."""
+import numpy as np
+
+MAX_NBITS = 9183                 # largest row tn_pair_hist takes: 16 bytes per bin and the staging in 160 KiB of LDS (include/tnpeps.h)
+WMAX = 2 ** 32 - 1               # weights of tn_pair_hist are uint32
+KINDS = ('spin', 'link', 'cell')
+
+
+# ---------------------------------------------------------------------------------------------- packing
+def pack_bits(bits):
+    """(M, n) array of 0 / 1 -> (M, ceil(n / 64)) uint64."""
+    bits = np.asarray(bits)
+    if bits.ndim != 2:
+        raise ValueError('bits must be a 2-d array')
+    if bits.size and not np.all((bits == 0) | (bits == 1)):
+        raise ValueError('bits must be 0 or 1')
+    M, n = bits.shape
+    nwords = -(-n // 64)
+    by = np.zeros((M, nwords * 8), dtype=np.uint8)
+    if n:
+        pk = np.packbits(bits.astype(np.uint8), axis=1, bitorder='little')
+        by[:, :pk.shape[1]] = pk
+    return np.ascontiguousarray(by).view('<u8').astype(np.uint64, copy=False)
+
+
+def pack_lanes16(states):
+    """(M, n) array of cell states in [0, 32768) -> (M, ceil(n / 4)) uint64, four 16-bit lanes per word."""
+    states = np.asarray(states)
+    if states.ndim != 2:
+        raise ValueError('states must be a 2-d array')
+    if states.size and (states.min() < 0 or states.max() >= 32768):
+        raise ValueError('cell states must lie in [0, 32768)')
+    M, n = states.shape
+    nwords = -(-n // 4)
+    la = np.zeros((M, nwords * 4), dtype='<u2')
+    la[:, :n] = states
+    return np.ascontiguousarray(la).view('<u8').astype(np.uint64, copy=False)
+
+
+def link_pairs(J0):
+    """The couplings of an Ising model: every i < j with off-diagonal J0[i, j] != 0, sorted -- the bond_pairs of model_correlations."""
+    return np.argwhere(np.triu(np.asarray(J0), 1) != 0).astype(np.int64)
+
+
+def _ising(solver, what):
+    if solver.mode != 'Ising':
+        raise ValueError("%s is defined for mode 'Ising' only" % what)
+
+
+def spin_bits(solver):
+    """binary_states() of solver.states restricted to the active spins, in model order: (M, solver.active) of 0 / 1.  Ising only."""
+    _ising(solver, 'spin_bits')
+    act = np.sort(np.concatenate([np.asarray(a, dtype=np.int64) for row in solver.ind0 for a in row] + [np.zeros(0, dtype=np.int64)]))
+    return solver.binary_states()[:, act].astype(np.uint8)
+
+
+def link_bits(solver):
+    """One bit per coupling of solver.states, [s_i == s_j], couplings in the order of link_pairs(solver.J0); from J0 alone.  Ising only."""
+    _ising(solver, 'link_bits')
+    pairs = link_pairs(solver.J0)
+    b = solver.binary_states()
+    return (b[:, pairs[:, 0]] == b[:, pairs[:, 1]]).astype(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------- estimator
+def condense(rows, w):
+    """Distinct rows with their aggregated weights.  rows (M, nwords) uint64, w (M,) -> (urows (K, nwords), W (K,) summed weights,
+    D0): D0 = sum_c (W_c^2 - S_c) / 2 with S_c the summed squared weights is the weight of the pairs of DISTINCT samples that carry
+    the SAME row: they have distance 0 and belong to bin 0.  float64 throughout.  The pair histogram of all M rows equals the one of
+    the K distinct rows with weights W plus D0 in bin 0; at low temperature, where one row carries most of the weight, this keeps
+    those pairs off a single word of the device histogram."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    w = np.asarray(w, dtype=np.float64)
+    if rows.ndim != 2 or w.shape != (rows.shape[0],):
+        raise ValueError('rows (M, nwords) and w (M,) expected')
+    if rows.shape[0] == 0:
+        return rows, w, 0.0
+    if rows.shape[1] == 0:
+        urows, inv = rows[:1], np.zeros(rows.shape[0], dtype=np.int64)
+    else:
+        urows, inv = np.unique(rows, axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    W = np.bincount(inv, weights=w, minlength=urows.shape[0])
+    S = np.bincount(inv, weights=w * w, minlength=urows.shape[0])
+    return urows, W, float(np.sum(W * W - S) / 2.0)
+
+
+def quantise(W):
+    """Weights as the uint32 tn_pair_hist takes: (wq (K,) uint32, keep (K,) bool, scale) with wq = rint(scale * W).  Integer W up to
+    2^32 - 1 (the multiplicities under uniform weights) pass through with scale 1: the device result is then the exact pair count.
+    Otherwise two scales are tried, (2^32 - 1) / max W and the largest power of two below it, and the one with the smaller total
+    rounding error sum |wq / scale - W| is taken.  The first puts every weight within half a unit, 2^-33 of the largest, so the
+    total is at most K 2^-33 max W with either.  The second is exact for weights that are multiples of a common power of two up to
+    rounding -- multiplicities of nearly equal importance weights -- where the first would shift every row of one multiplicity by
+    the same amount.  keep marks the rows with wq > 0; the others are to be dropped."""
+    W = np.asarray(W, dtype=np.float64)
+    if W.size == 0:
+        return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=bool), 1.0
+    if np.all(W == np.rint(W)) and W.max() <= WMAX:
+        wq, scale = W, 1.0
+    else:
+        full = WMAX / float(W.max())
+        best = None
+        for sc in (full, 2.0 ** np.floor(np.log2(full))):
+            q = np.minimum(np.rint(W * sc), WMAX)
+            err = float(np.sum(np.abs(q / sc - W)))
+            if best is None or err < best[0]:
+                best = (err, q, sc)
+        _, wq, scale = best
+    wq = wq.astype(np.uint32)
+    return wq, wq > 0, float(scale)
+
+
+def limbs_to_int(hist_limbs):
+    """(nbins, 2) limbs (lo, hi; any integer dtype, read as unsigned 64-bit) -> list of Python ints lo + 2^64 hi."""
+    h = np.asarray(hist_limbs)
+    if h.dtype != object:
+        h = np.ascontiguousarray(h).astype(np.int64, copy=False).view(np.uint64)
+    return [int(lo) + (int(hi) << 64) for lo, hi in h]
+
+
+def distribution(hist_limbs, scale, D0):
+    """P over the bins, float64, normalised to 1: (hist / scale^2 + D0 [d = 0]) / total, hist the integers of the device histogram of
+    the condensed rows, D0 the self term of condense in units of the unquantised weights."""
+    H = np.array([float(v) for v in limbs_to_int(hist_limbs)], dtype=np.float64) / (float(scale) * float(scale))
+    H[0] += D0
+    total = H.sum()
+    if not total > 0:
+        raise ValueError('no pair of distinct samples carries weight')
+    return H / total
+
+
+def moments(values, P):
+    """<q>, <|q|>, <q^2>, <q^4> and the Binder ratio (3 - <q^4> / <q^2>^2) / 2 of the distribution P over `values`."""
+    q, P = np.asarray(values, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    q2, q4 = float(P @ q ** 2), float(P @ q ** 4)
+    return {'q': float(P @ q), 'abs_q': float(P @ np.abs(q)), 'q2': q2, 'q4': q4, 'binder': 0.5 * (3.0 - q4 / (q2 * q2)) if q2 > 0 else float('nan')}
+
+
+def effective_sample_size(w):
+    """(sum w)^2 / sum w^2 of the raw weights."""
+    w = np.asarray(w, dtype=np.float64)
+    return float(w.sum() ** 2 / np.sum(w * w))
+
+
+def overlap_values(kind, n):
+    """The overlap at distance d = 0 .. n: 1 - 2 d / n for 'spin' and 'link', the fraction of equal cells 1 - d / n for 'cell'."""
+    d = np.arange(n + 1, dtype=np.float64)
+    return 1.0 - (1.0 if kind == 'cell' else 2.0) * d / n
+
+
+# ---------------------------------------------------------------------------------------------- driver
+def check_arguments(solver, kind, weights):
+    """Everything calculate_overlap_distribution can refuse before any device work.  Returns (kind, w (M,) float64)."""
+    if kind is None:
+        kind = 'spin' if solver.mode == 'Ising' else 'cell'
+    if kind not in KINDS:
+        raise ValueError("kind must be 'spin', 'link', 'cell' or None")
+    if kind != 'cell' and solver.mode != 'Ising':
+        raise ValueError("kind '%s' is defined for mode 'Ising' only" % kind)
+    M = int(np.asarray(solver.states).shape[0])
+    if M < 2:
+        raise ValueError('calculate_overlap_distribution needs at least two stored states (run sample_boltzmann, gibbs_sampling, a search or '
+                         'decode_low_energy_states first)')
+    if isinstance(weights, str):
+        if weights == 'uniform':
+            w = np.ones(M)
+        elif weights == 'importance':
+            lz = getattr(solver, 'sample_log2Z', None)
+            if lz is None or np.asarray(lz).shape != (M,):
+                raise ValueError("weights='importance' needs sample_log2Z of the stored states: run sample_boltzmann first")
+            lz = np.asarray(lz, dtype=np.float64)
+            if not np.all(np.isfinite(lz)):
+                raise ValueError('sample_log2Z is not finite')
+            w = np.exp2(lz - lz.max())
+        else:
+            raise ValueError("weights must be 'uniform', 'importance' or an array of length M")
+    else:
+        try:
+            w = np.array(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('weights must be numbers') from None
+        if w.shape != (M,):
+            raise ValueError('weights must have length %d, the number of stored states' % M)
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError('weights must be non-negative and finite')
+        if not w.max() > 0:
+            raise ValueError('all weights are zero')
+    return kind, w
+
+
+def rows_of(solver, kind):
+    """(packed rows (M, nwords) uint64, n, lanes16) of solver.states for a kind."""
+    if kind == 'cell':
+        st = np.asarray(solver.states)
+        if st.dtype.kind == 'i' and st.dtype.itemsize < 8:           # the solver keeps 256 states of a cell in int8: read them as unsigned
+            st = st.view('u%d' % st.dtype.itemsize)
+        return pack_lanes16(st), int(st.shape[1]), True
+    bits = spin_bits(solver) if kind == 'spin' else link_bits(solver)
+    return pack_bits(bits), int(bits.shape[1]), False
+
+
+def overlap_distribution(solver, kind=None, weights='uniform'):
+    """calculate_overlap_distribution of tnac4o (documented there)."""
+    kind, w = check_arguments(solver, kind, weights)
+    rows, n, lanes16 = rows_of(solver, kind)
+    if n < 1:
+        raise ValueError("kind '%s': the model has nothing to compare" % kind)
+    if n > MAX_NBITS:
+        raise NotImplementedError("kind '%s' compares %d %s per state; tn_pair_hist takes at most %d (its histogram must fit the 160 KiB of "
+                                  'LDS); there is no host fallback' % (kind, n, 'cells' if lanes16 else 'bits', MAX_NBITS))
+    import torch
+    from . import ops
+    M = rows.shape[0]
+    urows, W, D0 = condense(rows, w)
+    wq, keep, scale = quantise(W)
+    urows, wq = np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep])
+    if urows.shape[0] >= 2:
+        d_rows = torch.as_tensor(urows.view(np.int64)).cuda()
+        d_w = None if np.all(wq == 1) else torch.as_tensor(wq.view(np.int32)).cuda()
+        limbs = ops.pair_hist(d_rows, n, d_w, lanes16).cpu().numpy()
+    else:                                            # one distinct row: every pair sits in D0
+        limbs = np.zeros((n + 1, 2), dtype=np.int64)
+    P = distribution(limbs, scale, D0)
+    solver.overlap_kind = kind
+    solver.overlap_values = overlap_values(kind, n)
+    solver.overlap_distribution = P
+    solver.overlap_moments = moments(solver.overlap_values, P)
+    if kind == 'spin':
+        solver.overlap_moments['chi_sg'] = n * solver.overlap_moments['q2']
+    solver.overlap_ess = effective_sample_size(w)
+    solver.overlap_pairs = M * (M - 1) // 2
+    return P

@@ -1316,6 +1316,25 @@ class tnac4o:
                     e += nops[k]
         return laws, joints, log2z
 
+    # ------------------------------------------------------------------------------------ overlap distributions of the stored states (GPU)
+    def calculate_overlap_distribution(self, kind=None, weights='uniform'):
+        """Distribution of the overlap between two replicas, estimated from all pairs of distinct rows of `states`, whatever wrote
+        them (sample_boltzmann, gibbs_sampling, search_ground_state, decode_low_energy_states): P(q) = sum_{a<b} w_a w_b
+        [q_ab = q] / sum_{a<b} w_a w_b, the pair histogram on the device in exact integers (tn_pair_hist; tnac4o_amd/overlap.py).
+        kind: 'spin' q = 1 - 2 d / N over the N active spins (d = Hamming distance); 'link' q_l = 1 - 2 d / N_b over the N_b
+        couplings (every i < j with J0[i, j] != 0, one bit [s_i == s_j] each); 'cell' the fraction of cells in the same state,
+        1 - d / (Nx Ny).  None = 'spin' for Ising, 'cell' for RMF; 'spin' and 'link' on RMF are a ValueError.
+        weights: 'uniform'; 'importance' w_k = 2^(sample_log2Z_k - max), the self-normalised correction for a truncated contraction
+        -- meaningful after sample_boltzmann only, a ValueError unless sample_log2Z exists with the length of `states`; or M
+        non-negative finite numbers.  Anything else, and fewer than two states, is a ValueError raised before any device work.
+        Stores overlap_values (nbins,), overlap_distribution (nbins,) (returned; bin d belongs to overlap_values[d]), overlap_moments
+        {'q', 'abs_q', 'q2', 'q4', 'binder' = (3 - <q^4> / <q^2>^2) / 2, and for 'spin' 'chi_sg' = N <q^2>}, overlap_ess =
+        (sum w)^2 / sum w^2, overlap_pairs = M (M - 1) / 2 and overlap_kind.  Under uniform weights the device part is the exact
+        pair count; other weights are rounded to 32 bits of the largest.  More than 9183 bits (cells) per state do not fit the
+        kernel's histogram: NotImplementedError naming the limit, there is no host fallback.  Changes nothing else."""
+        from . import overlap
+        return overlap.overlap_distribution(self, kind, weights)
+
     # ------------------------------------------------------------------------------------ output
     def binary_states(self, number=-1):
         """Bit strings: 1 spin up, 0 spin down, 2 inactive (tnac4o.py:261-288)."""
