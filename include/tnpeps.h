@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 14 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 15 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -212,6 +212,18 @@ int tn_sample_pn(const double* T1, const double* RR, const double* F, const int3
                  const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
                  const double* uniforms, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child_out,
                  double* log2p_inout, double* minP_out, void* stream);
+/* ---- K8f: the forced twin of tn_sample_pn: every sample brings the state of its next cell instead of a uniform number, and gets the
+ * log2 of the conditional probability of that state.  Groups, table (built exactly as tn_calc_pn builds it: same bits) and minP_out as
+ * tn_sample_pn; no running sum is formed and nothing is searched.
+ *   forced (int16, DEVICE), ld, pos               the state of sample k is s = forced[k * ld + pos], 0 <= pos < ld
+ * Out, per sample k: child_out[k] (int32) = s; log2p_inout[k] += log2 P[s]; cell_log2p (may be NULL) [k * ld + pos] = that increment.
+ * An entry P[s] that is not positive gives the increment -inf, never NaN, and every later finite increment leaves the sum -inf.  A state
+ * outside [0, q) is never used as an index: its increment is -inf and child_out[k] = 0.  Limits (argument error otherwise):
+ * tn_calc_pn's, (p Dr + Dr br + p br + q) * 8 <= 150 KiB of LDS. */
+int tn_score_pn(const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+                const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
+                const int16_t* forced, int64_t ld, int64_t pos, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br,
+                int32_t* child_out, double* log2p_inout, double* cell_log2p, double* minP_out, void* stream);
 /* ---- a12: merge of the branches of a site-step with identical boundary indices (tnac4o.py:481-509).  The candidates arrive sorted by
  * group, in candidate order inside a group: E, log2p, deg, pos (their position in the candidate list), group g = members starts[g] ..
  * starts[g+1]-1 (ngroups + 1 offsets).  Per group: rep_pos_out = position of the FIRST member of minimal energy, deg_out = sum of the
@@ -488,6 +500,19 @@ int64_t tn_gibbs_sample_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax
 int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const double* uniforms, int64_t ldu,
                     int16_t* states_out, double* energy_out, double* log2p_out, double* globalmin_host, int64_t* max_groups_host, void* ws,
                     int64_t ws_bytes, void* stream);
+/* tn_gibbs_score: the same walk along GIVEN configurations -- the draw of every site-step replaced by tn_score_pn on the caller's
+ * states (DEVICE, M x Nx*Ny int16, lattice order of this rotation; they are only read).  Row keys, grouping, energies (same order of
+ * additions), environments and workspace layout are tn_gibbs_sample's own code, so a configuration that tn_gibbs_sample drew comes back
+ * with the log2p_out and energy_out it was drawn with, bit for bit, whatever other configurations share the call.
+ * Results (DEVICE): energy_out (M), log2p_out (M) = log2 q(x), the sum of the log2 conditional probabilities of the cells;
+ * cell_log2p_out (may be NULL; M x Nx*Ny) those increments, every entry written.  A cell state whose table entry is not positive, or
+ * that lies outside [0, q) of its cell, makes log2 q(x) = -inf (never NaN); the latter is walked on as state 0.
+ * HOST: *globalmin_host, *max_groups_host (may be NULL) as tn_gibbs_sample.  Memory, synchronisations and limits as tn_gibbs_sample,
+ * with tn_score_pn's LDS bound (tn_calc_pn's) at every cell.  Errors: -1 argument, -3 workspace too small; both before any launch. */
+int64_t tn_gibbs_score_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax, int64_t max_env, int64_t max_t1, int64_t max_w);
+int tn_gibbs_score(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const int16_t* states, double* energy_out,
+                   double* log2p_out, double* cell_log2p_out, double* globalmin_host, int64_t* max_groups_host, void* ws, int64_t ws_bytes,
+                   void* stream);
 
 /* ---- K9: weighted histogram of the pairwise distances of a set of packed rows (no counterpart in the reference: the overlap
  * distribution of the samples, tnac4o.calculate_overlap_distribution) ---------------------------------------------------------------

@@ -50,6 +50,7 @@ SIGNATURES = {
     'tn_scale_phys': (_int, [_ptr, _i64, _i64, _i64, _ptr, _int, _ptr]),
     'tn_calc_pn': (_int, [_ptr] * 9 + [_i64] * 7 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     'tn_sample_pn': (_int, [_ptr] * 11 + [_i64, _ptr] + [_i64] * 6 + [_ptr, _ptr, _ptr, _ptr]),
+    'tn_score_pn': (_int, [_ptr] * 11 + [_i64, _ptr] + [_i64] * 8 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     'tn_merge_groups': (_int, [_ptr] * 5 + [_i64, _f64, _ptr, _ptr, _ptr, _ptr]),
     'tn_mpo_from_factor_ops': (_int, [_ptr] * 4 + [_i64] * 6 + [_ptr, _ptr]),
     'tn_nfactor_batched': (_int, [_ptr, _i64, _i64, _ptr]),
@@ -85,6 +86,8 @@ SIGNATURES = {
                             C.POINTER(_f64), _ptr, _i64, _ptr, _int, _int, _ptr, _ptr]),
     'tn_gibbs_sample_ws_bytes': (_i64, [_i64] * 7),
     'tn_gibbs_sample': (_int, [_i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, C.POINTER(_f64), C.POINTER(_i64), _ptr, _i64, _ptr]),
+    'tn_gibbs_score_ws_bytes': (_i64, [_i64] * 7),
+    'tn_gibbs_score': (_int, [_i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, C.POINTER(_f64), C.POINTER(_i64), _ptr, _i64, _ptr]),
     'tn_env3_ws_bytes': (_i64, [_int] + [_i64] * 8),
     'tn_env3': (_int, [_int] + [_ptr] * 4 + [_i64] * 8 + [_ptr] * 5 + [_i64, _ptr]),
     'tn_cluster_marginal_ws_bytes': (_i64, [_i64] * 5),
@@ -190,14 +193,14 @@ def _stale(L):
 
 # short, non-blocking entry points (see lib())
 SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes', 'tn_absorb', 'tn_nfactor', 'tn_scale_by',
-               'tn_normalize_pow2', 'tn_scale_phys', 'tn_calc_pn', 'tn_sample_pn', 'tn_nfactor_batched', 'tn_env_rr_batched', 'tn_env_rl_batched',
+               'tn_normalize_pow2', 'tn_scale_phys', 'tn_calc_pn', 'tn_sample_pn', 'tn_score_pn', 'tn_nfactor_batched', 'tn_env_rr_batched', 'tn_env_rl_batched',
                'tn_balance', 'tn_merge_groups', 'tn_svdvals_async', 'tn_rar', 'tn_rar_ws_bytes', 'tn_env_mix', 'tn_env_mix_ws_bytes',
                'tn_apply_truncation', 'tn_apply_truncation_ws_bytes', 'tn_site_qr_ws_bytes', 'tn_gram_weights', 'tn_argsort_desc', 'tn_weighted_sum', 'tn_rows_norm2', 'tn_gather_scale_rows', 'tn_peps_factor', 'tn_mpo_from_factor', 'tn_env3', 'tn_env3_ws_bytes',
                'tn_cluster_marginal', 'tn_cluster_marginal_ws_bytes', 'tn_cluster_bond_marginal', 'tn_cluster_bond_marginal_ws_bytes',
                'tn_mpo_from_factor_ops', 'tn_env3_stack', 'tn_env3_stack_ws_bytes', 'tn_stack_cell_law', 'tn_stack_cell_law_ws_bytes',
                'tn_last_error')
 _lib = None
-ABI_VERSION = 14         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
+ABI_VERSION = 15         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
 
 
 def lib():

@@ -322,6 +322,12 @@ int calc_pn(hipStream_t st, const double* T1, const double* RR, const double* F,
 int sample_pn(hipStream_t st, const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
               const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
               const double* uniforms, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child, double* log2p, double* minP);
+// the forced twin of sample_pn: member k takes its state s = forced[k * ld + pos] (int16) from the caller; child[k] = s, log2p[k] += log2 P[s],
+// cell_log2p (may be null) [k * ld + pos] = that increment.  P[s] <= 0 or s outside [0, q): the increment is -inf (and child = 0 for the latter)
+int score_pn(hipStream_t st, const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+             const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
+             const int16_t* forced, int64_t ld, int64_t pos, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child,
+             double* log2p, double* cell_log2p, double* minP);
 // merges the branches of each of ng groups (starts: ng + 1 offsets) that lie within min_dEng of the group's lowest energy
 int merge_groups(hipStream_t st, const double* E, const double* lp, const int64_t* deg, const int64_t* pos, const int64_t* starts, int64_t ng,
                  double min_dEng, int64_t* rep_pos, int64_t* degn, double* lpn);

@@ -8,8 +8,12 @@
 // call.  Draw rule = np.searchsorted(cum, r), side 'left' (tnac4o.py:616-622), with two edge rules: a landing on a zero entry moves
 // forward to the next positive one, and r above cum[q-1] (the sum may end an ulp below 1) takes the last positive one.
 //
-// tn_gibbs_sample: the walk over rows and sites on one stream, samples keep their slot (no cut, no merge, no selection), on the
-// scaffolding it shares with the beam search (walk.h).  Two count read-backs per site-step, none of size M.
+// score_pn: the same workgroup per distinct boundary row and the same table, but every member brings its state instead of a uniform
+// number: no running sum, no search; the increment log2 P[s] is -inf where P[s] is not positive or s lies outside [0, q).
+//
+// tn_gibbs_sample / tn_gibbs_score: the walk over rows and sites on one stream (gibbs_walk), samples keep their slot (no cut, no merge,
+// no selection), on the scaffolding it shares with the beam search (walk.h).  The two entries differ in the draw step alone.  Two
+// count read-backs per site-step, none of size M.
 #include "walk.h"
 #include "devprim.h"
 #include "pn.h"
@@ -78,6 +82,39 @@ __global__ __launch_bounds__(256) void sample_pn_kernel(const double* __restrict
     }
 }
 
+// the forced twin of sample_pn_kernel: member k of the row takes its state from forced[k * ld + pos].  A state outside [0, q) never
+// indexes the table: it scores -inf and walks on as state 0.  log2p[k] += -inf stays -inf under every later finite increment.
+__global__ __launch_bounds__(256) void score_pn_kernel(const double* __restrict__ T1, const double* __restrict__ RR, const double* __restrict__ F,
+                                                       const int32_t* __restrict__ dmap, const int32_t* __restrict__ rmap,
+                                                       const int32_t* __restrict__ pref, const int32_t* __restrict__ suf,
+                                                       const int32_t* __restrict__ lidx, const int32_t* __restrict__ uidx,
+                                                       const int32_t* __restrict__ perm, const int64_t* __restrict__ starts,
+                                                       const int16_t* __restrict__ forced, int64_t ld, int64_t pos, int q, int nl, int nu, int p, int Dr,
+                                                       int br, int32_t* __restrict__ child, double* __restrict__ log2p, double* __restrict__ cell_log2p,
+                                                       double* __restrict__ minP) {
+    extern __shared__ double lds[];
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const int64_t g = blockIdx.x;
+    double* sP = lds + pn_front_doubles(p, Dr, br);    // [q]
+    const double mPn = pn_table(T1 + (int64_t)pref[g] * p * Dr, RR + (int64_t)suf[g] * Dr * br, F, dmap, rmap, lidx[g], uidx[g], q, nl, nu, p, Dr, br, lds,
+                                sP, red);
+    if (tid == 0) minP[g] = mPn;
+    __syncthreads();
+    const int64_t lo = starts[g], hi = starts[g + 1];
+    for (int64_t m = lo + tid; m < hi; m += 256) {
+        const int32_t k = perm[m];
+        int s = forced[k * ld + pos];
+        const bool inside = s >= 0 && s < q;
+        if (!inside) s = 0;
+        const double v = sP[s];
+        const double inc = (inside && v > 0.0) ? log2(v) : -std::numeric_limits<double>::infinity();
+        child[k] = s;
+        log2p[k] += inc;
+        if (cell_log2p) cell_log2p[k * ld + pos] = inc;
+    }
+}
+
 // row keys of the samples (prefix rank, left index, up index, suffix rank): equal keys = equal boundary rows at this site
 __global__ __launch_bounds__(256) void row_key_kernel(const int32_t* pref, const int32_t* lcol, const int32_t* ucol, const int32_t* suf, int64_t B,
                                                      int64_t nsuf, int64_t n, int64_t* key) {
@@ -132,25 +169,26 @@ int sample_pn(hipStream_t st, const double* T1, const double* RR, const double* 
     return 0;
 }
 
-}  // namespace tn
-
-using namespace tn;
-
-extern "C" {
-
-int tn_sample_pn(const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
-                 const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
-                 const double* uniforms, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child_out,
-                 double* log2p_inout, double* minP_out, void* stream) {
-    TN_CHECK_ARG(ng >= 0, "negative group count");
-    TN_CHECK_ARG(T1 && RR && F && dmap && rmap && pref && suf && lidx && uidx && perm && starts && uniforms && child_out && log2p_inout && minP_out,
-                 "null operand");
-    return sample_pn((hipStream_t)stream, T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, ng, uniforms, q, nl, nu, p, Dr, br, child_out,
-                     log2p_inout, minP_out);
+int score_pn(hipStream_t st, const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+             const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
+             const int16_t* forced, int64_t ld, int64_t pos, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child,
+             double* log2p, double* cell_log2p, double* minP) {
+    if (ng <= 0) return 0;
+    TN_CHECK_ARG(q >= 1 && nl >= 1 && nu >= 1 && p >= 1 && Dr >= 1 && br >= 1, "non-positive dimension");
+    TN_CHECK_ARG(ng < ((int64_t)1 << 31), "too many groups");
+    TN_CHECK_ARG(pos >= 0 && pos < ld, "forced states: column outside the row");
+    const int64_t lds = (pn_front_doubles(p, Dr, br) + q) * 8;                  // calc_pn's bound: no running sum is kept
+    TN_CHECK_ARG(lds <= 150 * 1024, "site too large for score_pn (the table and the environments must fit 150 KiB of LDS)");
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)score_pn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(score_pn_kernel, dim3((unsigned)ng), dim3(256), (size_t)lds, st, T1, RR, F, dmap, rmap, pref, suf, lidx,
+                       uidx, perm, starts, forced, ld, pos, (int)q, (int)nl, (int)nu, (int)p, (int)Dr, (int)br, child, log2p, cell_log2p, minP));
+    TN_CHECK_LAUNCH("score_pn_kernel");
+    return 0;
 }
 
-int64_t tn_gibbs_sample_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax, int64_t max_env, int64_t max_t1, int64_t max_w) {
-    (void)qmax;                                      // no table is ever materialised: nothing here grows with q
+namespace {
+
+int64_t gibbs_walk_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t max_env, int64_t max_t1, int64_t max_w) {
     const int64_t cap = M, nsites = Nx * Ny;
     int64_t b = 0;
     auto add = [&](int64_t bytes) { b = align_up(b, 256) + bytes; };
@@ -173,31 +211,52 @@ int64_t tn_gibbs_sample_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax
     return b + 4096;
 }
 
-int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const double* uniforms, int64_t ldu, int16_t* states_out,
-                    double* energy_out, double* log2p_out, double* globalmin_host, int64_t* max_groups_host, void* ws, int64_t ws_bytes, void* stream) {
-    TN_CHECK_ARG(Nx >= 1 && Ny >= 1 && M >= 1 && B >= 1 && cells && ws, "bad arguments");
-    TN_CHECK_ARG(M < ((int64_t)1 << 31), "too many samples in one call");
-    TN_CHECK_ARG(uniforms && ldu >= M, "uniforms: null, or rows shorter than M");
-    TN_CHECK_ARG(states_out && energy_out && log2p_out && globalmin_host, "null result pointer");
+#define WK_ARG(cond, msg)                                  \
+    do {                                                   \
+        if (!(cond)) {                                     \
+            set_error("%s: %s", who, msg);                 \
+            return -1;                                     \
+        }                                                  \
+    } while (0)
+
+// The walk of both entries (`who`: the entry, for the error text).  score = false: tn_gibbs_sample, the draw step is sample_pn with
+// `uniforms` and the configurations go to states_out.  score = true: tn_gibbs_score, the draw step is score_pn along `forced`
+// (M x Nx*Ny) and cell_log2p_out (may be NULL) takes the increments.  Everything else -- right_levels, the row keys and unique,
+// advance_kernel, env_rl_batched, the workspace layout -- is the same code.
+int gibbs_walk(const char* who, bool score, int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const double* uniforms,
+               int64_t ldu, const int16_t* forced, int16_t* states_out, double* energy_out, double* log2p_out, double* cell_log2p_out,
+               double* globalmin_host, int64_t* max_groups_host, void* ws, int64_t ws_bytes, void* stream) {
+    WK_ARG(Nx >= 1 && Ny >= 1 && M >= 1 && B >= 1 && cells && ws, "bad arguments");
+    WK_ARG(M < ((int64_t)1 << 31), "too many samples in one call");
+    if (score) {
+        WK_ARG(forced, "states: null");
+    } else {
+        WK_ARG(uniforms && ldu >= M, "uniforms: null, or rows shorter than M");
+    }
+    WK_ARG((score || states_out) && energy_out && log2p_out && globalmin_host, "null result pointer");
     hipStream_t st = (hipStream_t)stream;
     const int64_t nsites = Nx * Ny, cap = M, ncol = Nx + 1;
     int64_t qmax = 1, max_env = 1, max_t1 = 1, max_w = 1;
     WALK_CHECK_CELLS(cells, nsites, qmax, max_env, max_t1, max_w)
     for (int64_t i = 0; i < nsites; ++i) {
         const tn_beam_cell& c = cells[i];
-        TN_CHECK_ARG((sample_tab_off(c.q, c.p, c.Dr, c.br) + c.q) * 8 <= 150 * 1024, "a cell's table, its running sum and environments exceed 150 KiB of LDS (tn_sample_pn)");
+        if (score) {
+            WK_ARG((pn_front_doubles(c.p, c.Dr, c.br) + c.q) * 8 <= 150 * 1024, "a cell's table and environments exceed 150 KiB of LDS (tn_score_pn)");
+        } else {
+            WK_ARG((sample_tab_off(c.q, c.p, c.Dr, c.br) + c.q) * 8 <= 150 * 1024, "a cell's table, its running sum and environments exceed 150 KiB of LDS (tn_sample_pn)");
+        }
     }
     {   // the radix product of the row keys (prefix rank, left, up, suffix rank) must fit int64 in the worst case of M distinct prefixes and suffixes
         int64_t r = 0;
-        TN_CHECK_ARG(mul_fits(M, B, r) && mul_fits(r, B, r) && mul_fits(r, M, r), "M x B x B x M exceeds int64 (row keys): use fewer samples per call");
+        WK_ARG(mul_fits(M, B, r) && mul_fits(r, B, r) && mul_fits(r, M, r), "M x B x B x M exceeds int64 (row keys): use fewer samples per call");
     }
-    if (ws_bytes < tn_gibbs_sample_ws_bytes(Nx, Ny, M, qmax, max_env, max_t1, max_w)) {
-        set_error("tn_gibbs_sample: workspace too small (%lld bytes, tn_gibbs_sample_ws_bytes asks for %lld)", (long long)ws_bytes,
-                  (long long)tn_gibbs_sample_ws_bytes(Nx, Ny, M, qmax, max_env, max_t1, max_w));
+    if (ws_bytes < gibbs_walk_ws_bytes(Nx, Ny, M, max_env, max_t1, max_w)) {
+        set_error("%s: workspace too small (%lld bytes, %s_ws_bytes asks for %lld)", who, (long long)ws_bytes, who,
+                  (long long)gibbs_walk_ws_bytes(Nx, Ny, M, max_env, max_t1, max_w));
         return -3;
     }
     Bump bump;
-    bump.base = (char*)ws; bump.cap = ws_bytes; bump.who = "tn_gibbs_sample";
+    bump.base = (char*)ws; bump.cap = ws_bytes; bump.who = who;
     TAKE(vind, int32_t, bump, ncol * cap, "index rows");
     TAKE(vind2, int32_t, bump, ncol * cap, "index rows");
     TAKE(sufmat, int32_t, bump, Nx * cap, "suffix ranks");
@@ -212,7 +271,7 @@ int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M
     double* scal = bump.take<double>(8);             // device scalars: [0] globalmin, [1] min of minP
     S.cub_bytes = (size_t)sampler_cub_bytes(M);
     S.cub_tmp = bump.take<char>((int64_t)S.cub_bytes);
-    if (!S.iota || !scal || !S.cub_tmp) { set_error("tn_gibbs_sample: workspace too small (sort storage)"); return -3; }
+    if (!S.iota || !scal || !S.cub_tmp) { set_error("%s: workspace too small (sort storage)", who); return -3; }
     {   // the temporary storage rocPRIM asks for at the largest sizes must fit the slot
         size_t need = 0, t = 0;
         (void)rocprim::radix_sort_pairs(nullptr, t, (const int64_t*)nullptr, (int64_t*)nullptr, (const int32_t*)nullptr, (int32_t*)nullptr, (int)M, 0, 64, st);
@@ -221,7 +280,7 @@ int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M
         need = std::max(need, t);
         (void)rocprim::reduce(nullptr, t, (const double*)nullptr, (double*)nullptr, std::numeric_limits<double>::max(), (size_t)M, rocprim::minimum<double>(), st);
         need = std::max(need, t);
-        TN_CHECK_ARG(need <= S.cub_bytes, "rocPRIM temporary storage exceeds its slot");
+        WK_ARG(need <= S.cub_bytes, "rocPRIM temporary storage exceeds its slot");
     }
     hipLaunchKernelGGL(iota_kernel, dim3((unsigned)cdiv(cap, 256)), dim3(256), 0, st, S.iota, cap);
     TN_CHECK_LAUNCH("iota_kernel");
@@ -278,11 +337,16 @@ int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M
             TAKE(gsuf, int32_t, bump, ng, "group suffixes");
             hipLaunchKernelGGL(group_gather_kernel, dim3((unsigned)cdiv(ng, 256)), dim3(256), 0, st, first, pref, lcol, ucol, suf, ng, gpref, gl, gu, gsuf);
             TN_CHECK_LAUNCH("group_gather_kernel");
-            // ---- the draw (tnac4o.py:614-622)
+            // ---- the draw (tnac4o.py:614-622), or the caller's state in its place
             TAKE(child, int32_t, bump, M, "drawn states");
             TAKE(mP, double, bump, ng, "table flags");
-            BS(sample_pn(st, T1, RRs[(size_t)lvl], c.F, c.dmap, c.rmap, gpref, gsuf, gl, gu, perm, starts, ng, uniforms + pos * ldu, c.q, c.nl, c.nu, c.p,
-                         c.Dr, c.br, child, lq, mP));
+            if (score) {
+                BS(score_pn(st, T1, RRs[(size_t)lvl], c.F, c.dmap, c.rmap, gpref, gsuf, gl, gu, perm, starts, ng, forced, nsites, pos, c.q, c.nl, c.nu,
+                            c.p, c.Dr, c.br, child, lq, cell_log2p_out, mP));
+            } else {
+                BS(sample_pn(st, T1, RRs[(size_t)lvl], c.F, c.dmap, c.rmap, gpref, gsuf, gl, gu, perm, starts, ng, uniforms + pos * ldu, c.q, c.nl, c.nu, c.p,
+                             c.Dr, c.br, child, lq, mP));
+            }
             size_t tb = S.cub_bytes;
             BSH(rocprim::reduce(S.cub_tmp, tb, mP, scal + 1, std::numeric_limits<double>::max(), (size_t)ng, rocprim::minimum<double>(), st), "sampling walk: minimum");
             hipLaunchKernelGGL(scalar_min_kernel, dim3(1), dim3(1), 0, st, scal, 0, scal + 1);
@@ -309,7 +373,7 @@ int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M
         TN_CHECK_LAUNCH("shift_columns_kernel");
         std::swap(vind, vind2);
     }
-    BSH(hipMemcpyAsync(states_out, states, (size_t)M * nsites * 2, hipMemcpyDeviceToDevice, st), "sampling walk: results");
+    if (states_out) BSH(hipMemcpyAsync(states_out, states, (size_t)M * nsites * 2, hipMemcpyDeviceToDevice, st), "sampling walk: results");
     BSH(hipMemcpyAsync(energy_out, Eng, (size_t)M * 8, hipMemcpyDeviceToDevice, st), "sampling walk: results");
     BSH(hipMemcpyAsync(log2p_out, lq, (size_t)M * 8, hipMemcpyDeviceToDevice, st), "sampling walk: results");
     double hs = 0.0;
@@ -319,4 +383,57 @@ int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M
     return 0;
 }
 
+}  // namespace
+
+}  // namespace tn
+
+using namespace tn;
+
+extern "C" {
+
+int tn_sample_pn(const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+                 const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
+                 const double* uniforms, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child_out,
+                 double* log2p_inout, double* minP_out, void* stream) {
+    TN_CHECK_ARG(ng >= 0, "negative group count");
+    TN_CHECK_ARG(T1 && RR && F && dmap && rmap && pref && suf && lidx && uidx && perm && starts && uniforms && child_out && log2p_inout && minP_out,
+                 "null operand");
+    return sample_pn((hipStream_t)stream, T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, ng, uniforms, q, nl, nu, p, Dr, br, child_out,
+                     log2p_inout, minP_out);
+}
+
+int tn_score_pn(const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap, const int32_t* pref,
+                const int32_t* suf, const int32_t* lidx, const int32_t* uidx, const int32_t* perm, const int64_t* starts, int64_t ng,
+                const int16_t* forced, int64_t ld, int64_t pos, int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, int32_t* child_out,
+                double* log2p_inout, double* cell_log2p, double* minP_out, void* stream) {
+    TN_CHECK_ARG(ng >= 0, "negative group count");
+    TN_CHECK_ARG(T1 && RR && F && dmap && rmap && pref && suf && lidx && uidx && perm && starts && forced && child_out && log2p_inout && minP_out,
+                 "null operand");
+    return score_pn((hipStream_t)stream, T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, ng, forced, ld, pos, q, nl, nu, p, Dr, br, child_out,
+                    log2p_inout, cell_log2p, minP_out);
+}
+
+int64_t tn_gibbs_sample_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax, int64_t max_env, int64_t max_t1, int64_t max_w) {
+    (void)qmax;                                      // no table is ever materialised: nothing here grows with q
+    return gibbs_walk_ws_bytes(Nx, Ny, M, max_env, max_t1, max_w);
+}
+
+int tn_gibbs_sample(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const double* uniforms, int64_t ldu, int16_t* states_out,
+                    double* energy_out, double* log2p_out, double* globalmin_host, int64_t* max_groups_host, void* ws, int64_t ws_bytes, void* stream) {
+    return gibbs_walk("tn_gibbs_sample", false, Nx, Ny, cells, M, B, uniforms, ldu, nullptr, states_out, energy_out, log2p_out, nullptr, globalmin_host,
+                      max_groups_host, ws, ws_bytes, stream);
+}
+
+int64_t tn_gibbs_score_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t qmax, int64_t max_env, int64_t max_t1, int64_t max_w) {
+    (void)qmax;                                      // the walk's own workspace: the forced states and the increments are the caller's
+    return gibbs_walk_ws_bytes(Nx, Ny, M, max_env, max_t1, max_w);
+}
+
+int tn_gibbs_score(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t B, const int16_t* states, double* energy_out, double* log2p_out,
+                   double* cell_log2p_out, double* globalmin_host, int64_t* max_groups_host, void* ws, int64_t ws_bytes, void* stream) {
+    return gibbs_walk("tn_gibbs_score", true, Nx, Ny, cells, M, B, nullptr, 0, states, nullptr, energy_out, log2p_out, cell_log2p_out, globalmin_host,
+                      max_groups_host, ws, ws_bytes, stream);
+}
+
 }  // extern "C"
+

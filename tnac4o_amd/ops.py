@@ -753,6 +753,35 @@ def sample_pn(T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, unifor
     return child, log2p, mP
 
 
+def score_pn(T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, forced, pos, log2p=None, cells=False):
+    """log2 of the conditional probability of a GIVEN state per sample, from the table of its boundary row (tn_score_pn).  Groups as
+    sample_pn; forced (int16, n x ld): the state of sample k is forced[k, pos].  log2p (float64 per sample, updated in place; None:
+    zeros).  Returns (child (int32 per sample), log2p, minP (per group)), with cells=True also cell_log2p (n x ld, column pos written).
+    An entry that is not positive, or a state outside [0, q), scores -inf; the latter comes back as child 0."""
+    ng = starts.numel() - 1
+    n, ld = forced.shape
+    q, nl, nu = F.shape
+    _, p, Dr = T1.shape
+    br = RR.shape[2]
+    for t in (T1, RR, F, dmap, rmap, pref, suf, lidx, uidx, perm, starts, forced):
+        assert t.is_contiguous() and t.is_cuda
+    for t in (pref, suf, lidx, uidx):
+        assert t.dtype == torch.int32 and t.numel() == ng
+    assert perm.dtype == torch.int32 and starts.dtype == torch.int64 and forced.dtype == torch.int16 and 0 <= pos < ld
+    if log2p is None:
+        log2p = torch.zeros(n, dtype=torch.float64, device=T1.device)
+    assert log2p.is_contiguous() and log2p.numel() == n and log2p.dtype == torch.float64
+    child = torch.zeros(n, dtype=torch.int32, device=T1.device)
+    mP = torch.empty((ng,), dtype=torch.float64, device=T1.device)
+    cl = torch.zeros((n, ld), dtype=torch.float64, device=T1.device) if cells else None
+    check(lib().tn_score_pn(T1.data_ptr(), RR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), pref.data_ptr(), suf.data_ptr(),
+                            lidx.data_ptr(), uidx.data_ptr(), perm.data_ptr(), starts.data_ptr(), ng, forced.data_ptr(), ld, pos, q, nl, nu, p, Dr,
+                            br, child.data_ptr(), log2p.data_ptr(), cl.data_ptr() if cells else None, mP.data_ptr(), _stream()))
+    if cells:
+        return child, log2p, mP, cl
+    return child, log2p, mP
+
+
 def merge_groups(E, lp, deg, pos, starts, min_dEng):
     """Per-group merge of a site-step's candidates (tn_merge_groups): members sorted by group, `starts` the ngroups + 1 offsets.
     Returns (rep_pos, deg, log2p) per group, device tensors."""

@@ -1057,6 +1057,46 @@ class tnac4o:
         self._setup_rhoT(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
         return sampler.sample_native(self, int(M), uniforms=uniforms, chunk=chunk)
 
+    def _cell_sizes(self):
+        """Number of states of every cell of the rotated lattice, row-major (host)."""
+        if self.mode == 'Ising':
+            return np.array([2 ** int(self.sN[ny][nx]) for ny in range(self.Ny) for nx in range(self.Nx)], dtype=np.int64)
+        return np.array([int(self.N[ny][nx]) for ny in range(self.Ny) for nx in range(self.Nx)], dtype=np.int64)
+
+    def calculate_log_probability(self, states=None, boundary='build', cells=False, Dmax=32, tolS=1e-15, tolV=1e-10, max_sweeps=20,
+                                  graduate_truncation=True, chunk=None):
+        """log2 q(x) of GIVEN configurations: the probability with which the sampling walk of sample_boltzmann would draw each of
+        them, from the library's walk forced along them (tn_gibbs_score) -- for a configuration sample_boltzmann drew on the same
+        boundaries, the very bits of its `probability` and `energy`.  q is a normalised distribution for any truncation; with
+        calculate_free_energy, log2 q(x) + beta E(x) / ln 2 + log2 Z is the pointwise truncation error.
+        states: an integer numpy array (M, Nx*Ny) in model cell order, in the encoding of `states` (spin read-outs of an Ising
+        model: states_from_binary); None = the stored `states`.  A wrong shape or dtype, or an entry outside the states of its cell,
+        is a ValueError raised before any device work.  boundary: 'build' runs the sweep for rhoT with the given options, 'keep'
+        uses rhoT as it stands (ValueError when there is none).  chunk: configurations per call of the walk, as sample_boltzmann's.
+        Stores scored_log2q (M,) (returned), scored_energy (M,) in the convention of `energy`, scored_negative (<= 0, the smallest
+        conditional-table flag met) and, with cells=True, scored_cell_log2q (M, Nx*Ny) in model cell order, the log2 of the
+        conditional probability the walk used at every cell (None otherwise).  A configuration with a conditional probability that is
+        not positive scores -inf, never NaN.  Leaves states, energy, probability and every other search and sampling result alone.
+        Raises NotImplementedError naming the limit when a cell does not fit the walk; there is no host fallback."""
+        from . import sampler
+        if boundary not in ('build', 'keep'):
+            raise ValueError("boundary must be 'build' or 'keep'")
+        st = sampler.check_states(self.states if states is None else states, self._cell_sizes()[self.order])
+        if chunk is not None:
+            sampler.chunk_slices(st.shape[0], chunk)
+        if boundary == 'keep' and getattr(self, 'rhoT', None) is None:
+            raise ValueError("boundary='keep' needs rhoT: run a search, a sampling or a thermal call first, or use boundary='build'")
+        self.logger.info('Scoring %d configurations with beta = %.2f', st.shape[0], self.beta)
+        if boundary == 'build':
+            self._setup_rhoT(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
+        rot = np.empty_like(st)
+        rot[:, self.order] = st                                  # the inverse of _store_result's states[:, order]
+        log2q, energy, cell_lq, globalmin, _ = sampler.score_native(self, rot, chunk=chunk, cells=cells)
+        self.scored_log2q, self.scored_energy = log2q, energy
+        self.scored_cell_log2q = cell_lq[:, self.order] if cells else None
+        self.scored_negative = min(globalmin, 0)
+        return log2q
+
     # ------------------------------------------------------------------------------------ thermal marginals (GPU)
     def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
         """Boltzmann marginal of every cell and magnetisation of every spin at the solver's beta, from both boundary MPS.
@@ -1146,6 +1186,82 @@ class tnac4o:
         self.pair_marginals = model_correlations(Pl, Pu, self.order, self.Nx, self.Ny, keys=list(self.J['fac']), Nx_model=self.Nx_model)
         self.bond_pairs = self.correlations = None
         return self.pair_marginals
+
+    # ------------------------------------------------------------------------------------ partition function (GPU)
+    def calculate_free_energy(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True, boundary='build'):
+        """log2 Z, free energy and entropy at the solver's beta from both boundary MPS: the row contractions r_ny = <rhoB[ny]| row ny
+        |rhoT[ny+1]> of calculate_correlations over the overlaps o_ny = <rhoB[ny]|rhoT[ny]> of the boundaries at the Ny - 1 cuts,
+            log2 Z = sum_ny log2 |r_ny| - sum_ny log2 |o_ny| - (beta / ln 2) sum_cells (min Es + min E1 + min E4),
+        the last term putting back what the PEPS factors take out of the energy tables.  Exact when nothing is truncated; otherwise
+        an estimate that uses both boundaries symmetrically: the norm and sign of every interior boundary occur once above and once
+        below the line.  Z runs over the ACTIVE spins, E in the convention of `energy`: the number sample_log2Z estimates.
+        boundary: 'build' runs both sweeps with the given options, 'keep' uses rhoT and rhoB as they stand (ValueError when one is
+        missing).  Stores log2Z (returned), free_energy = -ln Z / beta, entropy = ln Z + beta energy_mean (nats), energy_mean,
+        log2Z_rows (Ny,) = log2 |r_ny| (taken at the first cell of the row), log2Z_overlaps (Ny-1,) = log2 |o_ny| and
+        free_energy_row_spread: the largest deviation of the row contraction along a row, |log2 r at a cell - log2 r at the first| /
+        max(|log2 r|, 1) -- every cell of a row contracts the same network, so this is rounding (1e-10 is the bar of the thermal
+        calls).  Leaves the search results, gauges and rotation alone."""
+        from . import sampler
+        if boundary not in ('build', 'keep'):
+            raise ValueError("boundary must be 'build' or 'keep'")
+        if boundary == 'keep' and (getattr(self, 'rhoT', None) is None or getattr(self, 'rhoB', None) is None):
+            raise ValueError("boundary='keep' needs rhoT and rhoB: run a thermal call first, or use boundary='build'")
+        self.logger.info('Free energy with beta = %.2f', self.beta)
+        if boundary == 'build':
+            kw = _sweep_options(graduate_truncation, Dmax, tolS, tolV, max_sweeps)
+            self._setup_rhoT(**kw)
+            self._setup_rhoB(**kw)
+        Ny, Nx = self.Ny, self.Nx
+        Pl, Pu, _, log2r = self._correlation_pass()
+        neg = np.flatnonzero(np.isnan(log2r).any(axis=1))
+        if neg.size:
+            # a row contraction below zero (a boundary that carries a sign; the kernel's log2 is NaN there): the same pass with the
+            # sign taken out of the first site of a copy of the boundary above those rows
+            kept = self.rhoT
+            try:
+                self.rhoT = list(kept)
+                for ny in neg:
+                    flipped = kept[ny + 1].copy()
+                    flipped.A[0] = -flipped.A[0]
+                    self.rhoT[ny + 1] = flipped
+                Pl, Pu, _, log2r = self._correlation_pass()
+            finally:
+                self.rhoT = kept
+        ends, o, log2o = self._boundary_overlaps()
+        shifts = [[np.min(t) for t in self._cell_energies(ny, nx)] for ny in range(Ny) for nx in range(Nx)]
+        self.log2Z, self.log2Z_rows, self.log2Z_overlaps = sampler.log2z_from_rows(
+            np.ones(Ny), o, shifts, self.beta, rows_log2=log2r[:, 0], overlaps_log2=log2o, ends=ends)
+        self.free_energy_row_spread = float(np.max(np.abs(log2r - log2r[:, :1]) / np.maximum(np.abs(log2r[:, :1]), 1.0)))
+        self.energy_mean = self._bond_energy(Pl, Pu)
+        lnZ = self.log2Z * sampler.LN2
+        self.free_energy = -lnZ / self.beta
+        self.entropy = lnZ + self.beta * self.energy_mean
+        return self.log2Z
+
+    def _boundary_overlaps(self):
+        """The two-layer overlaps o_ny = <rhoB[ny]|rhoT[ny]> at the cuts ny = 1 .. Ny-1 from the boundaries as they stand, walked left
+        to right on the device (tn_env_mix), every environment divided by a power of two (tn_normalize_pow2) so that no overlap of
+        two different states has to stay inside the double range; and what the two trivial boundaries beyond the lattice, rhoB[0]
+        and rhoT[Ny], contract to.  One read-back.  Returns ((e_B, e_T), mantissas (Ny-1,), log2 factors (Ny-1,)): o_ny =
+        mantissa 2^factor."""
+        Ny, Nx = self.Ny, self.Nx
+        dev = self.rhoT[0].A[0].device
+        outs = []
+        for psi in (self.rhoB[0], self.rhoT[Ny]):
+            if any(tuple(a.shape) != (1, 1, 1) for a in psi.A):
+                raise ValueError('the boundary beyond the lattice must be the trivial one (d = 1, D = 1)')
+            outs.append(torch.cat([a.reshape(-1) for a in psi.A]))
+        for ny in range(1, Ny):
+            E, nfs = torch.ones((1, 1), dtype=torch.float64, device=dev), []
+            for nx in range(Nx):
+                E = ops.env_mix(0, E, self.rhoT[ny].A[nx].contiguous(), self.rhoB[ny].A[nx].contiguous())
+                nfs.append(ops.normalize_pow2_(E)[:1])
+            outs += [E.reshape(-1), torch.cat(nfs)]
+        host = _read_back(outs)
+        ends = (float(np.prod(host[0])), float(np.prod(host[1])))
+        o = np.array([host[2 + 2 * i][0] for i in range(Ny - 1)])
+        log2o = np.array([np.sum(np.log2(host[3 + 2 * i])) for i in range(Ny - 1)])
+        return ends, o, log2o
 
     def _bond_energy(self, Pl, Pu):
         """<E> = sum_k [sum_s p_k Es_k + sum_{s,l} Pl_k E1_k + sum_{s,u} Pu_k E4_k] from the bond tables of the rotated frame
@@ -1349,6 +1465,27 @@ class tnac4o:
                 k += 1
                 act = self.ind0[ny][nx]
                 out[:, act] = (1 - _bits(len(act)))[self.states[:ns, k]]
+        return out
+
+    def states_from_binary(self, bits):
+        """Cell states, in the encoding of `states`, of spin read-outs (Ising): the inverse of binary_states() on the active spins.
+        bits: (M, L) integers, 1 spin up, 0 spin down; the entries of inactive spins are ignored.  Returns (M, Nx*Ny) int64 in
+        model cell order (host numpy); a value other than 0 / 1 at an active spin is a ValueError."""
+        if self.mode != 'Ising':
+            raise ValueError('states_from_binary is for Ising models (an RMF state is its own read-out)')
+        bits = np.asarray(bits)
+        if bits.ndim != 2 or bits.shape[1] != self.L or bits.dtype.kind not in 'iub':
+            raise ValueError('bits must be an integer array of shape (M, L) = (M, %d)' % self.L)
+        out = np.zeros((bits.shape[0], self.Nx_model * self.Ny_model), dtype=np.int64)
+        k = -1
+        for ny in range(self.Ny_model):
+            for nx in range(self.Nx_model):
+                k += 1
+                act = np.asarray(self.ind0[ny][nx], dtype=np.int64)
+                b = bits[:, act].astype(np.int64)
+                if np.any((b != 0) & (b != 1)):
+                    raise ValueError('bits of active spins must be 0 or 1')
+                out[:, k] = (1 - b) @ (2 ** np.arange(len(act), dtype=np.int64))
         return out
 
     def save(self, file_name):
