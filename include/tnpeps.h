@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 15 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 16 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -530,6 +530,23 @@ int tn_gibbs_score(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M,
 int64_t tn_pair_hist_ws_bytes(int64_t M, int64_t nbits, int lanes16);
 int tn_pair_hist(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, int lanes16, uint64_t* hist_out, void* ws,
                  int64_t ws_bytes, void* stream);
+
+/* tn_pair_moments: second moments of the GROUPED pairwise distances (no counterpart in the reference: the overlap correlations of the
+ * samples, tnac4o.calculate_overlap_correlations).  rows (DEVICE) = M rows at a stride of ldr words; a row is G groups of wpg uint64
+ * words, group g = words [g wpg, (g+1) wpg); the caller pads a group with zeros to whole words (nothing is masked), the words
+ * G wpg .. ldr-1 are never read.  d_g(a, b) = the distance of rows a and b within group g, tn_pair_hist's distance (lanes16 = 0:
+ * popcount of the XOR, lanes16 = 1: 16-bit lanes that differ), and d_G = 1.  weights (DEVICE, M uint32; NULL = all 1); a weight above
+ * wmax is read as wmax.  out (DEVICE, 16-byte aligned, (G+1) x (G+1) entries of two uint64: lo, hi), row-major and symmetric:
+ * out[i][j] = sum_{a<b} w_a w_b d_i d_j as the exact integer lo + 2^64 hi, so out[G][G] = sum w_a w_b, out[g][G] = sum w_a w_b d_g.
+ * An integer function of the inputs: bit-identical for every grid size, tile order and run (no atomics and no floating point; 128-bit
+ * accumulators in registers, one slab per workgroup in ws, summed with carry).  Every entry is written; M < 2 gives zeros.
+ * ws: 16-byte aligned, tn_pair_moments_ws_bytes (which reads TN_PAIR_MOMENTS_WGS as the call does; 0 for a shape the call refuses).
+ * Asynchronous on `stream`.  Limits: 0 <= M < 2^31; 1 <= G <= 64; 1 <= wpg <= 32; ldr >= G wpg; wmax >= 1 and, with
+ * dmax = (lanes16 ? 4 : 64) wpg, wmax dmax <= 2^32 - 1 -- every term is then below 2^64 and the fewer than 2^61 pairs fit two limbs.
+ * Errors: -1 argument (the message names the limit), -3 workspace too small; both before any launch, nothing is written. */
+int64_t tn_pair_moments_ws_bytes(int64_t M, int64_t G, int64_t wpg, int lanes16);
+int tn_pair_moments(const uint64_t* rows, int64_t M, int64_t G, int64_t wpg, int64_t ldr, const uint32_t* weights, uint32_t wmax, int lanes16,
+                    uint64_t* out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

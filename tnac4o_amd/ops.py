@@ -1029,3 +1029,36 @@ def pair_hist(rows, nbits, weights=None, lanes16=False):
     check(L.tn_pair_hist(rows.data_ptr() if M else ws.data_ptr(), M, nbits, max(ld, nwords), weights.data_ptr() if weights is not None else None,
                          int(bool(lanes16)), out.data_ptr(), ws.data_ptr(), wsb, _stream()))
     return out
+
+
+def pair_moments(rows, G, wpg, weights=None, wmax=None, lanes16=False):
+    """Second moments of the grouped pairwise distances of packed rows (tn_pair_moments): rows (M, ld) int64 / uint64 device tensor
+    whose first G * wpg words are G groups of wpg words each, zero-padded by the caller (overlap.pack_groups); weights None (all 1)
+    or (M,) uint32 values in an int32 / uint32 device tensor, read as at most wmax (None: the largest the call takes,
+    (2^32 - 1) // dmax with dmax = (4 if lanes16 else 64) * wpg).  Returns the (G + 1, G + 1, 2) int64 device tensor of the limbs
+    (lo, hi) of out[i][j] = sum_{a<b} w_a w_b d_i d_j, d_g the distance within group g and d_G = 1: exact integers (read them as
+    unsigned)."""
+    if not rows.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % rows.device)
+    if rows.dim() != 2 or rows.element_size() != 8 or rows.is_floating_point() or rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise TypeError('rows: a 2-d tensor of 64-bit integer words with unit stride along a row')
+    M, ld = int(rows.shape[0]), int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    G, wpg = int(G), int(wpg)
+    nwords = max(G, 0) * max(wpg, 0)
+    if rows.shape[1] < nwords:
+        raise ValueError('rows hold %d words, %d groups of %d words take %d' % (rows.shape[1], G, wpg, nwords))
+    if weights is not None:
+        if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous() or weights.numel() != M:
+            raise TypeError('weights: a contiguous device tensor of M 32-bit integers')
+    if wmax is None:
+        wmax = (2 ** 32 - 1) // ((4 if lanes16 else 64) * max(wpg, 1))
+    wmax = int(wmax)
+    if not 0 <= wmax < 2 ** 32:
+        raise ValueError('wmax must fit 32 bits')
+    L = lib()
+    wsb = int(L.tn_pair_moments_ws_bytes(M, G, wpg, int(bool(lanes16))))    # (not cached: it follows TN_PAIR_MOMENTS_WGS)
+    ws = workspace(max(wsb, 16), 1)
+    out = torch.empty((max(G, 0) + 1, max(G, 0) + 1, 2), dtype=torch.int64, device=rows.device)
+    check(L.tn_pair_moments(rows.data_ptr() if M else ws.data_ptr(), M, G, wpg, max(ld, nwords), weights.data_ptr() if weights is not None else None,
+                            wmax, int(bool(lanes16)), out.data_ptr(), ws.data_ptr(), wsb, _stream()))
+    return out

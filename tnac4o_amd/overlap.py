@@ -1,7 +1,8 @@
-"""Replica-overlap distributions of a set of configurations (host side of tnac4o.calculate_overlap_distribution).
+"""Replica-overlap distributions of a set of configurations (host side of tnac4o.calculate_overlap_distribution) and
+their line-resolved second moments (tnac4o.calculate_overlap_correlations).
 
-Plain numpy, importable without a GPU; the only device work is the pair histogram tn_pair_hist (ops.pair_hist), which the driver at the
-end of this module calls once.  Row layouts of the library: a row of n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at
+Plain numpy, importable without a GPU; the only device work is the pair histogram tn_pair_hist (ops.pair_hist), which the driver
+overlap_distribution calls once, and the pair moments tn_pair_moments (ops.pair_moments), which overlap_correlations calls once per axis.  Row layouts of the library: a row of n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at
 position i % 64; a row of n 16-bit lanes is ceil(n / 4) words, lane i in word i // 4 at bits 16 (i % 4) .. 16 (i % 4) + 15."""
 import numpy as np
 
@@ -89,24 +90,28 @@ def condense(rows, w):
     return urows, W, float(np.sum(W * W - S) / 2.0)
 
 
-def quantise(W):
+def quantise(W, wmax=WMAX):
     """Weights as the uint32 tn_pair_hist takes: (wq (K,) uint32, keep (K,) bool, scale) with wq = rint(scale * W).  Integer W up to
     2^32 - 1 (the multiplicities under uniform weights) pass through with scale 1: the device result is then the exact pair count.
     Otherwise two scales are tried, (2^32 - 1) / max W and the largest power of two below it, and the one with the smaller total
     rounding error sum |wq / scale - W| is taken.  The first puts every weight within half a unit, 2^-33 of the largest, so the
     total is at most K 2^-33 max W with either.  The second is exact for weights that are multiples of a common power of two up to
     rounding -- multiplicities of nearly equal importance weights -- where the first would shift every row of one multiplicity by
-    the same amount.  keep marks the rows with wq > 0; the others are to be dropped."""
+    the same amount.  keep marks the rows with wq > 0; the others are to be dropped.  wmax: the largest quantised weight, in place
+    of 2^32 - 1 everywhere above (tn_pair_moments takes less, so that its products stay below 2^64)."""
     W = np.asarray(W, dtype=np.float64)
+    wmax = int(wmax)
+    if not 1 <= wmax <= WMAX:
+        raise ValueError('wmax must lie in 1 .. 2^32 - 1')
     if W.size == 0:
         return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=bool), 1.0
-    if np.all(W == np.rint(W)) and W.max() <= WMAX:
+    if np.all(W == np.rint(W)) and W.max() <= wmax:
         wq, scale = W, 1.0
     else:
-        full = WMAX / float(W.max())
+        full = wmax / float(W.max())
         best = None
         for sc in (full, 2.0 ** np.floor(np.log2(full))):
-            q = np.minimum(np.rint(W * sc), WMAX)
+            q = np.minimum(np.rint(W * sc), wmax)
             err = float(np.sum(np.abs(q / sc - W)))
             if best is None or err < best[0]:
                 best = (err, q, sc)
@@ -235,3 +240,181 @@ def overlap_distribution(solver, kind=None, weights='uniform'):
     solver.overlap_ess = effective_sample_size(w)
     solver.overlap_pairs = M * (M - 1) // 2
     return P
+
+
+# ---------------------------------------------------------------------------------------------- line-resolved overlaps
+MAX_GROUPS = 64                  # lattice columns (rows) tn_pair_moments takes: the distance table of 65 groups fills the 160 KiB of LDS
+MAX_GROUP_WORDS = 32             # words of one group: 2048 spins or 128 cells in a lattice column (row)
+
+
+def line_groups(solver, axis, kind):
+    """The lattice line of everything a state is compared by: (group (n,) int64, sizes (G,) int64).  kind 'spin': entry k belongs to bit
+    k of spin_bits(solver), an active spin in model order; kind 'cell': to cell k of `states` (model cell order, k = ny Nx + nx).
+    The group is the model column nx (axis 'x', G = Nx) or the model row ny (axis 'y', G = Ny) of the cell -- for a spin, of the cell
+    that lists it in solver.ind0[ny][nx].  sizes[g] = the number of entries of group g."""
+    if axis not in ('x', 'y'):
+        raise ValueError("axis must be 'x' or 'y'")
+    if kind not in ('spin', 'cell'):
+        raise ValueError("kind must be 'spin' or 'cell' (a coupling lies in two groups)")
+    Nx, Ny = int(solver.Nx_model), int(solver.Ny_model)
+    line = np.tile(np.arange(Nx), Ny) if axis == 'x' else np.repeat(np.arange(Ny), Nx)           # of cell k = ny Nx + nx
+    if kind == 'cell':
+        group = line.astype(np.int64)
+    else:
+        _ising(solver, "kind 'spin'")
+        spins = np.concatenate([np.asarray(a, dtype=np.int64) for row in solver.ind0 for a in row] + [np.zeros(0, dtype=np.int64)])
+        cells = np.concatenate([np.full(len(a), ny * Nx + nx, dtype=np.int64) for ny, row in enumerate(solver.ind0) for nx, a in enumerate(row)]
+                               + [np.zeros(0, dtype=np.int64)])
+        group = line[cells[np.argsort(spins, kind='stable')]].astype(np.int64)                   # spin_bits sorts the active spins
+    return group, np.bincount(group, minlength=Nx if axis == 'x' else Ny).astype(np.int64)
+
+
+def pack_groups(bits_or_states, group, G, lanes16):
+    """(M, n) bits (lanes16: cell states in [0, 32768)) with the group of every column -> (rows (M, G wpg) uint64, wpg): group g in
+    the words [g wpg, (g+1) wpg) of a row, its entries in the order of their columns, layout of pack_bits (pack_lanes16) within the
+    group, zeros behind them.  wpg = the words of the largest group, at least 1."""
+    X = np.asarray(bits_or_states)
+    group = np.asarray(group, dtype=np.int64).reshape(-1)
+    G = int(G)
+    if X.ndim != 2 or group.shape != (X.shape[1],):
+        raise ValueError('an (M, n) array and the group of each of its n columns expected')
+    if G < 1 or group.size and (group.min() < 0 or group.max() >= G):
+        raise ValueError('groups must lie in [0, G)')
+    per = 4 if lanes16 else 64
+    sizes = np.bincount(group, minlength=G)
+    wpg = max(1, -(-int(sizes.max()) // per))
+    order = np.argsort(group, kind='stable')
+    rank = np.empty(group.size, dtype=np.int64)
+    rank[order] = np.arange(group.size) - np.concatenate([[0], np.cumsum(sizes)])[group[order]]  # position within the group
+    wide = np.zeros((X.shape[0], G * wpg * per), dtype=np.int64)
+    wide[:, group * (wpg * per) + rank] = X
+    return (pack_lanes16(wide) if lanes16 else pack_bits(wide)), wpg
+
+
+def second_moments(out_limbs, sizes, kind, scale=1.0, D0=0.0):
+    """(<Q_g> (G,), <Q_g Q_g'> (G, G)) in float64 from the integers of tn_pair_moments: out_limbs (G+1, G+1, 2), sizes n_g, Q_g =
+    n_g - 2 d_g for 'spin' (the sum of s_a s_b over the group) and n_g - d_g for 'cell' (the equal cells).  With c = 2 or 1,
+    sum p Q_g Q_g' = n_g n_g' out[G][G] - c n_g out[g'][G] - c n_g' out[g][G] + c^2 out[g][g'] is formed in Python integers and
+    divided once by sum p = out[G][G], so the cancellation is exact.  D0 (condense) is the weight of the pairs of equal rows, in
+    units of the unquantised weights: they have d_g = 0 for every g, so Q_g = n_g, and enter both sums -- as an integer when the
+    weights are integers (scale 1), as a float otherwise."""
+    h = np.asarray(out_limbs)
+    G = h.shape[0] - 1
+    n = [int(x) for x in sizes]
+    if h.shape != (G + 1, G + 1, 2) or len(n) != G:
+        raise ValueError('out_limbs (G+1, G+1, 2) and G sizes expected')
+    O = limbs_to_int(h.reshape(-1, 2))
+    O = [O[i * (G + 1):(i + 1) * (G + 1)] for i in range(G + 1)]
+    c = 1 if kind == 'cell' else 2
+    exact = float(scale) == 1.0 and float(D0) == np.rint(D0)
+    D0i = int(np.rint(D0)) if exact else 0
+    den = O[G][G] + D0i
+    S1 = [n[g] * den - c * O[g][G] for g in range(G)]
+    S2 = [[n[g] * n[k] * den - c * n[g] * O[k][G] - c * n[k] * O[g][G] + c * c * O[g][k] for k in range(G)] for g in range(G)]
+    if exact:
+        if den <= 0:
+            raise ValueError('no pair of distinct samples carries weight')
+        mean = np.array([v / den for v in S1], dtype=np.float64).reshape(G)
+        return mean, np.array([[v / den for v in r] for r in S2], dtype=np.float64).reshape(G, G)
+    s2 = float(scale) * float(scale)
+    nf = np.array(n, dtype=np.float64)
+    den = float(den) / s2 + float(D0)
+    if not den > 0:
+        raise ValueError('no pair of distinct samples carries weight')
+    mean = (np.array([float(v) for v in S1], dtype=np.float64).reshape(G) / s2 + D0 * nf) / den
+    return mean, (np.array([[float(v) for v in r] for r in S2], dtype=np.float64).reshape(G, G) / s2 + D0 * np.outer(nf, nf)) / den
+
+
+def chi_of_k(QQ, N):
+    """chi(k_m) = (1 / N) sum_{g,g'} <Q_g Q_g'> cos(k_m (g - g')), k_m = 2 pi m / G, m = 0 .. G // 2.  At k != 0 the G^2 terms cancel
+    down to a small remainder, so they are added up without rounding (math.fsum): what error is left is that of the terms."""
+    import math
+    QQ = np.asarray(QQ, dtype=np.float64)
+    G = QQ.shape[0]
+    dg = np.arange(G)[:, None] - np.arange(G)[None, :]
+    return np.array([math.fsum((QQ * np.cos(2.0 * np.pi * m * dg / G)).ravel()) for m in range(G // 2 + 1)], dtype=np.float64) / float(N)
+
+
+def correlation_length(QQ, N):
+    """(chi (G // 2 + 1,), xi): xi = 1 / (2 sin(pi / G)) sqrt(chi(0) / chi(k_1) - 1), the second-moment correlation length in units of
+    lattice lines.  nan when G < 2 or the ratio is below 1; a chi(k_1) that is zero to rounding -- not above G^2 2^-52 sum |<Q Q'>| / N,
+    the rounding error of its own sum -- has no ratio and gives nan as well."""
+    QQ = np.asarray(QQ, dtype=np.float64)
+    G = QQ.shape[0]
+    chi = chi_of_k(QQ, N)
+    if G < 2:
+        return chi, float('nan')
+    floor = G * G * 2.0 ** -52 * float(np.sum(np.abs(QQ))) / float(N)
+    if not chi[1] > floor or not chi[0] / chi[1] >= 1.0:
+        return chi, float('nan')
+    return chi, float(np.sqrt(chi[0] / chi[1] - 1.0) / (2.0 * np.sin(np.pi / G)))
+
+
+def _line_source(solver, kind):
+    """(what is compared (M, n), lanes16)"""
+    if kind == 'cell':
+        st = np.asarray(solver.states)
+        if st.dtype.kind == 'i' and st.dtype.itemsize < 8:           # as rows_of: int8 cell states are read as unsigned
+            st = st.view('u%d' % st.dtype.itemsize)
+        return st.astype(np.int64), True
+    return spin_bits(solver), False
+
+
+def overlap_correlations(solver, axis='both', kind=None, weights='uniform'):
+    """calculate_overlap_correlations of tnac4o (documented there)."""
+    if axis not in ('x', 'y', 'both'):
+        raise ValueError("axis must be 'x', 'y' or 'both'")
+    if kind == 'link':
+        raise ValueError("kind 'link' has no line-resolved overlap: a coupling lies in two groups")
+    kind, w = check_arguments(solver, kind, weights)
+    axes = ('x', 'y') if axis == 'both' else (axis,)
+    lanes16 = kind == 'cell'
+    per = 4 if lanes16 else 64
+    plan = {}
+    for ax in axes:                                                   # every refusal comes before any device work
+        group, sizes = line_groups(solver, ax, kind)
+        G, wpg = sizes.size, max(1, -(-int(sizes.max()) // per))
+        if G > MAX_GROUPS:
+            raise NotImplementedError("axis '%s' has %d lattice lines; tn_pair_moments takes at most %d groups (its distance table must fit "
+                                      'the 160 KiB of LDS); there is no host fallback' % (ax, G, MAX_GROUPS))
+        if wpg > MAX_GROUP_WORDS:
+            raise NotImplementedError("kind '%s', axis '%s': a lattice line holds %d %s, %d words; tn_pair_moments takes at most %d words per "
+                                      'group; there is no host fallback' % (kind, ax, int(sizes.max()), 'cells' if lanes16 else 'spins', wpg,
+                                                                            MAX_GROUP_WORDS))
+        if int(sizes.sum()) < 1:
+            raise ValueError("kind '%s': the model has nothing to compare" % kind)
+        plan[ax] = (group, sizes, G, wpg)
+    import torch
+    from . import ops
+    X, _ = _line_source(solver, kind)
+    C, mean, chi, xi, xil, nsz = {}, {}, {}, {}, {}, {}
+    for ax in axes:
+        group, sizes, G, wpg = plan[ax]
+        rows, wpg = pack_groups(X, group, G, lanes16)
+        wmax = WMAX // (per * wpg)
+        urows, W, D0 = condense(rows, w)
+        wq, keep, scale = quantise(W, wmax)
+        urows, wq = np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep])
+        if urows.shape[0] >= 2:
+            d_rows = torch.as_tensor(urows.view(np.int64)).cuda()
+            d_w = None if np.all(wq == 1) else torch.as_tensor(wq.view(np.int32)).cuda()
+            limbs = ops.pair_moments(d_rows, G, wpg, d_w, wmax, lanes16).cpu().numpy()
+        else:                                        # one distinct row: every pair sits in D0
+            limbs = np.zeros((G + 1, G + 1, 2), dtype=np.int64)
+        Q1, QQ = second_moments(limbs, sizes, kind, scale, D0)
+        nf = np.where(sizes > 0, sizes, 1).astype(np.float64)
+        empty = sizes == 0
+        mean[ax] = np.where(empty, np.nan, Q1 / nf)
+        C[ax] = np.where(empty[:, None] | empty[None, :], np.nan, QQ / np.outer(nf, nf))
+        chi[ax], xi[ax] = correlation_length(QQ, int(sizes.sum()))
+        xil[ax] = xi[ax] / G
+        nsz[ax] = sizes.copy()
+    solver.overlap_line_kind = kind
+    solver.overlap_line_correlations = C
+    solver.overlap_line_mean = mean
+    solver.overlap_line_sizes = nsz
+    solver.overlap_chi = chi
+    solver.overlap_xi = xi
+    solver.overlap_xi_over_L = xil
+    solver.overlap_ess = effective_sample_size(w)
+    return C

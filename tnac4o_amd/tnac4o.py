@@ -1451,6 +1451,23 @@ class tnac4o:
         from . import overlap
         return overlap.overlap_distribution(self, kind, weights)
 
+    def calculate_overlap_correlations(self, axis='both', kind=None, weights='uniform'):
+        """Overlap correlations between the lattice lines, from all pairs of distinct rows of `states` (whatever wrote them), and the
+        second-moment correlation length of the overlap.  The line overlap q_g of a replica pair is the overlap restricted to model
+        column g (axis 'x') or model row g (axis 'y'): for kind 'spin' (Ising default) the mean of s_a s_b over the active spins of
+        the line, for 'cell' (RMF default) the fraction of its cells in the same state; 'link' is a ValueError (a coupling lies in
+        two lines).  weights as calculate_overlap_distribution.  Per axis, one call of tn_pair_moments gives the exact integer sums
+        of w_a w_b, w_a w_b d_g and w_a w_b d_g d_g' over the pairs (tnac4o_amd/overlap.py).
+        Returns and stores overlap_line_correlations {'x': (Nx, Nx), 'y': (Ny, Ny)} = <q_g q_g'> (only the axes asked for; nan for a
+        line without spins); stores overlap_line_mean = <q_g>, overlap_line_sizes = n_g, overlap_chi[axis][m] = chi_SG(k_m) =
+        (1 / N) sum <Q_g Q_g'> cos(k_m (g - g')) with Q_g = n_g q_g, k_m = 2 pi m / G, m = 0 .. G // 2 (chi(0) of 'spin' is chi_sg
+        of calculate_overlap_distribution), overlap_xi = 1 / (2 sin(pi / G)) sqrt(chi(0) / chi(k_1) - 1) (nan when G < 2 or the
+        ratio is below 1), overlap_xi_over_L = xi / G, overlap_line_kind and overlap_ess.  More than 64 lines along an axis, or a
+        line wider than 32 words (2048 spins, 128 cells), is a NotImplementedError naming the limit, raised before any device
+        work; there is no host fallback.  Changes nothing else."""
+        from . import overlap
+        return overlap.overlap_correlations(self, axis, kind, weights)
+
     # ------------------------------------------------------------------------------------ output
     def binary_states(self, number=-1):
         """Bit strings: 1 spin up, 0 spin down, 2 inactive (tnac4o.py:261-288)."""
