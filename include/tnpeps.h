@@ -133,13 +133,17 @@ int tn_svd_trunc(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n
                  int64_t urs, int64_t ucs, double* S, double* Vt, int64_t vrs, int64_t vcs, int64_t* keep_host,
                  double* discarded_host, int* sweeps_host, int* info_host, void* ws, int64_t ws_bytes, void* stream);
 /* ---- K5: singular values only, sorted descending, min(k,n) values written to HOST memory.
- * Replaces mps.svd_S (mps.py:62-73) as used by MPS.update_S (:550-560). */
+ * Replaces mps.svd_S (mps.py:62-73) as used by MPS.update_S (:550-560).
+ * With both dimensions <= 64 (one launch) the input is scaled by a power of two inside the kernel: the full double range is served,
+ * and S(2^e C) = 2^e S(C) bit for bit while nothing leaves the range.  A NaN or Inf entry: -2, "svd: non-finite input". */
 int tn_svdvals(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* S_host, int* sweeps_host,
                int* info_host, void* ws, int64_t ws_bytes, void* stream);
 int64_t tn_svd_ws_bytes(int64_t k, int64_t n, int vectors);
 /* K5 without the read-back, for centre matrices with both dimensions <= 64 (the Schmidt-value checks of the variational sweeps,
  * mps.py:550-560, whose results are only needed at the end of a sweep): one asynchronous launch; out66_dev (DEVICE) receives 64
- * values sorted descending (zero padded), then the executed sweeps and a convergence flag (1 = converged) as doubles. */
+ * values sorted descending (zero padded), then the executed sweeps and a convergence flag (1 = converged) as doubles.  Same range
+ * as tn_svdvals; a NaN or Inf entry leaves 64 NaN values, sweeps 0 and flag 0 (the return code cannot know: the caller tests the
+ * flag and the values, and takes such a matrix to tn_svdvals).  tn_svdvals_small_batched: per item, the others are unaffected. */
 int tn_svdvals_async(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* out66_dev, void* stream);
 /* The same for `batch` centre matrices in ONE launch (one workgroup each): the Schmidt spectra of a whole variational sweep
  * (mps.py:550-560) are only compared at its end, so they are taken together after it.  Item i is described by 5 int64

@@ -109,7 +109,10 @@ __global__ __launch_bounds__(256) void svd_gather_kernel(const double* __restric
 // pairs per step, 8 threads per pair (8 consecutive elements of both rows each; the three inner products meet through
 // three xor-shuffles, every lane derives the same rotation).  Rows below 2^-56 of the largest are zeroed first, sweeps
 // repeat until one passes without a rotation above 4e-15 (the block path's criterion).  out: 64 values sorted
-// descending, out[64] = sweeps, out[65] = 1 if converged.  (A 128-row variant was tried: one workgroup then spends 2 ms on a
+// descending, out[64] = sweeps, out[65] = 1 if converged.  The entries are scaled by a power of two on the way in and the values
+// back on the way out, so the whole double range is served with the bits of the in-range case; a NaN or Inf entry gives 64 NaN
+// values, sweeps = 0 and converged = 0 (svd_vals turns that into -2, the asynchronous callers into the synchronous path).
+// (A 128-row variant was tried: one workgroup then spends 2 ms on a
 // 128 x 128 matrix against 0.9 ms for the block path, so 64 is the limit of the fused form.)
 __device__ __forceinline__ void rr_pair64(int s, int a, int& p, int& q) {
     if (a == 0) { p = 63; q = s; }
@@ -122,6 +125,7 @@ __device__ __forceinline__ void svd_vals_small_body(const double* __restrict__ M
     constexpr int NV = 64, P = 66;            // even pitch: 16-byte aligned 8-element segments
     const int tid = threadIdx.x, slot = tid >> 3, sub = tid & 7;
     double relevant2 = 0.0;
+    int ex = 0;
     {
         double xv[16];
 #pragma unroll
@@ -129,10 +133,21 @@ __device__ __forceinline__ void svd_vals_small_body(const double* __restrict__ M
             const int e = tid + 256 * t, r = e >> 6, c = e & 63;
             xv[t] = (r < nv && c < L) ? M[(int64_t)r * vs + (int64_t)c * es] : 0.0;
         }
+        // entries scaled into [0.5, 1) by a power of two, as svd_trunc_small_kernel does (squares of squares must neither overflow nor
+        // underflow; exact, so inputs that were in range keep their bits); NaN / Inf pass through to the norm check below
+        double mx = 0.0;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) { const double a = fabs(xv[t]); mx = (a < 1.7e308) ? fmax(mx, a) : mx; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+        if ((tid & 63) == 0) nrm[tid >> 6] = mx;
+        __syncthreads();
+        mx = fmax(fmax(nrm[0], nrm[1]), fmax(nrm[2], nrm[3]));
+        if (mx > 0.0) frexp(mx, &ex);
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const int e = tid + 256 * t;
-            X[(e >> 6) * P + (e & 63)] = xv[t];
+            X[(e >> 6) * P + (e & 63)] = ldexp(xv[t], -ex);      // (ldexp, not a product: 2^-ex itself leaves the range for subnormal input)
         }
     }
     __syncthreads();
@@ -151,7 +166,13 @@ __device__ __forceinline__ void svd_vals_small_body(const double* __restrict__ M
         if (sub == 0) { nrm[2 * slot] = a; nrm[2 * slot + 1] = b; }
         __syncthreads();
         double nmax = 0.0;
-        for (int r = 0; r < NV; ++r) nmax = fmax(nmax, nrm[r]);
+        bool bad = false;
+        for (int r = 0; r < NV; ++r) { nmax = fmax(nmax, nrm[r]); bad = bad || !(nrm[r] == nrm[r]) || nrm[r] > 1.7e308; }
+        if (bad) {                                               // non-finite input (uniform): NaN values, not converged
+            if (tid < NV) out[tid] = __longlong_as_double(0x7ff8000000000000LL);
+            if (tid == 0) { out[64] = 0.0; out[65] = 0.0; }
+            return;
+        }
         const double thr = nmax * 1.9259299443872359e-34;       // (2^-56)^2
         relevant2 = nmax * 3.0814879110195774e-33;              // (2^-54)^2: see jacobi_core
         if (!(a > thr)) {
@@ -216,7 +237,7 @@ __device__ __forceinline__ void svd_vals_small_body(const double* __restrict__ M
             const double mine = nrm[tid];
             int rank = 0;
             for (int r = 0; r < NV; ++r) rank += (nrm[r] > mine || (nrm[r] == mine && r < tid)) ? 1 : 0;
-            out[rank] = sqrt(mine);
+            out[rank] = ldexp(sqrt(mine), ex);
         }
         if (tid == 0) { out[64] = (double)sweeps; out[65] = (double)converged; }
     }
