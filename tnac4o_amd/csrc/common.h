@@ -145,6 +145,17 @@ static inline int gemm(hipStream_t st, int64_t M, int64_t N, int64_t K, double a
                        double* ws = nullptr, int64_t ws_bytes = 0) {
     return gemm(st, M, N, K, alpha, A.p, A.rs, A.cs, B.p, B.rs, B.cs, beta, C.p, C.rs, C.cs, 1, 0, 0, 0, ws, ws_bytes);
 }
+// the profiling family (PROF_GEMM_*) under which gemm books an unbatched M x N x K product with these strides of C
+int gemm_prof_family(int64_t M, int64_t N, int64_t K, int64_t rsc, int64_t csc);
+
+// ---- rank-b update of a trailing matrix (rank_update.hip): the K <= 32 products of the QR panel loops ---------------------------
+// C (m x n) -= W (m x b) X (b x n), 1 <= b <= 32, element strides; bit for bit what gemm(..., -1.0, W, X, 1.0, C) computes.
+// active (DEVICE, may be null): *active == 0 -> nothing is written
+int rank_update(hipStream_t st, int64_t m, int64_t n, int b, const double* W, int64_t wrs, int64_t wcs, const double* X, int64_t xrs,
+                int64_t xcs, double* C, int64_t rsc, int64_t csc, const int* active);
+static inline int rank_update(hipStream_t st, int64_t m, int64_t n, int b, Mat W, Mat X, Mat C, const int* active = nullptr) {
+    return rank_update(st, m, n, b, W.p, W.rs, W.cs, X.p, X.rs, X.cs, C.p, C.rs, C.cs, active);
+}
 
 // ---- small dense kernels (small.hip) ------------------------------------------------------------
 constexpr int NBMAX = 64;      // largest panel / Jacobi pair width handled by the single-workgroup kernels

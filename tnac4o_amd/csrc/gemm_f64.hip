@@ -275,7 +275,9 @@ static GemmPlan plan_gemm(int64_t M, int64_t N, int64_t K, int64_t batch) {
     static const int64_t small_work = (int64_t)1 << env_int("TN_GEMM_SMALLWORK_LOG2", 30);
     // small products: 128 x 128 tiles from this many workgroups on.  Round 5: never (was 128) -- the small products with hundreds of big
     // tiles are the rank-32 updates of the panel loops, HBM round trips of the trailing matrix with two K steps of arithmetic: four times
-    // the workgroups hide their prologues behind each other's epilogues (first pass -2.4 %, four chains 425.8 -> 418.1 ms/sweep)
+    // the workgroups hide their prologues behind each other's epilogues (first pass -2.4 %, four chains 425.8 -> 418.1 ms/sweep).
+    // The panel loops of qr.hip now send those updates to rank_update_kernel (rank_update.hip), which keeps these 64 x 64 tiles; the
+    // setting still serves the launches TN_QR_RANK_UPDATE=0 restores and the other small products with hundreds of tiles.
     static const int big_tiles = env_int("TN_GEMM_BIGTILES", 1 << 30);
     static const int target_wg = env_int("TN_GEMM_TARGETWG", 256);
     static const int min_chunk = env_int("TN_GEMM_MINCHUNK", 32);
@@ -307,6 +309,20 @@ static GemmPlan plan_gemm(int64_t M, int64_t N, int64_t K, int64_t batch) {
         p.s = s < 2 ? 1 : (int)s;
     }
     return p;
+}
+
+static int tile_family(const GemmPlan& p) {
+    return (p.bm == 128 && p.bn == 128) ? PROF_GEMM_128x128 : (p.bm == 128) ? PROF_GEMM_128x32 : (p.bm == 32) ? PROF_GEMM_32x128 : PROF_GEMM_64x64;
+}
+
+// column-major C is computed as the transposed product (see gemm_ex_impl)
+static bool swaps_roles(int64_t N, int64_t rsc, int64_t csc) {
+    static const bool swap_on = env_flag_on("TN_GEMM_SWAP");
+    return swap_on && rsc == 1 && csc != 1 && N > 1;
+}
+
+int gemm_prof_family(int64_t M, int64_t N, int64_t K, int64_t rsc, int64_t csc) {
+    return tile_family(swaps_roles(N, rsc, csc) ? plan_gemm(N, M, K, 1) : plan_gemm(M, N, K, 1));
 }
 
 int gemm_forced_split(int64_t K, int s, int64_t* kchunk) {
@@ -403,8 +419,7 @@ static int gemm_ex_impl(hipStream_t st, int64_t M, int64_t N, int64_t K, double 
     // 16 separate 32-byte pieces per instruction there.  The transposed product C^T = B^T A^T is the same arithmetic in the same
     // order (element by element: the same K sequence, the same splits) with C^T row-major -- full 128-byte segments.  Not for the
     // block-pair indirection / raw partials of the Jacobi SVD, whose index maps and partial layout are tied to the operand roles.
-    static const bool swap_on = env_flag_on("TN_GEMM_SWAP");
-    if (swap_on && rsc == 1 && csc != 1 && N > 1 && !(x && (x->pairs || x->raw_partials)))          // (skip flags are per batch item: they follow)
+    if (swaps_roles(N, rsc, csc) && !(x && (x->pairs || x->raw_partials)))          // (skip flags are per batch item: they follow)
         return gemm_ex_impl(st, N, M, K, alpha, B, csb, rsb, A, csa, rsa, beta, C, csc, rsc, batch, bsb, bsa, bsc, ws, ws_bytes, x);
     GemmP g;
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;
@@ -439,8 +454,7 @@ static int gemm_ex_impl(hipStream_t st, int64_t M, int64_t N, int64_t K, double 
     }
     const bool ak = (csa == 1 && rsa != 1), bk = (rsb == 1 && csb != 1);
     dim3 grid(g.tiles_m * g.tiles_n, 1, (unsigned)(batch * s));
-    const int fam = (bm == 128 && bn == 128) ? PROF_GEMM_128x128 : (bm == 128) ? PROF_GEMM_128x32
-                    : (bm == 32) ? PROF_GEMM_32x128 : PROF_GEMM_64x64;
+    const int fam = tile_family(pl);
     prof_begin(st, fam);
     if (bm == 128 && bn == 128) launch_tile<128, 128, 16>(st, g, grid, ak, bk);
     else if (bm == 128 && bn == 32) launch_tile<128, 32, 16>(st, g, grid, ak, bk);

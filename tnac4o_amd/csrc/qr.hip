@@ -792,6 +792,7 @@ static int qr_two_level(hipStream_t st, Mat Am, int64_t m, int64_t n, int64_t k,
                         int64_t rcs, int* fused_base) {
     const int nb = 32;
     int rc;
+    const bool ru_on = env_flag_on("TN_QR_RANK_UPDATE");          // (as in qr_factor_impl)
     const int nblk = (int)cdiv(k, nbo);
     for (int bi = 0; bi < nblk; ++bi) {
         const int64_t J0 = (int64_t)bi * nbo;
@@ -817,7 +818,7 @@ static int qr_two_level(hipStream_t st, Mat Am, int64_t m, int64_t n, int64_t k,
                 return rc;
             Mat Xm = mat(w.X, nin, 1);
             if ((rc = gemm(st, b, nin, mp, 1.0, tr(Yp), Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            if ((rc = gemm(st, mp, nin, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
+            if ((rc = ru_on ? rank_update(st, mp, nin, b, Wp, Xm, Ap) : gemm(st, mp, nin, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
             // T_blk: diagonal block = T_p (its pitch is b); column block from the recurrence once the Gram matrix exists (below)
             if ((rc = copy_mat(st, Tp, b, 1, Tb + (int64_t)(j0 - J0) * bw + (j0 - J0), bw, 1, b, b))) return rc;
         }
@@ -1345,6 +1346,9 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
     }
     // device-side panel pivoting (see pivot_select_kernel): the host runs one panel ahead of the verdicts it reads back
     const bool piv_dev_on = env_flag_on("TN_PIVOT_DEVICE");      // (read per call: the tests switch it)
+    // the rank-32 updates of the panels (trailing matrix and Q) through rank_update (rank_update.hip) instead of a K = 32 launch of gemm:
+    // the same bits (TN_QR_RANK_UPDATE=0 restores gemm; read per call: the tests switch it).  The 64-wide panels keep gemm.
+    const bool ru_on = nb == 32 && env_flag_on("TN_QR_RANK_UPDATE");
     const bool piv_dev = pivot && piv_dev_on && n <= PIV_MAXN;
     PivState* pst = (PivState*)w.piv;
     int* pperm = (int*)(w.piv + 1024);
@@ -1476,10 +1480,12 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
             if ((rc = gemm_ex(st, b, ntr, mp, 1.0, Yt.p, Yt.rs, Yt.cs, Ap.p, Ap.rs, Ap.cs, 0.0, Xm.p, Xm.rs, Xm.cs, 1, 0, 0, 0, w.gemm_ws, w.gemm_ws_bytes,
                               &gx_active)))
                 return rc;
-            if ((rc = gemm_ex(st, mp, ntr, b, -1.0, Wp.p, Wp.rs, Wp.cs, Xm.p, Xm.rs, Xm.cs, 1.0, Ap.p, Ap.rs, Ap.cs, 1, 0, 0, 0, nullptr, 0, &gx_active))) return rc;
+            if ((rc = ru_on ? rank_update(st, mp, ntr, b, Wp, Xm, Ap, active)
+                            : gemm_ex(st, mp, ntr, b, -1.0, Wp.p, Wp.rs, Wp.cs, Xm.p, Xm.rs, Xm.cs, 1.0, Ap.p, Ap.rs, Ap.cs, 1, 0, 0, 0, nullptr, 0, &gx_active)))
+                return rc;
         } else {
             if ((rc = gemm(st, b, ntr, mp, 1.0, tr(Yp), Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            if ((rc = gemm(st, mp, ntr, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
+            if ((rc = ru_on ? rank_update(st, mp, ntr, b, Wp, Xm, Ap) : gemm(st, mp, ntr, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
         }
         if (reveal && (p & 1) == 1 && p + 1 < P) {
             const int64_t j1 = j0 + b;
@@ -1584,7 +1590,8 @@ static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int
         Mat Xm = mat(w.X, nq, 1);
         // Y^T Q (the last panel meets [Z; 0]: only its top b rows are non-zero, the product over the rest adds zeros)
         if ((rc = gemm(st, b, nq, p == P - 1 ? (int64_t)b : mp, 1.0, tr(wform ? Wqp : Yp), Qp, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-        if ((rc = gemm(st, mp, nq, b, -1.0, wform ? Yp : Wqp, Xm, 1.0, Qp))) return rc;                     // Q -= (Y T) (Y^T Q) = Y (W^T Q)
+        // Q -= (Y T) (Y^T Q) = Y (W^T Q)
+        if ((rc = ru_on ? rank_update(st, mp, nq, b, wform ? Yp : Wqp, Xm, Qp) : gemm(st, mp, nq, b, -1.0, wform ? Yp : Wqp, Xm, 1.0, Qp))) return rc;
     }
     return 0;
 }
