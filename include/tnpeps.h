@@ -552,6 +552,24 @@ int64_t tn_pair_moments_ws_bytes(int64_t M, int64_t G, int64_t wpg, int lanes16)
 int tn_pair_moments(const uint64_t* rows, int64_t M, int64_t G, int64_t wpg, int64_t ldr, const uint32_t* weights, uint32_t wmax, int lanes16,
                     uint64_t* out, void* ws, int64_t ws_bytes, void* stream);
 
+/* tn_spin_moments: for every pair of BITS of the rows, the weight of the samples in which they differ (no counterpart in the reference:
+ * the sample correlations <s_i s_j> of all pairs of spins, tnac4o.calculate_sample_correlations).  rows (DEVICE) = M rows of nbits bits in
+ * tn_pair_hist's layout (lanes16 = 0) at a stride of ldr words: whatever lies beyond nbits in the last word is masked, the words
+ * ceil(nbits / 64) .. ldr-1 of a row are never read.  weights (DEVICE, M uint32; NULL = all 1); a weight above wmax is read as wmax, and
+ * only the P = bit length of wmax weight bit-planes are processed (NULL weights: P = 1 whatever wmax).  With n = nbits and two constant
+ * pseudo-bits x_a,n = 0 and x_a,n+1 = 1 appended to every row, out (DEVICE, (n+2) x (n+2) uint64 at a row stride of ldo entries) is
+ * out[i][j] = sum_a w_a [x_a,i != x_a,j]: symmetric with a zero diagonal, out[i][n] = sum_a w_a x_a,i, out[i][n+1] = sum_a w_a (1 - x_a,i),
+ * out[n][n+1] = sum_a w_a.  Every entry with i, j < n + 2 is written, nothing beyond column n+1 of a row; M = 0 gives zeros.  One limb
+ * suffices: an entry is at most M (2^32 - 1) < 2^64 for M < 2^32, and a larger M is refused.  An integer function of the inputs:
+ * bit-identical for every grid size, slicing and run (no atomics and no floating point).
+ * ws: 8-byte aligned, tn_spin_moments_ws_bytes (which reads TN_SPIN_MOMENTS_WGS as the call does; 0 for a shape the call refuses): the
+ * bit-major transpose of the rows, the weight planes and, with more than one workgroup, two slabs of 4096 partial sums per workgroup.
+ * Asynchronous on `stream`.  Limits: 0 <= M < 2^32; 1 <= nbits <= 65534; wmax >= 1; ldr >= ceil(nbits / 64); ldo >= nbits + 2.
+ * Errors: -1 argument (the message names the limit), -3 workspace too small; both before any launch, nothing is written. */
+int64_t tn_spin_moments_ws_bytes(int64_t M, int64_t nbits, uint32_t wmax);
+int tn_spin_moments(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, uint32_t wmax, uint64_t* out, int64_t ldo,
+                    void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ using namespace tn;
 
 extern "C" {
 
-int tn_version(void) { return 16; }
+int tn_version(void) { return 17; }
 
 #ifndef TN_SRC_HASH
 #define TN_SRC_HASH "unknown"

@@ -14,6 +14,9 @@
 //
 // Second moments of the distances within word groups of the rows (tn_pair_moments), behind tnac4o.calculate_overlap_correlations:
 // described where its kernels start, further down.
+//
+// Weighted counts of the samples in which two bits of the rows differ, for every pair of bits (tn_spin_moments), behind
+// tnac4o.calculate_sample_correlations: behind the kernels of tn_pair_moments.
 #include "common.h"
 
 namespace tn {
@@ -388,6 +391,272 @@ void pair_moments_launch_ept(int ne, A... a) {
     else pair_moments_launch<LANES16, PM_EPT_LARGE>(a...);
 }
 
+// ---- tn_spin_moments: out[i][j] = sum_a w_a [x_a,i != x_a,j] over every pair of BITS i, j of the rows, two constant pseudo-bits appended -
+// The Gram matrix of the rows over the sample index.  spin_transpose_kernel turns the sample-major rows into the bit-major matrix T:
+// row i of T holds bit i of the samples 64 c .. 64 c + 63 in word c (KW = ceil(M / 64) words; NB blocks of 64 rows; row n is the
+// constant 0, row n + 1 the constant 1, the rows behind them 0), and the weights into P = bit length of wmax plane words
+// Wp[p][c] = bit p of min(w_a, wmax) of those samples (0 for a sample >= M, so nothing else needs a mask).  A wave holds word wb of 64
+// samples; ballot b is row 64 wb + b of T, kept by lane b and written through LDS so that a row's 16 words leave as one segment.
+// spin_moments_kernel is pair_hist_kernel's loop run on T: tiles of 64 x 64 bits of the upper triangle, 256 threads, 4 x 4 each, both
+// blocks staged word-major as stage_block does, the chunk's plane words next to them, each chunk fetched into registers while the one
+// before it is counted; per word and pair sum_p 2^p popcount((a ^ b) & Wp[p]) by
+// Horner over the planes in two halves of at most 16 planes (64 (2^16 - 1) < 2^22 per word and half, 16 words of a chunk < 2^26 in 32
+// bits), folded into 16 uint64 sums once per chunk.  The unit of work is (tile, chunk of 16 words), tile-major, and the persistent grid
+// cuts the sequence of all units into equal contiguous shares, one per workgroup, so that every workgroup has the same work whatever
+// the number of tiles (6 at n = 128).  A share is the end of one tile, whole tiles, and the start of another: a whole tile is written
+// into out, [i][j] and [j][i]; the at most two part tiles of workgroup g go to the slabs 2 g (its first piece) and 2 g + 1 of 4096
+// partial sums, and spin_moments_reduce_kernel adds the pieces of every tile that was cut.  Integer adds, no atomics: the same integers
+// for every grid.
+constexpr int SM_TC = 16;                        // word columns of T (blocks of 64 samples) per workgroup of the transposition
+constexpr int SM_TPITCH = SM_TC + 1;
+constexpr int SM_MAX_P = 32;
+constexpr int64_t SM_MAX_NBITS = 65534;          // n + 2 <= 2^16: at most 1024 blocks of 64 rows of T
+constexpr int64_t SM_TILE_WORDS = PH_TILE * PH_TILE;
+
+__global__ __launch_bounds__(256) void spin_transpose_kernel(const uint64_t* __restrict__ rows, int64_t M, int64_t nbits, int64_t nwords, int64_t ldr,
+                                                             uint64_t last_mask, const uint32_t* __restrict__ weights, uint32_t wmax, int P, int64_t NB,
+                                                             int64_t KW, uint64_t* __restrict__ T, uint64_t* __restrict__ Wp) {
+    __shared__ uint64_t tile[64 * SM_TPITCH];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t wb = blockIdx.y, c0 = (int64_t)blockIdx.x * SM_TC;
+    const bool planes = wb == NB;                // the last grid row makes the weight planes
+    for (int q = 0; q < SM_TC / 4; ++q) {
+        const int cl = wave * (SM_TC / 4) + q;
+        const int64_t a = (c0 + cl) * 64 + lane;
+        const bool valid = a < M;
+        uint64_t v = 0;
+        if (planes) {
+            if (valid) v = weights ? (uint64_t)min(weights[a], wmax) : 1u;
+        } else {
+            if (valid && wb < nwords) {
+                v = rows[a * ldr + wb];
+                if (wb == nwords - 1) v &= last_mask;
+            }
+            if (valid && (nbits + 1) / 64 == wb) v |= (uint64_t)1 << ((nbits + 1) & 63);          // the constant 1; bit n stays 0
+        }
+        uint64_t mine = 0;
+#pragma unroll
+        for (int b = 0; b < 64; ++b) {
+            const uint64_t m = __ballot((int)((v >> b) & 1u));
+            if (lane == b) mine = m;
+        }
+        tile[lane * SM_TPITCH + cl] = mine;
+    }
+    __syncthreads();
+    const int nrow = planes ? P : 64;
+    uint64_t* dst = planes ? Wp : T + wb * 64 * KW;
+    for (int e = tid; e < nrow * SM_TC; e += 256) {
+        const int r = e / SM_TC, cl = e % SM_TC;
+        if (c0 + cl < KW) dst[(int64_t)r * KW + c0 + cl] = tile[r * SM_TPITCH + cl];
+    }
+}
+
+// UNIT: one plane (wmax = 1 or no weights)
+template <bool UNIT>
+__global__ __launch_bounds__(256) void spin_moments_kernel(const uint64_t* __restrict__ T, const uint64_t* __restrict__ Wp, int64_t KW,
+                                                           int P, int64_t ntiles, int64_t nchunks, int64_t nrows, uint64_t* __restrict__ out,
+                                                           int64_t ldo, uint64_t* __restrict__ slabs) {
+    __shared__ uint64_t sA[PH_CW * PH_PITCH], sB[PH_CW * PH_PITCH], sW[PH_CW * SM_MAX_P];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int64_t total = ntiles * nchunks;                            // units (tile, chunk), tile-major; this workgroup's share:
+    const int64_t end = ((int64_t)blockIdx.x + 1) * total / gridDim.x;
+    const int plo = min(P, 16);
+    int piece = 0;
+    for (int64_t u = (int64_t)blockIdx.x * total / gridDim.x; u < end; ++piece) {
+        const int64_t t = u / nchunks, c0 = u % nchunks, c1 = c0 + end - u < nchunks ? c0 + end - u : nchunks;
+        u += c1 - c0;
+        int64_t bj = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);        // as pair_hist_kernel
+        while (bj > 0 && bj * (bj + 1) / 2 > t) --bj;
+        while ((bj + 1) * (bj + 2) / 2 <= t) ++bj;
+        const int64_t bi = t - bj * (bj + 1) / 2;
+        const int64_t a0 = bi * PH_TILE, b0 = bj * PH_TILE;
+        uint64_t acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = 0;
+        // the thread's words of a chunk, in stage_block's layout: word k = tid % 16 of the rows tid / 16 + 16 q of both blocks, and two
+        // of the chunk's plane words; fetched into registers a chunk ahead, so that the loads are in flight under the popcounts
+        uint64_t ra[4], rb[4], rw[2];
+        auto fetch = [&](int64_t ch) {
+            const int64_t w = ch * PH_CW + (tid & (PH_CW - 1));
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t r = tid / PH_CW + (256 / PH_CW) * q;
+                ra[q] = w < KW ? T[(a0 + r) * KW + w] : 0;
+                rb[q] = w < KW ? T[(b0 + r) * KW + w] : 0;
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int e = tid + 256 * q, k = e / P, p = e % P;
+                rw[q] = e < PH_CW * P && ch * PH_CW + k < KW ? Wp[(int64_t)p * KW + ch * PH_CW + k] : 0;
+            }
+        };
+        fetch(c0);
+        for (int64_t ch = c0; ch < c1; ++ch) {
+            __syncthreads();                                   // the previous chunk has been read
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int at = (tid & (PH_CW - 1)) * PH_PITCH + tid / PH_CW + (256 / PH_CW) * q;
+                sA[at] = ra[q];
+                sB[at] = rb[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int e = tid + 256 * q;
+                if (e < PH_CW * P) sW[(e / P) * SM_MAX_P + e % P] = rw[q];
+            }
+            __syncthreads();
+            if (ch + 1 < c1) fetch(ch + 1);
+            unsigned s0[4][4], s1[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s0[i][j] = s1[i][j] = 0;
+#pragma unroll 1                                               // (unrolled, the 16 x 6 operations of a word cost the third workgroup its registers)
+            for (int k = 0; k < PH_CW; ++k) {
+                uint64_t x[4][4];
+                {
+                    uint64_t a[4], b[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        a[i] = sA[k * PH_PITCH + ty * 4 + i];
+                        b[i] = sB[k * PH_PITCH + tx * 4 + i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) x[i][j] = a[i] ^ b[j];
+                }
+                if (UNIT) {
+                    const uint64_t w = sW[k * SM_MAX_P];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) s0[i][j] += (unsigned)__popcll(x[i][j] & w);
+                } else {
+                    unsigned h[4][4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) h[i][j] = 0;
+                    for (int p = P - 1; p >= 16; --p) {        // planes 16 .. P-1, in units of 2^16
+                        const uint64_t w = sW[k * SM_MAX_P + p];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) h[i][j] = 2 * h[i][j] + (unsigned)__popcll(x[i][j] & w);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            s1[i][j] += h[i][j];
+                            h[i][j] = 0;
+                        }
+                    for (int p = plo - 1; p >= 0; --p) {       // planes 0 .. 15
+                        const uint64_t w = sW[k * SM_MAX_P + p];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) h[i][j] = 2 * h[i][j] + (unsigned)__popcll(x[i][j] & w);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) s0[i][j] += h[i][j];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] += (uint64_t)s0[i][j] + ((uint64_t)s1[i][j] << 16);
+        }
+        if (c0 > 0 || c1 < nchunks) {                          // part of a tile: the first piece of the share, or its last
+            uint64_t* slab = slabs + (2 * (int64_t)blockIdx.x + (piece ? 1 : 0)) * SM_TILE_WORDS;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) slab[(ty * 4 + i) * PH_TILE + tx * 4 + j] = acc[i][j];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int64_t gi = a0 + ty * 4 + i, gj = b0 + tx * 4 + j;
+                    if (gi < nrows && gj < nrows) {
+                        out[gi * ldo + gj] = acc[i][j];
+                        if (bi != bj) out[gj * ldo + gi] = acc[i][j];          // (a diagonal tile holds both triangles itself)
+                    }
+                }
+        }
+    }
+}
+
+// share of workgroup g of the nwg: units [spin_share(g), spin_share(g + 1))
+__host__ __device__ __forceinline__ int64_t spin_share(int64_t g, int64_t total, int64_t nwg) { return g * total / nwg; }
+
+// out[i][j] (and out[j][i] off the diagonal tiles) = entry (r, c) of tile t summed over its pieces, for every tile that was cut.  The
+// workgroups that hold units of tile t, [t nchunks, (t + 1) nchunks), are consecutive; a tile that one of them holds whole is in out
+// already.  The piece of workgroup g is in slab 2 g when its share starts inside the tile, else in slab 2 g + 1.
+__global__ __launch_bounds__(256) void spin_moments_reduce_kernel(const uint64_t* __restrict__ slabs, int64_t ntiles, int64_t nchunks, int64_t nwg,
+                                                                  int64_t nrows, uint64_t* __restrict__ out, int64_t ldo) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ntiles * SM_TILE_WORDS) return;
+    const int64_t t = e / SM_TILE_WORDS, total = ntiles * nchunks, lo = t * nchunks, hi = lo + nchunks;
+    int64_t g = lo * nwg / total;                                      // the workgroup that holds unit lo
+    while (g > 0 && spin_share(g, total, nwg) > lo) --g;
+    while (spin_share(g + 1, total, nwg) <= lo) ++g;
+    if (spin_share(g + 1, total, nwg) >= hi) return;                   // (it starts at or before lo: the tile is whole)
+    const int r = (int)(e % SM_TILE_WORDS) / PH_TILE, c = (int)(e % PH_TILE);
+    int64_t bj = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (bj > 0 && bj * (bj + 1) / 2 > t) --bj;
+    while ((bj + 1) * (bj + 2) / 2 <= t) ++bj;
+    const int64_t bi = t - bj * (bj + 1) / 2;
+    const int64_t gi = bi * PH_TILE + r, gj = bj * PH_TILE + c;
+    if (gi >= nrows || gj >= nrows) return;
+    uint64_t s = 0;
+    for (; g < nwg && spin_share(g, total, nwg) < hi; ++g)
+        s += slabs[(2 * g + (spin_share(g, total, nwg) >= lo ? 0 : 1)) * SM_TILE_WORDS + r * PH_TILE + c];
+    out[gi * ldo + gj] = s;
+    if (bi != bj) out[gj * ldo + gi] = s;
+}
+
+inline int spin_moments_planes(uint32_t wmax) {
+    int P = 0;
+    while (wmax) {
+        ++P;
+        wmax >>= 1;
+    }
+    return P;
+}
+inline bool spin_moments_shape_ok(int64_t M, int64_t nbits, uint32_t wmax) {
+    return M >= 0 && M < ((int64_t)1 << 32) && nbits >= 1 && nbits <= SM_MAX_NBITS && wmax >= 1;
+}
+struct SpinMomentsPlan {
+    int64_t NB, KW, ntiles, nchunks, nwg;
+    int P;
+    int64_t t_words, w_words, slab_words;
+};
+// The persistent grid: TN_SPIN_MOMENTS_WGS (read per call) or what the registers admit on the 256 compute units, 3 workgroups each with
+// one plane (160 VGPRs) and 2 with more (234); never more than there are units.  M = 0 keeps one chunk (of zeros) per tile.
+inline SpinMomentsPlan spin_moments_plan(int64_t M, int64_t nbits, uint32_t wmax) {
+    SpinMomentsPlan p;
+    p.NB = cdiv(nbits + 2, PH_TILE);
+    p.KW = cdiv(M, 64);
+    p.P = spin_moments_planes(wmax);
+    p.ntiles = p.NB * (p.NB + 1) / 2;
+    int64_t g = env_i64("TN_SPIN_MOMENTS_WGS", 0);
+    if (g <= 0) g = 256 * (p.P == 1 ? 3 : 2);
+    g = std::min<int64_t>(g, PH_MAX_WGS);
+    p.nchunks = std::max<int64_t>(1, cdiv(p.KW, PH_CW));
+    p.nwg = std::min<int64_t>(g, p.ntiles * p.nchunks);
+    p.t_words = p.NB * PH_TILE * p.KW;
+    p.w_words = (int64_t)p.P * p.KW;
+    p.slab_words = p.nwg > 1 ? 2 * p.nwg * SM_TILE_WORDS : 0;
+    return p;
+}
+
 }  // namespace
 
 }  // namespace tn
@@ -484,6 +753,59 @@ int tn_pair_moments(const uint64_t* rows, int64_t M, int64_t G, int64_t wpg, int
     TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(pair_moments_reduce_kernel, dim3((unsigned)cdiv(ne, 256)), dim3(256), 0, st, slabs, nwg, (int)G, ne,
                                                      (unsigned long long*)out));
     TN_CHECK_LAUNCH("pair_moments_reduce_kernel");
+    return 0;
+}
+
+int64_t tn_spin_moments_ws_bytes(int64_t M, int64_t nbits, uint32_t wmax) {
+    if (!spin_moments_shape_ok(M, nbits, wmax)) return 0;
+    const SpinMomentsPlan p = spin_moments_plan(M, nbits, wmax);
+    return std::max<int64_t>(16, 8 * (p.t_words + p.w_words + p.slab_words));
+}
+
+int tn_spin_moments(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, uint32_t wmax, uint64_t* out, int64_t ldo,
+                    void* ws, int64_t ws_bytes, void* stream) {
+    TN_CHECK_ARG(M >= 0 && M < ((int64_t)1 << 32), "M negative or not below 2^32 = 4294967296 (an entry, at most M (2^32 - 1), must fit 64 bits)");
+    if (nbits < 1 || nbits > SM_MAX_NBITS) {
+        set_error("tn_spin_moments: nbits = %lld outside 1 .. %lld (n + 2 rows and columns, at most 2^16)", (long long)nbits, (long long)SM_MAX_NBITS);
+        return -1;
+    }
+    TN_CHECK_ARG(wmax >= 1, "wmax must be at least 1");
+    const int64_t nwords = cdiv(nbits, 64), nrows = nbits + 2;
+    TN_CHECK_ARG(rows && out && ws, "null operand");
+    TN_CHECK_ARG(ldr >= nwords, "ldr shorter than a row");
+    TN_CHECK_ARG(ldo >= nrows, "ldo shorter than a row of nbits + 2 entries");
+    const int64_t need = tn_spin_moments_ws_bytes(M, nbits, wmax);
+    if (ws_bytes < need) {
+        set_error("tn_spin_moments: workspace too small (%lld bytes, tn_spin_moments_ws_bytes asks for %lld)", (long long)ws_bytes, (long long)need);
+        return -3;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const SpinMomentsPlan p = spin_moments_plan(M, nbits, wmax);
+    uint64_t* T = (uint64_t*)ws;
+    uint64_t* Wp = T + p.t_words;
+    uint64_t* slabs = Wp + p.w_words;
+    const int P = weights ? p.P : 1;                       // without weights there is one plane, whatever wmax
+    if (p.KW > 0) {
+        const int used = (int)(nbits - (nwords - 1) * 64);
+        const uint64_t last_mask = used == 64 ? ~(uint64_t)0 : (((uint64_t)1 << used) - 1);
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(spin_transpose_kernel, dim3((unsigned)cdiv(p.KW, SM_TC), (unsigned)(p.NB + 1)), dim3(256), 0, st,
+                                                         rows, M, nbits, nwords, ldr, last_mask, weights, wmax, P, p.NB, p.KW, T, Wp));
+        TN_CHECK_LAUNCH("spin_transpose_kernel");
+    }
+    prof_begin(st, PROF_MISC);
+    if (P == 1)
+        hipLaunchKernelGGL(spin_moments_kernel<true>, dim3((unsigned)p.nwg), dim3(256), 0, st, T, Wp, p.KW, P, p.ntiles, p.nchunks, nrows, out,
+                           ldo, slabs);
+    else
+        hipLaunchKernelGGL(spin_moments_kernel<false>, dim3((unsigned)p.nwg), dim3(256), 0, st, T, Wp, p.KW, P, p.ntiles, p.nchunks, nrows, out,
+                           ldo, slabs);
+    prof_end(st, PROF_MISC, 0.0, 0.0);
+    TN_CHECK_LAUNCH("spin_moments_kernel");
+    if (p.nwg > 1) {
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(spin_moments_reduce_kernel, dim3((unsigned)cdiv(p.ntiles * SM_TILE_WORDS, 256)), dim3(256), 0, st,
+                                                         slabs, p.ntiles, p.nchunks, p.nwg, nrows, out, ldo));
+        TN_CHECK_LAUNCH("spin_moments_reduce_kernel");
+    }
     return 0;
 }
 

@@ -1062,3 +1062,37 @@ def pair_moments(rows, G, wpg, weights=None, wmax=None, lanes16=False):
     check(L.tn_pair_moments(rows.data_ptr() if M else ws.data_ptr(), M, G, wpg, max(ld, nwords), weights.data_ptr() if weights is not None else None,
                             wmax, int(bool(lanes16)), out.data_ptr(), ws.data_ptr(), wsb, _stream()))
     return out
+
+
+def spin_moments(rows, nbits, weights=None, wmax=None):
+    """For every pair of bits of packed rows, the weight of the rows in which they differ (tn_spin_moments): rows (M, ld) int64 / uint64
+    device tensor whose first ceil(nbits / 64) words hold a row of nbits bits, layout of tnac4o_amd/overlap.py; weights None (all 1)
+    or (M,) uint32 values in an int32 / uint32 device tensor, read as at most wmax (None: 2^32 - 1, or 1 without weights); only the
+    bit-planes of the weights up to the bit length of wmax are processed.  Returns the (nbits + 2, nbits + 2) int64 device tensor
+    out[i][j] = sum_a w_a [x_a,i != x_a,j] with the constant pseudo-bits x_a,nbits = 0 and x_a,nbits+1 = 1: exact integers (read them
+    as unsigned)."""
+    if not rows.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % rows.device)
+    if rows.dim() != 2 or rows.element_size() != 8 or rows.is_floating_point() or rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise TypeError('rows: a 2-d tensor of 64-bit integer words with unit stride along a row')
+    M, ld = int(rows.shape[0]), int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    nbits = int(nbits)
+    nwords = -(-max(nbits, 0) // 64)
+    if rows.shape[1] < nwords:
+        raise ValueError('rows hold %d words, %d bits take %d' % (rows.shape[1], nbits, nwords))
+    if weights is not None:
+        if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous() or weights.numel() != M:
+            raise TypeError('weights: a contiguous device tensor of M 32-bit integers')
+    if wmax is None:
+        wmax = 2 ** 32 - 1 if weights is not None else 1
+    wmax = int(wmax)
+    if not 0 <= wmax < 2 ** 32:
+        raise ValueError('wmax must fit 32 bits')
+    L = lib()
+    wsb = int(L.tn_spin_moments_ws_bytes(M, nbits, wmax))                   # (not cached: it follows TN_SPIN_MOMENTS_WGS)
+    ws = workspace(max(wsb, 16), 1)
+    n2 = max(nbits, 0) + 2
+    out = torch.empty((n2, n2), dtype=torch.int64, device=rows.device)
+    check(L.tn_spin_moments(rows.data_ptr() if M else ws.data_ptr(), M, nbits, max(ld, nwords), weights.data_ptr() if weights is not None else None,
+                            wmax, out.data_ptr(), n2, ws.data_ptr(), wsb, _stream()))
+    return out

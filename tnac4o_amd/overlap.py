@@ -1,8 +1,11 @@
 """Replica-overlap distributions of a set of configurations (host side of tnac4o.calculate_overlap_distribution) and
-their line-resolved second moments (tnac4o.calculate_overlap_correlations).
+their line-resolved second moments (tnac4o.calculate_overlap_correlations), and the correlations of every pair of spins
+over the configurations (tnac4o.calculate_sample_correlations).
 
 Plain numpy, importable without a GPU; the only device work is the pair histogram tn_pair_hist (ops.pair_hist), which the driver
-overlap_distribution calls once, and the pair moments tn_pair_moments (ops.pair_moments), which overlap_correlations calls once per axis.  Row layouts of the library: a row of n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at
+overlap_distribution calls once, the pair moments tn_pair_moments (ops.pair_moments), which overlap_correlations calls once per axis,
+and the spin moments tn_spin_moments (ops.spin_moments), which sample_correlations calls once.  Row layouts of the library: a row of
+n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at
 position i % 64; a row of n 16-bit lanes is ceil(n / 4) words, lane i in word i // 4 at bits 16 (i % 4) .. 16 (i % 4) + 15."""
 import numpy as np
 
@@ -416,5 +419,116 @@ def overlap_correlations(solver, axis='both', kind=None, weights='uniform'):
     solver.overlap_chi = chi
     solver.overlap_xi = xi
     solver.overlap_xi_over_L = xil
+    solver.overlap_ess = effective_sample_size(w)
+    return C
+
+
+# ---------------------------------------------------------------------------------------------- every pair of spins
+MAX_SPIN_BITS = 65534            # largest row tn_spin_moments takes: nbits + 2 rows and columns, at most 2^16 (include/tnpeps.h)
+
+
+def pair_weight(W, S2, scale=1.0):
+    """(W, S2, W^2 - S2) in the arithmetic spin_estimators uses: W = sum_a w_a an integer, S2 = sum_a w_a^2 over the raw samples in units
+    of scale^2.  scale 1 and an integer S2: np.int64 while W < 2^31 (the square fits), Python integers above; otherwise float64.
+    W^2 - S2 = sum_{a != b} w_a w_b must be positive -- in float64 above 2^-40 W^2, what the rounding of the weights to 32 bits can
+    leave of a single sample -- or: ValueError."""
+    W = int(W)
+    if float(scale) == 1.0 and float(S2) == np.rint(S2):
+        Wn, S2n = (np.int64(W), np.int64(int(np.rint(S2)))) if W < 2 ** 31 else (W, int(np.rint(S2)))
+        floor = 0
+    else:
+        Wn, S2n = float(W), float(S2)
+        floor = 2.0 ** -40 * Wn * Wn
+    den = Wn * Wn - S2n
+    if not W > 0 or not den > floor:
+        raise ValueError('no pair of distinct samples carries weight')
+    return Wn, S2n, den
+
+
+def spin_estimators(out, S2, scale=1.0):
+    """(m (n,), C (n, n), QQ (n, n)) in float64 from the integers of tn_spin_moments: out (n+2, n+2) (any integer dtype, read as
+    unsigned 64-bit; or nested Python integers), D_ij = out[i][j] the weight of the samples in which bits i and j differ,
+    W = out[n][n+1] the total weight.  m_i = (W - 2 out[i][n+1]) / W = <sigma_i> with sigma = +1 where the bit is 1 (binary_states
+    writes 1 there: the convention of `magnetization`), C_ij = (W - 2 D_ij) / W = <sigma_i sigma_j>, and the pair estimator over the
+    distinct samples QQ_ij = <q_i q_j> = sum_{a != b} w_a w_b (s_i s_j)_a (s_i s_j)_b / sum_{a != b} w_a w_b
+    = ((W - 2 D_ij)^2 - S2) / (W^2 - S2), S2 = sum_a w_a^2 over the raw samples in units of scale^2.  With scale 1 and an integer S2
+    everything up to the final divisions is exact: in int64 while W < 2^31, in Python integers above.  With a scale the weights were
+    rounded; the expression is then formed in float64, whose error (2^-52 of W^2, like the denominator) is far below the
+    rounding of the weights (pair_weight).  Fewer than two samples with weight: ValueError."""
+    O = np.asarray(out)
+    if O.dtype != object:
+        O = np.ascontiguousarray(O).astype(np.int64, copy=False).view(np.uint64)
+    n = O.shape[0] - 2
+    if O.ndim != 2 or O.shape != (n + 2, n + 2) or n < 1:
+        raise ValueError('out (n+2, n+2) expected')
+    W = int(O[n, n + 1])
+    Wn, S2n, den = pair_weight(W, S2, scale)
+    D = O.astype(np.int64 if isinstance(Wn, np.int64) else np.float64 if isinstance(Wn, float) else object)
+    A = Wn - 2 * D[:n, :n]
+    m = (Wn - 2 * D[:n, n + 1]).astype(np.float64) / float(W)
+    C = A.astype(np.float64) / float(W)
+    QQ = (A * A - S2n).astype(np.float64) / float(den)
+    return m, C, QQ
+
+
+def chi_sg_2d(QQ, gx, gy, Nx, Ny):
+    """chi_SG(k_x, k_y) = (1 / N) sum_ij <q_i q_j> cos(k_x (x_i - x_j) + k_y (y_i - y_j)) on the grid k = 2 pi (m_x / Nx, m_y / Ny):
+    (Nx, Ny) float64, entry [m_x, m_y].  gx, gy (n,): the model column and row of spin i's cell (line_groups).  <q_i q_j> is summed
+    into blocks of cell pairs first; the (Nx Ny)^2 terms of a wave vector cancel at k != 0, so they are added without rounding
+    (math.fsum, as chi_of_k).  The phase is reduced in integers, k.r = 2 pi ((m_x dx Ny + m_y dy Nx) mod Nx Ny) / (Nx Ny);
+    chi(-k) = chi(k) is computed once."""
+    import math
+    QQ = np.asarray(QQ, dtype=np.float64)
+    gx, gy = np.asarray(gx, dtype=np.int64), np.asarray(gy, dtype=np.int64)
+    n, nc = QQ.shape[0], Nx * Ny
+    cell = gy * Nx + gx
+    Z = np.zeros((n, nc))
+    Z[np.arange(n), cell] = 1.0
+    B = Z.T @ QQ @ Z                                                    # blocks of cell pairs
+    cx, cy = np.arange(nc) % Nx, np.arange(nc) // Nx
+    dx, dy = cx[:, None] - cx[None, :], cy[:, None] - cy[None, :]
+    table = np.cos(2.0 * np.pi * np.arange(nc) / nc)
+    chi = np.zeros((Nx, Ny))
+    for mx in range(Nx):
+        for my in range(Ny):
+            tx, ty = (-mx) % Nx, (-my) % Ny
+            if (tx, ty) < (mx, my):
+                chi[mx, my] = chi[tx, ty]
+                continue
+            phase = (mx * dx * Ny + my * dy * Nx) % nc
+            chi[mx, my] = math.fsum((B * table[phase]).ravel()) / float(n)
+    return chi
+
+
+def sample_correlations(solver, weights='uniform'):
+    """calculate_sample_correlations of tnac4o (documented there)."""
+    _ising(solver, 'calculate_sample_correlations')
+    _, w = check_arguments(solver, 'spin', weights)
+    bits = spin_bits(solver)
+    n = int(bits.shape[1])
+    if n < 1:
+        raise ValueError('the model has no active spin')
+    if n > MAX_SPIN_BITS:
+        raise NotImplementedError('the model has %d active spins; tn_spin_moments takes at most %d; there is no host fallback' % (n, MAX_SPIN_BITS))
+    gx, gy = line_groups(solver, 'x', 'spin')[0], line_groups(solver, 'y', 'spin')[0]
+    urows, W, _ = condense(pack_bits(bits), w)
+    wq, keep, scale = quantise(W, WMAX)
+    urows, wq = np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep])
+    S2 = float(np.sum(w * w)) * scale * scale
+    Wt = int(wq.astype(np.uint64).sum(dtype=object)) if wq.size else 0
+    pair_weight(Wt, S2, scale)                                         # every refusal comes before any device work
+    import torch
+    from . import ops
+    d_rows = torch.as_tensor(urows.view(np.int64)).cuda()
+    d_w = None if np.all(wq == 1) else torch.as_tensor(wq.view(np.int32)).cuda()
+    out = ops.spin_moments(d_rows, n, d_w, int(wq.max())).cpu().numpy()
+    m, C, QQ = spin_estimators(out, S2, scale)
+    act = np.sort(np.concatenate([np.asarray(a, dtype=np.int64) for row in solver.ind0 for a in row] + [np.zeros(0, dtype=np.int64)]))
+    chi = chi_sg_2d(QQ, gx, gy, int(solver.Nx_model), int(solver.Ny_model))
+    solver.sample_spins = act
+    solver.sample_magnetization = m
+    solver.sample_correlations = C
+    solver.sample_overlap_correlations = QQ
+    solver.sample_chi_sg = chi
     solver.overlap_ess = effective_sample_size(w)
     return C

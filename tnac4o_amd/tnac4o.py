@@ -1468,6 +1468,24 @@ class tnac4o:
         from . import overlap
         return overlap.overlap_correlations(self, axis, kind, weights)
 
+    def calculate_sample_correlations(self, weights='uniform'):
+        """<s_i s_j> between every pair of active spins, from the rows of `states` (whatever wrote them), with the magnetisations and
+        the site-resolved replica-overlap correlations.  Ising only (ValueError for RMF).  weights as calculate_overlap_distribution.
+        Equal rows are condensed; one call of tn_spin_moments gives, for every pair of spins, the exact integer weight of the samples
+        in which they differ (tnac4o_amd/overlap.py).
+        Returns and stores sample_correlations (n, n) = <sigma_i sigma_j> over the n active spins, sigma = +1 where binary_states
+        writes 1 (the convention of `magnetization` and `correlations`), diagonal 1; stores sample_spins (n,), the active spins in
+        model order (row and column i belong to spin sample_spins[i]), sample_magnetization (n,) = <sigma_i>,
+        sample_overlap_correlations (n, n) = <q_i q_j>, the mean of (s_i s_j)_a (s_i s_j)_b over the pairs of DISTINCT samples
+        a != b (the unbiased estimator of <s_i s_j>^2; its mean over i, j is <q^2> of calculate_overlap_distribution and its sums over
+        lattice lines are those of calculate_overlap_correlations), sample_chi_sg (Nx, Ny) = chi_SG(k_x, k_y) = (1 / N) sum_ij
+        <q_i q_j> cos(k . (r_i - r_j)) at k = 2 pi (m_x / Nx, m_y / Ny), r the model column and row of the spin's cell, and
+        overlap_ess.  Under uniform weights everything is exact up to the final divisions; other weights are rounded to 32 bits of
+        the largest.  Fewer than two states, or fewer than two with weight, and bad weights are a ValueError, more than 65534 active
+        spins a NotImplementedError, all raised before any device work; there is no host fallback.  Changes nothing else."""
+        from . import overlap
+        return overlap.sample_correlations(self, weights)
+
     # ------------------------------------------------------------------------------------ output
     def binary_states(self, number=-1):
         """Bit strings: 1 spin up, 0 spin down, 2 inactive (tnac4o.py:261-288)."""
