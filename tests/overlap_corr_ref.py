@@ -1,6 +1,6 @@
 """Host references for tn_pair_moments and tnac4o.calculate_overlap_correlations (numpy and Python integers, no GPU).
 
-- make_group_rows / weight_sets: the inputs of the kernel tests (the patterns of test_gpu_overlap.py, restated for grouped rows).
+- make_group_rows / weight_sets: the inputs of the kernel tests (those of overlap_ref, for grouped rows).
 - group_dists / pair_moments_ref: out[i][j] = sum_{a<b} w_a w_b d_i d_j by brute force, the sums in Python integers.
 - correlations_ref: <q_g>, <Q_g Q_g'>, C and chi from all M^2 ordered pairs in float64, without condensing or quantisation.
 - chi_ref: chi(k_m) by plain loops.
@@ -8,33 +8,13 @@
 """
 import numpy as np
 
-from overlap_ref import unpack_rows
-
-PAD = 3                                                                # words of random padding behind a row
+from overlap_ref import make_rows, unpack_rows, weight_sets  # noqa: F401 (the tests take weight_sets from here)
 
 
 def make_group_rows(M, G, wpg, lanes16, seed):
-    """(M, G wpg + 3) uint64: random rows with random words in the padding; row 1 repeats row 0 and M // 2 repeats row 2
-    (duplicates), the last row is the complement of row 0 (lanes16: differs from it in every lane), so d_g(0, M - 1) is the
-    largest distance, (4 or 64) wpg, in every group."""
-    rng = np.random.default_rng(seed)
-    nw = G * wpg
-    if lanes16:
-        U = rng.integers(0, 32768, (M, nw * 4)).astype('<u2')
-        if M >= 2:
-            U[M - 1] = (U[0] + 1 + rng.integers(0, 32766, nw * 4)) % 32768
-        body = U.view('<u8').astype(np.uint64)
-    else:
-        body = rng.integers(0, 2 ** 64, (M, nw), dtype=np.uint64)
-        if M >= 2:
-            body[M - 1] = ~body[0]
-    rows = rng.integers(0, 2 ** 64, (M, nw + PAD), dtype=np.uint64)
-    rows[:, :nw] = body
-    if M >= 3:
-        rows[1, :nw] = rows[0, :nw]
-    if M >= 6:
-        rows[M // 2, :nw] = rows[2, :nw]
-    return rows
+    """(M, G wpg + 3) uint64: make_rows for rows of G wpg whole words, so d_g(0, M - 1) is the largest distance, (4 or 64) wpg, in
+    every group."""
+    return make_rows(M, G * wpg * (4 if lanes16 else 64), lanes16, seed)
 
 
 def dmax_of(wpg, lanes16):
@@ -44,15 +24,6 @@ def dmax_of(wpg, lanes16):
 def wmax_of(wpg, lanes16):
     """The largest wmax tn_pair_moments takes: wmax dmax <= 2^32 - 1."""
     return (2 ** 32 - 1) // dmax_of(wpg, lanes16)
-
-
-def weight_sets(M, wmax, seed):
-    rng = np.random.default_rng(seed)
-    some_zero = rng.integers(0, wmax + 1, M, dtype=np.uint64)
-    some_zero[rng.random(M) < 0.3] = 0
-    if M >= 2:
-        some_zero[0] = 0
-    return {'none': None, 'random': rng.integers(0, wmax + 1, M, dtype=np.uint64), 'max': np.full(M, wmax, dtype=np.uint64), 'zeros': some_zero}
 
 
 def group_dists(rows, G, wpg, lanes16):

@@ -3,8 +3,101 @@
 - pair_dist_ref / pair_hist_ref: the pair histogram by brute force, the sums in Python integers.
 - distribution_ref: P over the distances from all M^2 ordered pairs in float64, without condensing and without quantisation.
 - exact_spin_overlap_law: the exact overlap law of two independent replicas of an enumerated Boltzmann law.
+- what the tests of tn_pair_hist, tn_pair_moments and tn_spin_moments share: the small solvers, states_with_duplicates and source for
+  the pipeline tests, make_rows / weight_sets for the kernel tests, last_error, first_diffs.
 """
 import numpy as np
+
+PAD = 3                                                                # words of random padding behind a row
+WMAX = 2 ** 32 - 1
+
+
+def droplet(beta=3.0):
+    import golden_inputs as gi
+    import tnac4o_amd
+    return tnac4o_amd.tnac4o(mode='Ising', Nx=4, Ny=4, Nc=8, J=gi.droplet_J(128, 1), beta=beta)
+
+
+def ising3x3(beta=1.0):
+    import marginals_ref as mr
+    import tnac4o_amd
+    return tnac4o_amd.tnac4o(mode='Ising', Nx=3, Ny=3, Nc=2, J=mr.ising_3x3_nc2(), beta=beta)
+
+
+def rmf(beta=1.0):
+    import tnac4o_amd
+    from tnac4o_amd import auxx
+    return tnac4o_amd.tnac4o(mode='RMF', Nx=3, Ny=3, J=auxx.synthetic_rmf(3, 3, 3, 17), beta=beta)
+
+
+def states_with_duplicates(M, rng, distinct):
+    """(M, 16) cell states of the droplet lattice drawn from `distinct` configurations that differ from one another in a few cells."""
+    base = rng.integers(0, 256, 16)
+    pool = np.tile(base, (distinct, 1))
+    for k in range(distinct):
+        cells = rng.integers(0, 16, rng.integers(0, 5))
+        pool[k, cells] = rng.integers(0, 256, cells.size)
+    return pool[rng.integers(0, distinct, M)]
+
+
+def source(s, kind, unsigned=False):
+    """(M, n) of what `kind` compares in the states of solver s: the spin or link bits, or the cell states as int64 -- as they are stored
+    (int8 states above 127 negative), or, unsigned, in 0 .. 255."""
+    from tnac4o_amd import overlap
+    if kind == 'cell':
+        st = np.asarray(s.states).astype(np.int64)
+        return st & 0xff if unsigned else st
+    return {'spin': overlap.spin_bits, 'link': overlap.link_bits}[kind](s)
+
+
+def last_error(L):
+    import ctypes as ct
+    buf = ct.create_string_buffer(512)
+    L.tn_last_error(buf, 512)
+    return buf.value.decode()
+
+
+def first_diffs(got, want):
+    """The first four entries in which two square tables (nested lists or arrays) differ: (i, j, got, want)."""
+    return [(i, j, got[i][j], want[i][j]) for i in range(len(want)) for j in range(len(want)) if got[i][j] != want[i][j]][:4]
+
+
+def make_rows(M, nbits, lanes16, seed):
+    """(M, ld) uint64 with ld = nwords + 3: random rows, random words in the padding, random bits (lanes) beyond nbits in the last
+    word; row 1 repeats row 0 and M // 2 repeats row 2 (duplicates), the last row differs from row 0 everywhere (bin nbits)."""
+    rng = np.random.default_rng(seed)
+    per = 4 if lanes16 else 64
+    nwords = -(-nbits // per)
+    if lanes16:
+        U = rng.integers(0, 32768, (M, nwords * 4)).astype('<u2')
+        if M >= 2:
+            U[M - 1] = (U[0] + 1 + rng.integers(0, 32766, nwords * 4)) % 32768
+        body = U.view('<u8').astype(np.uint64)
+    else:
+        body = rng.integers(0, 2 ** 64, (M, nwords), dtype=np.uint64)
+        if M >= 2:
+            body[M - 1] = ~body[0]
+    rows = rng.integers(0, 2 ** 64, (M, nwords + PAD), dtype=np.uint64)
+    rows[:, :nwords] = body
+    if M >= 3:
+        rows[1, :nwords] = rows[0, :nwords]
+    if M >= 6:
+        rows[M // 2, :nwords] = rows[2, :nwords]
+    if nbits % per:                                                    # what lies beyond nbits in the last word differs from row to row
+        cut = (nbits % per) * (16 if lanes16 else 1)
+        junk = rng.integers(0, 2 ** 64, M, dtype=np.uint64) << np.uint64(cut)
+        keep = np.uint64((1 << cut) - 1)
+        rows[:, nwords - 1] = (rows[:, nwords - 1] & keep) | junk
+    return rows
+
+
+def weight_sets(M, wmax, seed):
+    rng = np.random.default_rng(seed)
+    some_zero = rng.integers(0, wmax + 1, M, dtype=np.uint64)
+    some_zero[rng.random(M) < 0.3] = 0
+    if M >= 2:
+        some_zero[0] = 0
+    return {'none': None, 'random': rng.integers(0, wmax + 1, M, dtype=np.uint64), 'max': np.full(M, wmax, dtype=np.uint64), 'zeros': some_zero}
 
 
 def unpack_rows(rows, nbits, lanes16):

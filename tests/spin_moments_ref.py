@@ -11,10 +11,7 @@
 """
 import numpy as np
 
-from overlap_ref import unpack_rows
-
-PAD = 3                                                                # words of random padding behind a row
-WMAX = 2 ** 32 - 1
+from overlap_ref import PAD, WMAX, unpack_rows
 
 
 def make_rows(M, nbits, seed):

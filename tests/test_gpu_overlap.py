@@ -4,54 +4,15 @@ overlap law of sample_boltzmann's samples against the exact one of two independe
 import numpy as np
 import pytest
 
-import golden_inputs as gi
 import overlap_ref as oref
 from guarded import Guarded
+from overlap_ref import WMAX, droplet, make_rows
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
-WMAX = 2 ** 32 - 1
 MS = (1, 2, 63, 64, 65, 129, 300)
 NBITS = (1, 63, 64, 65, 130, 2048)
-
-
-def make_rows(M, nbits, lanes16, seed):
-    """(M, ld) uint64 with ld = nwords + 3: random rows, random words in the padding, random bits (lanes) beyond nbits in the last
-    word; row 1 repeats row 0 and M // 2 repeats row 2 (duplicates), the last row differs from row 0 everywhere (bin nbits)."""
-    rng = np.random.default_rng(seed)
-    per = 4 if lanes16 else 64
-    nwords = -(-nbits // per)
-    if lanes16:
-        U = rng.integers(0, 32768, (M, nwords * 4)).astype('<u2')
-        if M >= 2:
-            U[M - 1] = (U[0] + 1 + rng.integers(0, 32766, nwords * 4)) % 32768
-        body = U.view('<u8').astype(np.uint64)
-    else:
-        body = rng.integers(0, 2 ** 64, (M, nwords), dtype=np.uint64)
-        if M >= 2:
-            body[M - 1] = ~body[0]
-    rows = rng.integers(0, 2 ** 64, (M, nwords + 3), dtype=np.uint64)
-    rows[:, :nwords] = body
-    if M >= 3:
-        rows[1, :nwords] = rows[0, :nwords]
-    if M >= 6:
-        rows[M // 2, :nwords] = rows[2, :nwords]
-    if nbits % per:                                                    # what lies beyond nbits in the last word differs from row to row
-        cut = (nbits % per) * (16 if lanes16 else 1)
-        junk = rng.integers(0, 2 ** 64, M, dtype=np.uint64) << np.uint64(cut)
-        keep = np.uint64((1 << cut) - 1)
-        rows[:, nwords - 1] = (rows[:, nwords - 1] & keep) | junk
-    return rows
-
-
-def weight_sets(M, seed):
-    rng = np.random.default_rng(seed)
-    some_zero = rng.integers(0, 2 ** 32, M, dtype=np.uint64)
-    some_zero[rng.random(M) < 0.3] = 0
-    if M >= 2:
-        some_zero[0] = 0
-    return {'none': None, 'random': rng.integers(0, 2 ** 32, M, dtype=np.uint64), 'max': np.full(M, WMAX, dtype=np.uint64), 'zeros': some_zero}
 
 
 def run(rows, nbits, w, lanes16):
@@ -74,7 +35,7 @@ def test_pair_hist_is_exact(M, nbits, lanes16):
     D = oref.pair_dist_ref(rows, nbits, lanes16)
     if M >= 2:
         assert D[0, M - 1] == nbits and (M < 3 or D[0, 1] == 0)
-    for name, w in weight_sets(M, seed=M + nbits).items():
+    for name, w in oref.weight_sets(M, WMAX, seed=M + nbits).items():
         want = oref.pair_hist_ref(rows, nbits, w, lanes16, dist=D)
         got = run(rows, nbits, w, lanes16)
         assert got == want, (name, [(d, g, x) for d, (g, x) in enumerate(zip(got, want)) if g != x][:4])
@@ -90,7 +51,7 @@ def test_pair_hist_at_the_largest_nbits(lanes16):
     M, nbits = 65, overlap.MAX_NBITS
     rows = make_rows(M, nbits, lanes16, seed=77)
     D = oref.pair_dist_ref(rows, nbits, lanes16)
-    for name, w in weight_sets(M, seed=5).items():
+    for name, w in oref.weight_sets(M, WMAX, seed=5).items():
         assert run(rows, nbits, w, lanes16) == oref.pair_hist_ref(rows, nbits, w, lanes16, dist=D), name
     with pytest.raises(_lib.TnError, match=str(nbits)):               # one more does not fit: refused by name, nothing launched
         ops.pair_hist(torch.zeros((2, 4096), dtype=torch.int64, device='cuda'), nbits + 1, None, lanes16)
@@ -105,7 +66,7 @@ def test_result_does_not_depend_on_the_grid(lanes16, monkeypatch):
     same[:] = same[0]
     cases.append((same, 130))                                          # 300 identical rows: every pair in bin 0
     for rows, nbits in cases:
-        for name, w in weight_sets(M, seed=nbits).items():
+        for name, w in oref.weight_sets(M, WMAX, seed=nbits).items():
             out = {}
             for wgs in ('1', '3', None):
                 if wgs is None:
@@ -130,7 +91,7 @@ def test_workspace_and_output_contract(lanes16):
     M, nbits = 300, 130
     rows = make_rows(M, nbits, bool(lanes16), seed=31)
     ld = rows.shape[1]
-    w = weight_sets(M, seed=3)['random']
+    w = oref.weight_sets(M, WMAX, seed=3)['random']
     want = oref.limbs(oref.pair_hist_ref(rows, nbits, w, bool(lanes16)))
     d_rows = torch.as_tensor(rows.view(np.int64)).cuda()
     d_w = torch.as_tensor(w.astype(np.uint32).view(np.int32)).cuda()
@@ -159,26 +120,6 @@ def test_workspace_and_output_contract(lanes16):
 
 
 # ---------------------------------------------------------------------------------------------- 4. pipeline against all M^2 pairs
-def droplet(beta=3.0):
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=4, Ny=4, Nc=8, J=gi.droplet_J(128, 1), beta=beta)
-
-
-def _states_with_duplicates(M, rng, distinct):
-    """(M, 16) cell states of the droplet lattice drawn from `distinct` configurations that differ from one another in a few cells."""
-    base = rng.integers(0, 256, 16)
-    pool = np.tile(base, (distinct, 1))
-    for k in range(distinct):
-        cells = rng.integers(0, 16, rng.integers(0, 5))
-        pool[k, cells] = rng.integers(0, 256, cells.size)
-    return pool[rng.integers(0, distinct, M)]
-
-
-def _source(s, kind):
-    from tnac4o_amd import overlap
-    return {'spin': overlap.spin_bits, 'link': overlap.link_bits, 'cell': lambda x: np.asarray(x.states).astype(np.int64)}[kind](s)
-
-
 @pytest.fixture(scope='module')
 def pipeline_cases():
     """kind -> weights -> (solver attributes after the call, reference): M = 2048 on the droplet lattice."""
@@ -190,10 +131,10 @@ def pipeline_cases():
         s = droplet()
         out[kind] = {}
         for name in ('uniform', 'float'):
-            s.states = _states_with_duplicates(M, rng, 60 if name == 'uniform' else 700).astype(np.uint8).astype(s.indtype)
+            s.states = oref.states_with_duplicates(M, rng, 60 if name == 'uniform' else 700).astype(np.uint8).astype(s.indtype)
             w = np.ones(M) if name == 'uniform' else 10.0 ** rng.uniform(-12.0, 0.0, M)
             P = s.calculate_overlap_distribution(kind, 'uniform' if name == 'uniform' else w)
-            src = _source(s, kind)
+            src = oref.source(s, kind)
             K = np.unique(src, axis=0).shape[0]
             out[kind][name] = (P, dict(values=s.overlap_values, moments=dict(s.overlap_moments), ess=s.overlap_ess, pairs=s.overlap_pairs,
                                        kind=s.overlap_kind, stored=s.overlap_distribution, n=src.shape[1], K=K, w=w),
@@ -233,13 +174,12 @@ def test_pipeline_float_weights(pipeline_cases, kind):
 
 # ---------------------------------------------------------------------------------------------- 5. end to end
 def _small(case, beta=1.0):
-    import marginals_ref as mr
     import tnac4o_amd
     from tnac4o_amd import auxx
     if case == 'ising3x3':
-        return tnac4o_amd.tnac4o(mode='Ising', Nx=3, Ny=3, Nc=2, J=mr.ising_3x3_nc2(), beta=beta)
+        return oref.ising3x3(beta)
     if case == 'rmf3x3':
-        return tnac4o_amd.tnac4o(mode='RMF', Nx=3, Ny=3, J=auxx.synthetic_rmf(3, 3, 3, 17), beta=beta)
+        return oref.rmf(beta)
     return tnac4o_amd.tnac4o(mode='Ising', Nx=2, Ny=2, Nc=8, J=auxx.synthetic_chimera(2, 2, 29), beta=beta)
 
 

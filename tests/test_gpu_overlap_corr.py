@@ -4,9 +4,9 @@ against all M^2 pairs in float64, and the line overlaps of sample_boltzmann's sa
 import numpy as np
 import pytest
 
-import golden_inputs as gi
 import overlap_corr_ref as cref
 from guarded import Guarded
+from overlap_ref import droplet, first_diffs, last_error, source, states_with_duplicates
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
@@ -32,10 +32,6 @@ def run(rows, G, wpg, w, wmax, lanes16):
     out = ops.pair_moments(d_rows[:, :G * wpg], G, wpg, d_w, wmax, lanes16)
     assert out.shape == (G + 1, G + 1, 2) and out.dtype == torch.int64
     return to_ints(out)
-
-
-def first_diffs(got, want):
-    return [(i, j, got[i][j], want[i][j]) for i in range(len(want)) for j in range(len(want)) if got[i][j] != want[i][j]][:4]
 
 
 def check_exact(M, G, wpg, lanes16):
@@ -131,13 +127,6 @@ def test_result_does_not_depend_on_the_grid(lanes16, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- 4. workspace and output contract
-def _last_error(L):
-    import ctypes as ct
-    buf = ct.create_string_buffer(512)
-    L.tn_last_error(buf, 512)
-    return buf.value.decode()
-
-
 @pytest.mark.parametrize('lanes16', [0, 1])
 def test_workspace_and_output_contract(lanes16):
     """Exactly tn_pair_moments_ws_bytes suffices whatever the workspace and the output held before; every entry of out is written;
@@ -179,7 +168,7 @@ def test_workspace_and_output_contract(lanes16):
         out = Guarded.of(torch.int64, (66, 66, 2), 0xFF, seed=8)
         rc = L.tn_pair_moments(wide.data_ptr(), M, g, k, 65 * 33, d_w.data_ptr(), wm, lanes16, out.ptr, big.ptr, big.nbytes, ops._stream())
         torch.cuda.synchronize()
-        assert rc == -1 and word in _last_error(L), (g, k, wm, _last_error(L))
+        assert rc == -1 and word in last_error(L), (g, k, wm, last_error(L))
         assert out.untouched(0xFF) and big.untouched(0xFF) and out.intact() and big.intact()
     # M < 2: zeros in every entry
     out = Guarded.of(torch.int64, shape, 0xFF, seed=5)
@@ -190,26 +179,6 @@ def test_workspace_and_output_contract(lanes16):
 
 
 # ---------------------------------------------------------------------------------------------- 5. pipeline against all M^2 pairs
-def droplet(beta=3.0):
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=4, Ny=4, Nc=8, J=gi.droplet_J(128, 1), beta=beta)
-
-
-def _states_with_duplicates(M, rng, distinct):
-    """(M, 16) cell states of the droplet lattice drawn from `distinct` configurations that differ from one another in a few cells."""
-    base = rng.integers(0, 256, 16)
-    pool = np.tile(base, (distinct, 1))
-    for k in range(distinct):
-        cells = rng.integers(0, 16, rng.integers(0, 5))
-        pool[k, cells] = rng.integers(0, 256, cells.size)
-    return pool[rng.integers(0, distinct, M)]
-
-
-def _source(s, kind):
-    from tnac4o_amd import overlap
-    return overlap.spin_bits(s) if kind == 'spin' else np.asarray(s.states).astype(np.int64) & 0xff
-
-
 STORED = ('overlap_line_correlations', 'overlap_line_mean', 'overlap_line_sizes', 'overlap_chi', 'overlap_xi', 'overlap_xi_over_L')
 
 
@@ -224,7 +193,7 @@ def pipeline_cases():
         s = droplet()
         out[kind] = {}
         for name in ('uniform', 'float'):
-            s.states = _states_with_duplicates(M, rng, 60 if name == 'uniform' else 700).astype(np.uint8).astype(s.indtype)
+            s.states = states_with_duplicates(M, rng, 60 if name == 'uniform' else 700).astype(np.uint8).astype(s.indtype)
             w = np.ones(M) if name == 'uniform' else 10.0 ** rng.uniform(-12.0, 0.0, M)
             more = {}
             if kind == 'spin' and name == 'uniform':
@@ -233,7 +202,7 @@ def pipeline_cases():
             C = s.calculate_overlap_correlations('both', kind, 'uniform' if name == 'uniform' else w)
             if more:
                 more['P_after'], more['pairs_after'], more['chi_sg_after'] = s.overlap_distribution, s.overlap_pairs, s.overlap_moments['chi_sg']
-            src = _source(s, kind)
+            src = source(s, kind, unsigned=True)
             ref = {ax: cref.correlations_ref(src, overlap.line_groups(s, ax, kind)[0], 4, w, kind) for ax in ('x', 'y')}
             more.update(K=np.unique(src, axis=0).shape[0], w=w, ess=s.overlap_ess, kind=s.overlap_line_kind)
             out[kind][name] = (C, {a: getattr(s, a) for a in STORED}, ref, more)

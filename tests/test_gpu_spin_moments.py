@@ -7,17 +7,16 @@ import math
 import numpy as np
 import pytest
 
-import golden_inputs as gi
 import overlap_corr_ref as cref
 import spin_moments_ref as sref
 from guarded import Guarded
+from overlap_ref import WMAX, droplet, first_diffs, last_error, states_with_duplicates
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 MS = (1, 2, 63, 64, 65, 300)
 NBITS = (1, 2, 62, 63, 64, 65, 130)
-WMAX = 2 ** 32 - 1
 WGS = ('1', '2', '3', '4', '7', None)
 
 
@@ -29,10 +28,6 @@ def run(rows, nbits, w, wmax):
     out = ops.spin_moments(d_rows[:, :-(-nbits // 64)], nbits, d_w, wmax)
     assert out.shape == (nbits + 2, nbits + 2) and out.dtype == torch.int64
     return sref.to_ints(out.cpu().numpy())
-
-
-def first_diffs(got, want):
-    return [(i, j, got[i, j], want[i, j]) for i, j in np.argwhere(got != want)[:4]]
 
 
 def check_properties(got, nbits, total):
@@ -141,13 +136,6 @@ def test_result_does_not_depend_on_the_grid(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- 4. workspace and output contract
-def _last_error(L):
-    import ctypes as ct
-    buf = ct.create_string_buffer(512)
-    L.tn_last_error(buf, 512)
-    return buf.value.decode()
-
-
 @pytest.mark.parametrize('M,nbits', [(300, 130), (2565, 70)])
 def test_workspace_and_output_contract(M, nbits, monkeypatch):
     """Exactly tn_spin_moments_ws_bytes suffices whatever the workspace and the output held before; every entry of out is written and,
@@ -191,7 +179,7 @@ def test_workspace_and_output_contract(M, nbits, monkeypatch):
         out = Guarded.of(torch.int64, (n2, n2), 0xFF, seed=8)
         rc = L.tn_spin_moments(d_rows.data_ptr(), m, n, ldr, d_w.data_ptr(), wm, out.ptr, ldo, big.ptr, big.nbytes, ops._stream())
         torch.cuda.synchronize()
-        assert rc == -1 and word in _last_error(L), (m, n, wm, ldr, ldo, _last_error(L))
+        assert rc == -1 and word in last_error(L), (m, n, wm, ldr, ldo, last_error(L))
         assert out.untouched(0xFF) and big.untouched(0xFF) and out.intact() and big.intact()
     # M = 0: zeros in every entry
     out = Guarded.of(torch.int64, (n2, n2), 0xFF, seed=5)
@@ -202,21 +190,6 @@ def test_workspace_and_output_contract(M, nbits, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- 5. pipeline, uniform weights
-def droplet(beta=3.0):
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=4, Ny=4, Nc=8, J=gi.droplet_J(128, 1), beta=beta)
-
-
-def _states_with_duplicates(M, rng, distinct):
-    """(M, 16) cell states of the droplet lattice drawn from `distinct` configurations that differ from one another in a few cells."""
-    base = rng.integers(0, 256, 16)
-    pool = np.tile(base, (distinct, 1))
-    for k in range(distinct):
-        cells = rng.integers(0, 16, rng.integers(0, 5))
-        pool[k, cells] = rng.integers(0, 256, cells.size)
-    return pool[rng.integers(0, distinct, M)]
-
-
 STORED = ('sample_spins', 'sample_magnetization', 'sample_correlations', 'sample_overlap_correlations', 'sample_chi_sg', 'overlap_ess')
 
 
@@ -228,7 +201,7 @@ def test_pipeline_uniform_weights():
     M = 2048
     rng = np.random.default_rng(11)
     s = droplet()
-    s.states = _states_with_duplicates(M, rng, 60).astype(np.uint8).astype(s.indtype)
+    s.states = states_with_duplicates(M, rng, 60).astype(np.uint8).astype(s.indtype)
     s.calculate_overlap_distribution('spin')
     s.calculate_overlap_correlations('both', 'spin')
     C = s.calculate_sample_correlations()
@@ -285,7 +258,7 @@ def test_pipeline_float_weights():
     M = 1024
     rng = np.random.default_rng(12)
     s = droplet()
-    s.states = _states_with_duplicates(M, rng, 700).astype(np.uint8).astype(s.indtype)
+    s.states = states_with_duplicates(M, rng, 700).astype(np.uint8).astype(s.indtype)
     w = 10.0 ** rng.uniform(-12.0, 0.0, M)
     C = s.calculate_sample_correlations(weights=w)
     bits = overlap.spin_bits(s)

@@ -1,30 +1,11 @@
 """Host side of tnac4o.calculate_overlap_correlations (tnac4o_amd/overlap.py) and the argument errors of tn_pair_moments.  No GPU."""
-import ctypes as ct
-
 import numpy as np
 import pytest
 
-import golden_inputs as gi
 import overlap_corr_ref as cref
 import overlap_ref as oref
+from overlap_ref import droplet, ising3x3, last_error, rmf
 from tnac4o_amd import overlap as ov
-
-
-def droplet(beta=3.0):
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=4, Ny=4, Nc=8, J=gi.droplet_J(128, 1), beta=beta)
-
-
-def ising3x3():
-    import marginals_ref as mr
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=3, Ny=3, Nc=2, J=mr.ising_3x3_nc2(), beta=1.0)
-
-
-def rmf():
-    import tnac4o_amd
-    from tnac4o_amd import auxx
-    return tnac4o_amd.tnac4o(mode='RMF', Nx=3, Ny=3, J=auxx.synthetic_rmf(3, 3, 3, 17), beta=1.0)
 
 
 # ---------------------------------------------------------------------------------------------- 1. pack_groups
@@ -242,12 +223,6 @@ def test_public_call_errors_before_any_device_work():
 
 
 # ---------------------------------------------------------------------------------------------- argument errors of the export
-def _last_error(L):
-    buf = ct.create_string_buffer(512)
-    L.tn_last_error(buf, 512)
-    return buf.value.decode()
-
-
 def test_pair_moments_argument_errors():
     """rc < 0 with a message and nothing launched: the pointers below are not device memory, they are never followed."""
     from tnac4o_amd import _lib
@@ -261,22 +236,22 @@ def test_pair_moments_argument_errors():
     for args in ((None, M, G, wpg, 32, None, wmax, 0, p, p, need, None), (p, M, G, wpg, 32, None, wmax, 0, None, p, need, None),
                  (p, M, G, wpg, 32, None, wmax, 0, p, None, need, None)):
         assert L.tn_pair_moments(*args) == -1
-        assert 'null operand' in _last_error(L)
+        assert 'null operand' in last_error(L)
     assert L.tn_pair_moments(p, M, G, wpg, 31, None, wmax, 0, p, p, need, None) == -1
-    assert 'ldr' in _last_error(L)
+    assert 'ldr' in last_error(L)
     assert L.tn_pair_moments(p, -1, G, wpg, 32, None, wmax, 0, p, p, need, None) == -1
     assert L.tn_pair_moments(p, 2 ** 31, G, wpg, 32, None, wmax, 0, p, p, need, None) == -1
     for bad_G in (0, 65):
         assert int(L.tn_pair_moments_ws_bytes(M, bad_G, wpg, 0)) == 0
         assert L.tn_pair_moments(p, M, bad_G, wpg, 4096, None, wmax, 0, p, p, 1 << 30, None) == -1
-        assert '64' in _last_error(L)
+        assert '64' in last_error(L)
     assert int(L.tn_pair_moments_ws_bytes(M, G, 33, 0)) == 0
     assert L.tn_pair_moments(p, M, G, 33, 4096, None, 1, 0, p, p, 1 << 30, None) == -1
-    assert '32' in _last_error(L)
+    assert '32' in last_error(L)
     assert L.tn_pair_moments(p, M, G, wpg, 32, None, 0, 0, p, p, need, None) == -1
-    assert 'wmax' in _last_error(L)
+    assert 'wmax' in last_error(L)
     for lanes16, dmax in ((0, 128), (1, 8)):                           # wmax dmax = 2^32 is one too many, 2^32 - dmax is the largest
         assert L.tn_pair_moments(p, M, G, wpg, 32, None, 2 ** 32 // dmax, lanes16, p, p, need, None) == -1
-        assert '4294967295' in _last_error(L)
+        assert '4294967295' in last_error(L)
         assert L.tn_pair_moments(p, M, G, wpg, 32, None, 2 ** 32 // dmax - 1, lanes16, p, p, need - 1, None) == -3
-        assert 'workspace too small' in _last_error(L)
+        assert 'workspace too small' in last_error(L)

@@ -1,23 +1,11 @@
 """Host side of tnac4o.calculate_overlap_distribution (tnac4o_amd/overlap.py) and the argument errors of tn_pair_hist.  No GPU."""
-import ctypes as ct
-
 import numpy as np
 import pytest
 
 import golden_inputs as gi
 import overlap_ref as oref
+from overlap_ref import droplet, last_error, rmf
 from tnac4o_amd import overlap as ov
-
-
-def droplet(beta=3.0):
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=4, Ny=4, Nc=8, J=gi.droplet_J(128, 1), beta=beta)
-
-
-def rmf():
-    import tnac4o_amd
-    from tnac4o_amd import auxx
-    return tnac4o_amd.tnac4o(mode='RMF', Nx=3, Ny=3, J=auxx.synthetic_rmf(3, 3, 3, 17), beta=1.0)
 
 
 # ---------------------------------------------------------------------------------------------- packers
@@ -147,6 +135,31 @@ def test_quantise():
     assert wq.size == 0 and keep.size == 0
 
 
+def test_prepare_is_condense_quantise_keep():
+    """prepare, which the three drivers call, returns exactly what the sequence they wrote out returns: the droplet rows with
+    duplicates under uniform weights and under float weights with zeros and with values that quantise to 0, at the full wmax and
+    at a smaller one."""
+    rng = np.random.default_rng(11)
+    s = droplet()
+    w = 10.0 ** rng.uniform(-12.0, 0.0, 2048)
+    w[::3] = 0.0
+    for distinct, weights in ((60, np.ones(2048)), (700, w)):
+        s.states = oref.states_with_duplicates(2048, rng, distinct).astype(np.uint8).astype(s.indtype)
+        for kind in ('spin', 'cell'):
+            rows = ov.rows_of(s, kind)[0]
+            for wmax in (ov.WMAX, ov.WMAX // 128, 5):
+                urows, W, D0 = ov.condense(rows, weights)
+                wq, keep, scale = ov.quantise(W, wmax)
+                if weights is w:
+                    assert (W == 0).any() and (wq[W > 0] == 0).any() and 2 <= keep.sum() < keep.size
+                got = ov.prepare(rows, weights, wmax)
+                assert len(got) == 4 and got[2] == scale and got[3] == D0
+                assert np.array_equal(got[0], urows[keep]) and got[0].dtype == np.uint64 and got[0].flags['C_CONTIGUOUS']
+                assert np.array_equal(got[1], wq[keep]) and got[1].dtype == np.uint32 and got[1].flags['C_CONTIGUOUS']
+    got, want = ov.prepare(rows, w), ov.quantise(ov.condense(rows, w)[1])           # wmax defaults to 2^32 - 1
+    assert np.array_equal(got[1], want[0][want[1]]) and got[2] == want[2]
+
+
 # ---------------------------------------------------------------------------------------------- distribution / moments
 def test_distribution_and_moments_by_hand():
     """Three rows of 4 bits, 0000 (weight 1), 0011 (weight 2), 1111 (weight 3): distances 2, 4, 2 with products 2, 3, 6."""
@@ -214,12 +227,6 @@ def test_public_call_names_the_lds_limit():
 
 
 # ---------------------------------------------------------------------------------------------- argument errors of the export
-def _last_error(L):
-    buf = ct.create_string_buffer(512)
-    L.tn_last_error(buf, 512)
-    return buf.value.decode()
-
-
 def test_pair_hist_argument_errors():
     """rc < 0 with a message and nothing launched: the pointers below are not device memory, they are never followed."""
     from tnac4o_amd import _lib
@@ -231,11 +238,11 @@ def test_pair_hist_argument_errors():
     for args in ((None, M, nbits, 3, None, 0, p, p, need, None), (p, M, nbits, 3, None, 0, None, p, need, None),
                  (p, M, nbits, 3, None, 0, p, None, need, None)):
         assert L.tn_pair_hist(*args) == -1
-        assert 'null operand' in _last_error(L)
+        assert 'null operand' in last_error(L)
     assert L.tn_pair_hist(p, M, nbits, 2, None, 0, p, p, need, None) == -1          # three words per row
-    assert 'ldr' in _last_error(L)
+    assert 'ldr' in last_error(L)
     assert L.tn_pair_hist(p, M, 5, 1, None, 1, p, p, need, None) == -1              # five lanes take two words
-    assert 'ldr' in _last_error(L)
+    assert 'ldr' in last_error(L)
     assert L.tn_pair_hist(p, -1, nbits, 3, None, 0, p, p, need, None) == -1
     assert L.tn_pair_hist(p, M, 0, 3, None, 0, p, p, need, None) == -1
     # the LDS limit: the largest nbits has a workspace size, one more is refused by name
@@ -243,8 +250,8 @@ def test_pair_hist_argument_errors():
     assert int(L.tn_pair_hist_ws_bytes(65, ov.MAX_NBITS + 1, 0)) == 0
     for lanes16 in (0, 1):
         assert L.tn_pair_hist(p, 65, ov.MAX_NBITS + 1, 4096, None, lanes16, p, p, 1 << 30, None) == -1
-        msg = _last_error(L)
+        msg = last_error(L)
         assert str(ov.MAX_NBITS) in msg and 'LDS' in msg, msg
     assert L.tn_pair_hist(p, M, nbits, 3, None, 0, p, p, need - 1, None) == -3
-    assert 'workspace too small' in _last_error(L)
+    assert 'workspace too small' in last_error(L)
     assert L.tn_pair_hist(p, M, nbits, 3, None, 0, p, p, 0, None) == -3

@@ -1,30 +1,11 @@
 """Host side of tnac4o.calculate_sample_correlations (tnac4o_amd/overlap.py), with the reference's integers in place of the device
 call, and the argument errors of tn_spin_moments.  No GPU."""
-import ctypes as ct
-
 import numpy as np
 import pytest
 
-import golden_inputs as gi
 import spin_moments_ref as sref
+from overlap_ref import droplet, ising3x3, last_error, rmf
 from tnac4o_amd import overlap as ov
-
-
-def droplet(beta=3.0):
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=4, Ny=4, Nc=8, J=gi.droplet_J(128, 1), beta=beta)
-
-
-def ising3x3():
-    import marginals_ref as mr
-    import tnac4o_amd
-    return tnac4o_amd.tnac4o(mode='Ising', Nx=3, Ny=3, Nc=2, J=mr.ising_3x3_nc2(), beta=1.0)
-
-
-def rmf():
-    import tnac4o_amd
-    from tnac4o_amd import auxx
-    return tnac4o_amd.tnac4o(mode='RMF', Nx=3, Ny=3, J=auxx.synthetic_rmf(3, 3, 3, 17), beta=1.0)
 
 
 def host_pipeline(bits, w):
@@ -189,12 +170,6 @@ def test_ops_wrapper_refuses_before_the_library_call():
 
 
 # ---------------------------------------------------------------------------------------------- argument errors of the export
-def _last_error(L):
-    buf = ct.create_string_buffer(512)
-    L.tn_last_error(buf, 512)
-    return buf.value.decode()
-
-
 def test_spin_moments_argument_errors(monkeypatch):
     """rc < 0 with a message and nothing launched: the pointers below are not device memory, they are never followed."""
     from tnac4o_amd import _lib
@@ -215,21 +190,21 @@ def test_spin_moments_argument_errors(monkeypatch):
     for args in ((None, M, n, 2, None, wmax, p, n + 2, p, need, None), (p, M, n, 2, None, wmax, None, n + 2, p, need, None),
                  (p, M, n, 2, None, wmax, p, n + 2, None, need, None)):
         assert L.tn_spin_moments(*args) == -1
-        assert 'null operand' in _last_error(L)
+        assert 'null operand' in last_error(L)
     assert L.tn_spin_moments(p, M, n, 1, None, wmax, p, n + 2, p, need, None) == -1
-    assert 'ldr' in _last_error(L)
+    assert 'ldr' in last_error(L)
     assert L.tn_spin_moments(p, M, n, 2, None, wmax, p, n + 1, p, need, None) == -1
-    assert 'ldo' in _last_error(L)
+    assert 'ldo' in last_error(L)
     for bad_M in (-1, 2 ** 32):
         assert int(L.tn_spin_moments_ws_bytes(bad_M, n, wmax)) == 0
         assert L.tn_spin_moments(p, bad_M, n, 2, None, wmax, p, n + 2, p, 1 << 40, None) == -1
-        assert '4294967296' in _last_error(L)
+        assert '4294967296' in last_error(L)
     for bad_n in (0, 65535):
         assert int(L.tn_spin_moments_ws_bytes(M, bad_n, wmax)) == 0
         assert L.tn_spin_moments(p, M, bad_n, 1024, None, wmax, p, 65537, p, 1 << 40, None) == -1
-        assert '65534' in _last_error(L)
+        assert '65534' in last_error(L)
     assert int(L.tn_spin_moments_ws_bytes(M, n, 0)) == 0
     assert L.tn_spin_moments(p, M, n, 2, None, 0, p, n + 2, p, need, None) == -1
-    assert 'wmax' in _last_error(L)
+    assert 'wmax' in last_error(L)
     assert L.tn_spin_moments(p, M, n, 2, None, wmax, p, n + 2, p, need - 1, None) == -3
-    assert 'workspace too small' in _last_error(L)
+    assert 'workspace too small' in last_error(L)

@@ -1,22 +1,11 @@
-// Weighted histogram of the pairwise distances of M packed rows (tn_pair_hist): hist[d] = sum_{a<b} w_a w_b [dist(a, b) = d], an exact
-// integer in two 64-bit limbs.  Behind tnac4o.calculate_overlap_distribution: the overlap distribution P(q) of a set of samples is
-// this histogram over the bit-packed spins (dist = popcount(a XOR b)) or over the 16-bit cell states (dist = lanes that differ).
-//
-// pair_hist_kernel: the upper triangle of the pair matrix in tiles of 64 x 64 rows, 256 threads with a 4 x 4 sub-tile each.  Both row
-// blocks pass through LDS in chunks of PH_CW words (word-major, so a thread reads its four rows with two 16-byte loads); the 16
-// running distances stay in registers.  After the last chunk the 16 products w_a w_b go into the workgroup's own histogram in LDS
-// with integer atomics: a 64-bit add on the low limb whose returned old value tells whether this add wrapped, in which case 1 goes
-// to the high limb -- every wrap is seen by exactly one add, so the two limbs are exact whatever the interleaving.  Products of one
-// thread that fall into the same bin in a row are added up in registers first (identical rows: 16 times fewer atomics).  The grid is
-// persistent: workgroup g takes tiles g, g + G, ... and writes its histogram once, into slab g of the workspace;
-// pair_hist_reduce_kernel adds the slabs bin by bin with carry and writes every bin of the result.  Integer sums: the result does not
-// depend on G, on the tile order or on the run.
-//
-// Second moments of the distances within word groups of the rows (tn_pair_moments), behind tnac4o.calculate_overlap_correlations:
-// described where its kernels start, further down.
-//
-// Weighted counts of the samples in which two bits of the rows differ, for every pair of bits (tn_spin_moments), behind
-// tnac4o.calculate_sample_correlations: behind the kernels of tn_pair_moments.
+// Exact integer statistics of M packed rows, the samples of tnac4o: three entries, each a persistent grid over the tiles of an upper
+// triangle whose workgroups write partial sums into slabs of the workspace, and a kernel that adds the slabs.  Integer sums
+// throughout: no result depends on the grid, on the tile order or on the run.
+//   tn_pair_hist     hist[d] = sum_{a<b} w_a w_b [dist(a, b) = d]                  tnac4o.calculate_overlap_distribution
+//   tn_pair_moments  out[i][j] = sum_{a<b} w_a w_b d_i(a, b) d_j(a, b)             tnac4o.calculate_overlap_correlations
+//   tn_spin_moments  out[i][j] = sum_a w_a [x_a,i != x_a,j]                        tnac4o.calculate_sample_correlations
+// dist = popcount(a XOR b) over bit-packed spins, or the 16-bit lanes (cell states) that differ.  Each family is described where its
+// kernels start; what they share comes first.
 #include "common.h"
 
 namespace tn {
@@ -39,6 +28,80 @@ __device__ __forceinline__ unsigned pair_dist(uint64_t a, uint64_t b) {
     const uint64_t t = (((x & low) + low) | x) & ~low;
     return (unsigned)__popcll(t);
 }
+
+// tile t of the upper triangle of a matrix of blocks, column by column: bj = the largest j with j (j + 1) / 2 <= t, bi = t - bj (bj + 1) / 2
+// <= bj
+__host__ __device__ __forceinline__ void tri_decode(int64_t t, int64_t& bi, int64_t& bj) {
+    bj = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (bj > 0 && bj * (bj + 1) / 2 > t) --bj;
+    while ((bj + 1) * (bj + 2) / 2 <= t) ++bj;
+    bi = t - bj * (bj + 1) / 2;
+}
+// tiles of `tile` x `tile` rows in the upper triangle of the M x M pairs, the diagonal ones included (no pair: none)
+inline int64_t tri_tiles(int64_t M, int tile) {
+    if (M < 2) return 0;
+    const int64_t nblk = cdiv(M, tile);
+    return nblk * (nblk + 1) / 2;
+}
+
+// (lo, hi) += (vlo, vhi): a 128-bit add on two 64-bit limbs.  (Inlined, it is the carry written out by hand, but the compiler's
+// schedule and register allocation follow the order in which values are formed: with `run` as one struct in pair_hist_kernel and the
+// shifted high sum formed first in pair_moments_kernel, the loops of both compile to the instructions and registers they had before
+// this helper; in pair_moments_kernel the fold itself, once per tile, comes out in another order.)
+__host__ __device__ __forceinline__ void add128(unsigned long long& lo, unsigned long long& hi, unsigned long long vlo, unsigned long long vhi) {
+    lo += vlo;
+    hi += vhi + (lo < vlo ? 1u : 0u);
+}
+
+// mask of the last word of a row of nbits bits (lanes16: 16-bit lanes): what lies behind the row in that word is cut
+inline uint64_t last_word_mask(int64_t nbits, int lanes16) {
+    const int per = lanes16 ? 4 : 64, used = (int)(nbits - (cdiv(nbits, per) - 1) * per);
+    return used == per ? ~(uint64_t)0 : (((uint64_t)1 << (used * (lanes16 ? 16 : 1))) - 1);
+}
+
+// workgroups of a persistent grid: the value of the entry's switch (read per call) where it is positive, else `dflt`; at most PH_MAX_WGS
+// and never more than there are units of work
+inline int64_t persistent_wgs(int64_t asked, int64_t dflt, int64_t work) {
+    return std::min<int64_t>(std::min<int64_t>(asked > 0 ? asked : dflt, PH_MAX_WGS), work);
+}
+
+// launch of a persistent kernel of 256 threads with `lds` bytes of dynamic LDS, which it has to be allowed first above 48 KiB
+template <typename... P, typename... A>
+void launch_persistent(void (*kernel)(P...), hipStream_t st, int64_t nwg, size_t lds, A... args) {
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    prof_begin(st, PROF_MISC);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(256), lds, st, args...);
+    prof_end(st, PROF_MISC, 0.0, 0.0);
+}
+
+// What the three entries refuse alike, as TN_CHECK_ARG does (-1, "<entry>: <what>"), and a workspace below what <entry>_ws_bytes asks
+// for (-3); 0: nothing to refuse
+inline int refuse(const char* entry, const char* what) {
+    set_error("%s: %s", entry, what);
+    return -1;
+}
+inline int check_pair_count(const char* entry, int64_t M) {
+    return M >= 0 && M < ((int64_t)1 << 31) ? 0 : refuse(entry, "M negative or not below 2^31");
+}
+inline int check_operands(const char* entry, bool all, int64_t ldr, int64_t nwords, const char* short_row) {
+    if (!all) return refuse(entry, "null operand");
+    return ldr >= nwords ? 0 : refuse(entry, short_row);
+}
+inline int check_workspace(const char* entry, int64_t ws_bytes, int64_t need) {
+    if (ws_bytes >= need) return 0;
+    set_error("%s: workspace too small (%lld bytes, %s_ws_bytes asks for %lld)", entry, (long long)ws_bytes, entry, (long long)need);
+    return -3;
+}
+
+// ---- tn_pair_hist: hist[d] = sum_{a<b} w_a w_b [dist(a, b) = d], an exact integer in two 64-bit limbs ---------------------------------
+// pair_hist_kernel: the upper triangle of the pair matrix in tiles of 64 x 64 rows, 256 threads with a 4 x 4 sub-tile each.  Both row
+// blocks pass through LDS in chunks of PH_CW words (word-major, so a thread reads its four rows with two 16-byte loads); the 16
+// running distances stay in registers.  After the last chunk the 16 products w_a w_b go into the workgroup's own histogram in LDS
+// with integer atomics: a 64-bit add on the low limb whose returned old value tells whether this add wrapped, in which case 1 goes
+// to the high limb -- every wrap is seen by exactly one add, so the two limbs are exact whatever the interleaving.  Products of one
+// thread that fall into the same bin in a row are added up in registers first (identical rows: 16 times fewer atomics).  The grid is
+// persistent: workgroup g takes tiles g, g + G, ... and writes its histogram once, into slab g of the workspace;
+// pair_hist_reduce_kernel adds the slabs bin by bin with carry and writes every bin of the result.
 
 // rows [r0, r0 + 64) x words [k0, k0 + PH_CW) into dst[k * PH_PITCH + r]; rows >= M and words >= nwords read as 0 and are never
 // addressed, the last word of a row is cut to nbits
@@ -74,11 +137,8 @@ __global__ __launch_bounds__(256) void pair_hist_kernel(const uint64_t* __restri
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     for (int64_t i = tid; i < 2 * nbins; i += 256) hist[i] = 0;
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        // tile t of the upper triangle, column by column: bj = the largest j with j (j + 1) / 2 <= t, bi = t - bj (bj + 1) / 2 <= bj
-        int64_t bj = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while (bj > 0 && bj * (bj + 1) / 2 > t) --bj;
-        while ((bj + 1) * (bj + 2) / 2 <= t) ++bj;
-        const int64_t bi = t - bj * (bj + 1) / 2;
+        int64_t bi, bj;
+        tri_decode(t, bi, bj);
         const int64_t a0 = bi * PH_TILE, b0 = bj * PH_TILE;
         unsigned dist[4][4];
 #pragma unroll
@@ -112,8 +172,7 @@ __global__ __launch_bounds__(256) void pair_hist_kernel(const uint64_t* __restri
             wa[i] = ra < M ? (weights ? weights[ra] : 1u) : 0u;
             wb[i] = rb < M ? (weights ? weights[rb] : 1u) : 0u;
         }
-        unsigned cur = 0;
-        unsigned long long lo = 0, hi = 0;
+        struct { unsigned d; unsigned long long lo, hi; } run = {0, 0, 0};             // the pairs in a row that share a bin: the bin, their sum
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -121,14 +180,13 @@ __global__ __launch_bounds__(256) void pair_hist_kernel(const uint64_t* __restri
                 const unsigned long long p = wa[i] * wb[j];
                 if (p == 0 || a0 + ty * 4 + i >= b0 + tx * 4 + j) continue;       // (diagonal tiles keep a < b)
                 const unsigned d = dist[i][j];
-                if (d != cur) {
-                    if (lo | hi) hist_add(hist, cur, lo, hi);
-                    cur = d; lo = 0; hi = 0;
+                if (d != run.d) {
+                    if (run.lo | run.hi) hist_add(hist, run.d, run.lo, run.hi);
+                    run.d = d; run.lo = 0; run.hi = 0;
                 }
-                lo += p;
-                if (lo < p) ++hi;
+                add128(run.lo, run.hi, p, 0);
             }
-        if (lo | hi) hist_add(hist, cur, lo, hi);
+        if (run.lo | run.hi) hist_add(hist, run.d, run.lo, run.hi);
     }
     __syncthreads();
     ulonglong2* out = (ulonglong2*)(slabs + (int64_t)blockIdx.x * 2 * nbins);
@@ -140,8 +198,7 @@ __device__ __forceinline__ ulonglong2 slab_sum(const unsigned long long* __restr
     unsigned long long lo = 0, hi = 0;
     for (int64_t s = 0; s < nslab; ++s) {
         const ulonglong2 v = ((const ulonglong2*)(slabs + s * 2 * nbins))[d];
-        lo += v.x;
-        hi += v.y + (lo < v.x ? 1u : 0u);
+        add128(lo, hi, v.x, v.y);
     }
     return make_ulonglong2(lo, hi);
 }
@@ -155,18 +212,10 @@ __global__ __launch_bounds__(256) void pair_hist_reduce_kernel(const unsigned lo
 }
 
 inline int64_t pair_hist_nwords(int64_t nbits, int lanes16) { return lanes16 ? cdiv(nbits, 4) : cdiv(nbits, 64); }
-inline int64_t pair_hist_tiles(int64_t M) {
-    if (M < 2) return 0;
-    const int64_t nblk = cdiv(M, PH_TILE);
-    return nblk * (nblk + 1) / 2;
-}
-// workgroups of the persistent grid: as many as fit the device's 256 compute units with this much LDS each (at most 4 per unit), or
-// TN_PAIR_HIST_WGS (read per call); never more than there are tiles
+// the persistent grid: TN_PAIR_HIST_WGS, or as many workgroups as fit the device's 256 compute units with this much LDS each (at most 4
+// per unit)
 inline int64_t pair_hist_wgs(int64_t M, int64_t nbins) {
-    const int64_t tiles = pair_hist_tiles(M);
-    int64_t g = env_i64("TN_PAIR_HIST_WGS", 0);
-    if (g <= 0) g = 256 * std::min<int64_t>(4, PH_LDS / (PH_STAGE_BYTES + 16 * nbins));
-    return std::min<int64_t>(std::min<int64_t>(g, PH_MAX_WGS), tiles);
+    return persistent_wgs(env_i64("TN_PAIR_HIST_WGS", 0), 256 * std::min<int64_t>(4, PH_LDS / (PH_STAGE_BYTES + 16 * nbins)), tri_tiles(M, PH_TILE));
 }
 inline bool pair_hist_shape_ok(int64_t M, int64_t nbits) { return M >= 0 && M < ((int64_t)1 << 31) && nbits >= 1 && nbits + 1 <= PH_MAX_BINS; }
 
@@ -247,10 +296,8 @@ __global__ __launch_bounds__(256) void pair_moments_kernel(const uint64_t* __res
     }
     const int gpc = PM_CW / wpg;                               // whole groups per chunk
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        int64_t bj = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);        // as pair_hist_kernel
-        while (bj > 0 && bj * (bj + 1) / 2 > t) --bj;
-        while ((bj + 1) * (bj + 2) / 2 <= t) ++bj;
-        const int64_t bi = t - bj * (bj + 1) / 2;
+        int64_t bi, bj;
+        tri_decode(t, bi, bj);
         const int64_t a0 = bi * PM_TILE, b0 = bj * PM_TILE;
         // ---- phase 1: distances and products of the tile's pairs
         for (int g0 = 0; g0 < G; g0 += gpc) {
@@ -316,11 +363,9 @@ __global__ __launch_bounds__(256) void pair_moments_kernel(const uint64_t* __res
         }
 #pragma unroll
         for (int n = 0; n < EPT; ++n) {
-            const unsigned long long t = sh0[n] << 32;
-            lo[n] += sl0[n];
-            hi[n] += lo[n] < sl0[n] ? 1u : 0u;
-            lo[n] += t;
-            hi[n] += (sh0[n] >> 32) + (lo[n] < t ? 1u : 0u);
+            const unsigned long long t = sh0[n] << 32;                            // (formed first: see add128)
+            add128(lo[n], hi[n], sl0[n], 0);
+            add128(lo[n], hi[n], t, sh0[n] >> 32);
         }
     }
     __syncthreads();
@@ -333,8 +378,7 @@ __global__ __launch_bounds__(256) void pair_moments_kernel(const uint64_t* __res
         unsigned long long l = 0, h = 0;
         for (int sl = 0; sl < nsl; ++sl) {
             const ulonglong2 v = red[sl * ne + e];
-            l += v.x;
-            h += v.y + (l < v.x ? 1u : 0u);
+            add128(l, h, v.x, v.y);
         }
         out[e] = make_ulonglong2(l, h);
     }
@@ -352,43 +396,24 @@ __global__ __launch_bounds__(256) void pair_moments_reduce_kernel(const unsigned
     ((ulonglong2*)out)[j * (G + 1) + i] = v;
 }
 
-inline int64_t pair_moments_tiles(int64_t M) {
-    if (M < 2) return 0;
-    const int64_t nblk = cdiv(M, PM_TILE);
-    return nblk * (nblk + 1) / 2;
-}
-// workgroups of the persistent grid: what fits 256 compute units with this much LDS each (at most 4 per unit), or TN_PAIR_MOMENTS_WGS
-// (read per call); never more than there are tiles
+// the persistent grid: TN_PAIR_MOMENTS_WGS, or what fits 256 compute units with this much LDS each (at most 4 per unit)
 inline int64_t pair_moments_wgs(int64_t M, int64_t G) {
-    int64_t g = env_i64("TN_PAIR_MOMENTS_WGS", 0);
-    if (g <= 0) g = 256 * std::min<int64_t>(4, PH_LDS / pair_moments_lds(G));
-    return std::min<int64_t>(std::min<int64_t>(g, PH_MAX_WGS), pair_moments_tiles(M));
+    return persistent_wgs(env_i64("TN_PAIR_MOMENTS_WGS", 0), 256 * std::min<int64_t>(4, PH_LDS / pair_moments_lds(G)), tri_tiles(M, PM_TILE));
 }
 inline int64_t pair_moments_dmax(int64_t wpg, int lanes16) { return (lanes16 ? 4 : 64) * wpg; }
 inline bool pair_moments_shape_ok(int64_t M, int64_t G, int64_t wpg) {
     return M >= 0 && M < ((int64_t)1 << 31) && G >= 1 && G <= PM_MAX_G && wpg >= 1 && wpg <= PM_MAX_WPG;
 }
 
-template <bool LANES16, int EPT>
-void pair_moments_launch(hipStream_t st, int64_t nwg, size_t lds, const uint64_t* rows, int64_t M, int G, int wpg, int64_t ldr, const uint32_t* weights,
-                         uint32_t wmax, int ne, int64_t ntiles, unsigned long long* slabs) {
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)pair_moments_kernel<LANES16, EPT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    prof_begin(st, PROF_MISC);
-    hipLaunchKernelGGL((pair_moments_kernel<LANES16, EPT>), dim3((unsigned)nwg), dim3(256), lds, st, rows, M, G, wpg, ldr, weights, wmax, ne, ntiles,
-                       slabs);
-    prof_end(st, PROF_MISC, 0.0, 0.0);
-}
 // elements per thread: 3 while that gives every element at least two slices of the pairs, else 9
 constexpr int PM_EPT_SMALL = 3, PM_EPT_LARGE = 9, PM_NE_SMALL = PM_EPT_SMALL * 256 / 2;
 static_assert((PM_MAX_G + 1) * (PM_MAX_G + 2) / 2 <= PM_EPT_LARGE * 256, "nine elements per thread cover the largest G");
 static_assert(PM_STAGE_BYTES >= PM_EPT_SMALL * 256 * 16, "the staging area holds the units of the final sum at three per thread");
 static_assert(PM_STAGE_BYTES + PM_P_BYTES + 2 * PM_DPITCH * 28 >= PM_EPT_LARGE * 256 * 16 && 28 * 29 / 2 > PM_NE_SMALL,
               "and the whole LDS of G >= 27 those at nine per thread");
-template <bool LANES16, typename... A>
-void pair_moments_launch_ept(int ne, A... a) {
-    if (ne <= PM_NE_SMALL) pair_moments_launch<LANES16, PM_EPT_SMALL>(a...);
-    else pair_moments_launch<LANES16, PM_EPT_LARGE>(a...);
+template <bool LANES16>
+auto* pair_moments_instance(int ne) {
+    return ne <= PM_NE_SMALL ? &pair_moments_kernel<LANES16, PM_EPT_SMALL> : &pair_moments_kernel<LANES16, PM_EPT_LARGE>;
 }
 
 // ---- tn_spin_moments: out[i][j] = sum_a w_a [x_a,i != x_a,j] over every pair of BITS i, j of the rows, two constant pseudo-bits appended -
@@ -451,6 +476,9 @@ __global__ __launch_bounds__(256) void spin_transpose_kernel(const uint64_t* __r
     }
 }
 
+// share of workgroup g of the nwg: units [spin_share(g), spin_share(g + 1))
+__host__ __device__ __forceinline__ int64_t spin_share(int64_t g, int64_t total, int64_t nwg) { return g * total / nwg; }
+
 // UNIT: one plane (wmax = 1 or no weights)
 template <bool UNIT>
 __global__ __launch_bounds__(256) void spin_moments_kernel(const uint64_t* __restrict__ T, const uint64_t* __restrict__ Wp, int64_t KW,
@@ -459,16 +487,14 @@ __global__ __launch_bounds__(256) void spin_moments_kernel(const uint64_t* __res
     __shared__ uint64_t sA[PH_CW * PH_PITCH], sB[PH_CW * PH_PITCH], sW[PH_CW * SM_MAX_P];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int64_t total = ntiles * nchunks;                            // units (tile, chunk), tile-major; this workgroup's share:
-    const int64_t end = ((int64_t)blockIdx.x + 1) * total / gridDim.x;
+    const int64_t end = spin_share((int64_t)blockIdx.x + 1, total, gridDim.x);
     const int plo = min(P, 16);
     int piece = 0;
-    for (int64_t u = (int64_t)blockIdx.x * total / gridDim.x; u < end; ++piece) {
+    for (int64_t u = spin_share(blockIdx.x, total, gridDim.x); u < end; ++piece) {
         const int64_t t = u / nchunks, c0 = u % nchunks, c1 = c0 + end - u < nchunks ? c0 + end - u : nchunks;
         u += c1 - c0;
-        int64_t bj = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);        // as pair_hist_kernel
-        while (bj > 0 && bj * (bj + 1) / 2 > t) --bj;
-        while ((bj + 1) * (bj + 2) / 2 <= t) ++bj;
-        const int64_t bi = t - bj * (bj + 1) / 2;
+        int64_t bi, bj;
+        tri_decode(t, bi, bj);
         const int64_t a0 = bi * PH_TILE, b0 = bj * PH_TILE;
         uint64_t acc[4][4];
 #pragma unroll
@@ -593,9 +619,6 @@ __global__ __launch_bounds__(256) void spin_moments_kernel(const uint64_t* __res
     }
 }
 
-// share of workgroup g of the nwg: units [spin_share(g), spin_share(g + 1))
-__host__ __device__ __forceinline__ int64_t spin_share(int64_t g, int64_t total, int64_t nwg) { return g * total / nwg; }
-
 // out[i][j] (and out[j][i] off the diagonal tiles) = entry (r, c) of tile t summed over its pieces, for every tile that was cut.  The
 // workgroups that hold units of tile t, [t nchunks, (t + 1) nchunks), are consecutive; a tile that one of them holds whole is in out
 // already.  The piece of workgroup g is in slab 2 g when its share starts inside the tile, else in slab 2 g + 1.
@@ -609,10 +632,8 @@ __global__ __launch_bounds__(256) void spin_moments_reduce_kernel(const uint64_t
     while (spin_share(g + 1, total, nwg) <= lo) ++g;
     if (spin_share(g + 1, total, nwg) >= hi) return;                   // (it starts at or before lo: the tile is whole)
     const int r = (int)(e % SM_TILE_WORDS) / PH_TILE, c = (int)(e % PH_TILE);
-    int64_t bj = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (bj > 0 && bj * (bj + 1) / 2 > t) --bj;
-    while ((bj + 1) * (bj + 2) / 2 <= t) ++bj;
-    const int64_t bi = t - bj * (bj + 1) / 2;
+    int64_t bi, bj;
+    tri_decode(t, bi, bj);
     const int64_t gi = bi * PH_TILE + r, gj = bj * PH_TILE + c;
     if (gi >= nrows || gj >= nrows) return;
     uint64_t s = 0;
@@ -646,11 +667,8 @@ inline SpinMomentsPlan spin_moments_plan(int64_t M, int64_t nbits, uint32_t wmax
     p.KW = cdiv(M, 64);
     p.P = spin_moments_planes(wmax);
     p.ntiles = p.NB * (p.NB + 1) / 2;
-    int64_t g = env_i64("TN_SPIN_MOMENTS_WGS", 0);
-    if (g <= 0) g = 256 * (p.P == 1 ? 3 : 2);
-    g = std::min<int64_t>(g, PH_MAX_WGS);
     p.nchunks = std::max<int64_t>(1, cdiv(p.KW, PH_CW));
-    p.nwg = std::min<int64_t>(g, p.ntiles * p.nchunks);
+    p.nwg = persistent_wgs(env_i64("TN_SPIN_MOMENTS_WGS", 0), 256 * (p.P == 1 ? 3 : 2), p.ntiles * p.nchunks);
     p.t_words = p.NB * PH_TILE * p.KW;
     p.w_words = (int64_t)p.P * p.KW;
     p.slab_words = p.nwg > 1 ? 2 * p.nwg * SM_TILE_WORDS : 0;
@@ -673,7 +691,7 @@ int64_t tn_pair_hist_ws_bytes(int64_t M, int64_t nbits, int lanes16) {
 
 int tn_pair_hist(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, int lanes16, uint64_t* hist_out, void* ws,
                  int64_t ws_bytes, void* stream) {
-    TN_CHECK_ARG(M >= 0 && M < ((int64_t)1 << 31), "M negative or not below 2^31");
+    if (int rc = check_pair_count(__func__, M)) return rc;
     TN_CHECK_ARG(nbits >= 1, "nbits must be positive");
     if (nbits + 1 > PH_MAX_BINS) {
         set_error("tn_pair_hist: nbits = %lld exceeds the limit of %lld (the histogram, 16 bytes per bin, and the staging must fit 160 KiB of LDS)",
@@ -681,30 +699,14 @@ int tn_pair_hist(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, co
         return -1;
     }
     const int64_t nwords = pair_hist_nwords(nbits, lanes16), nbins = nbits + 1;
-    TN_CHECK_ARG(rows && hist_out && ws, "null operand");
-    TN_CHECK_ARG(ldr >= nwords, "ldr shorter than a row");
-    const int64_t need = tn_pair_hist_ws_bytes(M, nbits, lanes16);
-    if (ws_bytes < need) {
-        set_error("tn_pair_hist: workspace too small (%lld bytes, tn_pair_hist_ws_bytes asks for %lld)", (long long)ws_bytes, (long long)need);
-        return -3;
-    }
+    if (int rc = check_operands(__func__, rows && hist_out && ws, ldr, nwords, "ldr shorter than a row")) return rc;
+    if (int rc = check_workspace(__func__, ws_bytes, tn_pair_hist_ws_bytes(M, nbits, lanes16))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t ntiles = pair_hist_tiles(M), nwg = pair_hist_wgs(M, nbins);
+    const int64_t ntiles = tri_tiles(M, PH_TILE), nwg = pair_hist_wgs(M, nbins);
     unsigned long long* slabs = (unsigned long long*)ws;
     if (nwg > 0) {
-        const int per = lanes16 ? 4 : 64, used = (int)(nbits - (nwords - 1) * per);            // bits or lanes of the last word that belong to the row
-        const uint64_t last_mask = used == per ? ~(uint64_t)0 : (((uint64_t)1 << (used * (lanes16 ? 16 : 1))) - 1);
-        const size_t lds = (size_t)(PH_STAGE_BYTES + 16 * nbins);
-        const void* fn = lanes16 ? (const void*)pair_hist_kernel<true> : (const void*)pair_hist_kernel<false>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        prof_begin(st, PROF_MISC);
-        if (lanes16)
-            hipLaunchKernelGGL(pair_hist_kernel<true>, dim3((unsigned)nwg), dim3(256), lds, st, rows, M, nwords, ldr, last_mask, weights, nbins,
-                               ntiles, slabs);
-        else
-            hipLaunchKernelGGL(pair_hist_kernel<false>, dim3((unsigned)nwg), dim3(256), lds, st, rows, M, nwords, ldr, last_mask, weights, nbins,
-                               ntiles, slabs);
-        prof_end(st, PROF_MISC, 0.0, 0.0);
+        launch_persistent(lanes16 ? &pair_hist_kernel<true> : &pair_hist_kernel<false>, st, nwg, (size_t)(PH_STAGE_BYTES + 16 * nbins), rows, M, nwords, ldr,
+                          last_word_mask(nbits, lanes16), weights, nbins, ntiles, slabs);
         TN_CHECK_LAUNCH("pair_hist_kernel");
     }
     TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(pair_hist_reduce_kernel, dim3((unsigned)cdiv(nbins, 256)), dim3(256), 0, st, slabs, nwg, nbins,
@@ -721,7 +723,7 @@ int64_t tn_pair_moments_ws_bytes(int64_t M, int64_t G, int64_t wpg, int lanes16)
 
 int tn_pair_moments(const uint64_t* rows, int64_t M, int64_t G, int64_t wpg, int64_t ldr, const uint32_t* weights, uint32_t wmax, int lanes16,
                     uint64_t* out, void* ws, int64_t ws_bytes, void* stream) {
-    TN_CHECK_ARG(M >= 0 && M < ((int64_t)1 << 31), "M negative or not below 2^31");
+    if (int rc = check_pair_count(__func__, M)) return rc;
     TN_CHECK_ARG(G >= 1 && G <= PM_MAX_G, "G outside 1 .. 64 (the number of groups)");
     TN_CHECK_ARG(wpg >= 1 && wpg <= PM_MAX_WPG, "wpg outside 1 .. 32 (the words of a group)");
     TN_CHECK_ARG(wmax >= 1, "wmax must be at least 1");
@@ -731,23 +733,15 @@ int tn_pair_moments(const uint64_t* rows, int64_t M, int64_t G, int64_t wpg, int
                   (unsigned long long)wmax, (long long)dmax);
         return -1;
     }
-    TN_CHECK_ARG(rows && out && ws, "null operand");
-    TN_CHECK_ARG(ldr >= G * wpg, "ldr shorter than a row of G * wpg words");
-    const int64_t need = tn_pair_moments_ws_bytes(M, G, wpg, lanes16);
-    if (ws_bytes < need) {
-        set_error("tn_pair_moments: workspace too small (%lld bytes, tn_pair_moments_ws_bytes asks for %lld)", (long long)ws_bytes, (long long)need);
-        return -3;
-    }
+    if (int rc = check_operands(__func__, rows && out && ws, ldr, G * wpg, "ldr shorter than a row of G * wpg words")) return rc;
+    if (int rc = check_workspace(__func__, ws_bytes, tn_pair_moments_ws_bytes(M, G, wpg, lanes16))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t ntiles = pair_moments_tiles(M), nwg = pair_moments_wgs(M, G);
+    const int64_t ntiles = tri_tiles(M, PM_TILE), nwg = pair_moments_wgs(M, G);
     const int ne = (int)pair_moments_ne(G);
     unsigned long long* slabs = (unsigned long long*)ws;
     if (nwg > 0) {
-        const size_t lds = (size_t)pair_moments_lds(G);
-        if (lanes16)
-            pair_moments_launch_ept<true>(ne, st, nwg, lds, rows, M, (int)G, (int)wpg, ldr, weights, wmax, ne, ntiles, slabs);
-        else
-            pair_moments_launch_ept<false>(ne, st, nwg, lds, rows, M, (int)G, (int)wpg, ldr, weights, wmax, ne, ntiles, slabs);
+        launch_persistent(lanes16 ? pair_moments_instance<true>(ne) : pair_moments_instance<false>(ne), st, nwg, (size_t)pair_moments_lds(G), rows, M, (int)G,
+                          (int)wpg, ldr, weights, wmax, ne, ntiles, slabs);
         TN_CHECK_LAUNCH("pair_moments_kernel");
     }
     TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(pair_moments_reduce_kernel, dim3((unsigned)cdiv(ne, 256)), dim3(256), 0, st, slabs, nwg, (int)G, ne,
@@ -771,14 +765,9 @@ int tn_spin_moments(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr,
     }
     TN_CHECK_ARG(wmax >= 1, "wmax must be at least 1");
     const int64_t nwords = cdiv(nbits, 64), nrows = nbits + 2;
-    TN_CHECK_ARG(rows && out && ws, "null operand");
-    TN_CHECK_ARG(ldr >= nwords, "ldr shorter than a row");
+    if (int rc = check_operands(__func__, rows && out && ws, ldr, nwords, "ldr shorter than a row")) return rc;
     TN_CHECK_ARG(ldo >= nrows, "ldo shorter than a row of nbits + 2 entries");
-    const int64_t need = tn_spin_moments_ws_bytes(M, nbits, wmax);
-    if (ws_bytes < need) {
-        set_error("tn_spin_moments: workspace too small (%lld bytes, tn_spin_moments_ws_bytes asks for %lld)", (long long)ws_bytes, (long long)need);
-        return -3;
-    }
+    if (int rc = check_workspace(__func__, ws_bytes, tn_spin_moments_ws_bytes(M, nbits, wmax))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const SpinMomentsPlan p = spin_moments_plan(M, nbits, wmax);
     uint64_t* T = (uint64_t*)ws;
@@ -786,20 +775,12 @@ int tn_spin_moments(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr,
     uint64_t* slabs = Wp + p.w_words;
     const int P = weights ? p.P : 1;                       // without weights there is one plane, whatever wmax
     if (p.KW > 0) {
-        const int used = (int)(nbits - (nwords - 1) * 64);
-        const uint64_t last_mask = used == 64 ? ~(uint64_t)0 : (((uint64_t)1 << used) - 1);
         TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(spin_transpose_kernel, dim3((unsigned)cdiv(p.KW, SM_TC), (unsigned)(p.NB + 1)), dim3(256), 0, st,
-                                                         rows, M, nbits, nwords, ldr, last_mask, weights, wmax, P, p.NB, p.KW, T, Wp));
+                                                         rows, M, nbits, nwords, ldr, last_word_mask(nbits, 0), weights, wmax, P, p.NB, p.KW, T, Wp));
         TN_CHECK_LAUNCH("spin_transpose_kernel");
     }
-    prof_begin(st, PROF_MISC);
-    if (P == 1)
-        hipLaunchKernelGGL(spin_moments_kernel<true>, dim3((unsigned)p.nwg), dim3(256), 0, st, T, Wp, p.KW, P, p.ntiles, p.nchunks, nrows, out,
-                           ldo, slabs);
-    else
-        hipLaunchKernelGGL(spin_moments_kernel<false>, dim3((unsigned)p.nwg), dim3(256), 0, st, T, Wp, p.KW, P, p.ntiles, p.nchunks, nrows, out,
-                           ldo, slabs);
-    prof_end(st, PROF_MISC, 0.0, 0.0);
+    launch_persistent(P == 1 ? &spin_moments_kernel<true> : &spin_moments_kernel<false>, st, p.nwg, 0, T, Wp, p.KW, P, p.ntiles, p.nchunks, nrows, out, ldo,
+                      slabs);
     TN_CHECK_LAUNCH("spin_moments_kernel");
     if (p.nwg > 1) {
         TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(spin_moments_reduce_kernel, dim3((unsigned)cdiv(p.ntiles * SM_TILE_WORDS, 256)), dim3(256), 0, st,

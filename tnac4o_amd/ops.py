@@ -1005,29 +1005,54 @@ def stack_cell_law(HL, HR, F, dmap, rmap):
     return D
 
 
+def _packed_rows(rows):
+    """The packed-rows operand of the sample statistics (pair_hist, pair_moments, spin_moments): (M, ld)."""
+    if not rows.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % rows.device)
+    if rows.dim() != 2 or rows.element_size() != 8 or rows.is_floating_point() or rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise TypeError('rows: a 2-d tensor of 64-bit integer words with unit stride along a row')
+    return int(rows.shape[0]), int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+
+
+def _row_weights(weights, M):
+    """The weights operand: its pointer, None without weights."""
+    if weights is None:
+        return None
+    if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous() or weights.numel() != M:
+        raise TypeError('weights: a contiguous device tensor of M 32-bit integers')
+    return weights.data_ptr()
+
+
+def _wmax(wmax, default):
+    """The largest weight a statistic reads, `default` for None."""
+    wmax = int(default if wmax is None else wmax)
+    if not 0 <= wmax < 2 ** 32:
+        raise ValueError('wmax must fit 32 bits')
+    return wmax
+
+
+def _stat_buffers(query, rows, M, out_shape, *shape):
+    """(rows pointer -- the workspace's when there is no row --, out, workspace pointer, its bytes) of a sample statistic.  The bytes
+    are query(M, *shape) of the library, asked on every call: they follow the TN_*_WGS switch."""
+    wsb = int(getattr(lib(), query)(M, *shape))
+    ws = workspace(max(wsb, 16), 1)
+    return rows.data_ptr() if M else ws.data_ptr(), torch.empty(out_shape, dtype=torch.int64, device=rows.device), ws.data_ptr(), wsb
+
+
 def pair_hist(rows, nbits, weights=None, lanes16=False):
     """Weighted histogram of the pairwise distances of packed rows (tn_pair_hist): rows (M, ld) int64 / uint64 device tensor whose
     first ceil(nbits / 64) words (lanes16: ceil(nbits / 4)) hold a row of nbits bits (lanes16: nbits 16-bit lanes), layout of
     tnac4o_amd/overlap.py; weights None (all 1) or (M,) uint32 values in an int32 / uint32 device tensor.  Returns the (nbits + 1, 2)
     int64 device tensor of the limbs (lo, hi) of hist[d] = sum_{a<b} w_a w_b [dist(a, b) = d], exact integers (read them as unsigned)."""
-    if not rows.is_cuda:
-        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % rows.device)
-    if rows.dim() != 2 or rows.element_size() != 8 or rows.is_floating_point() or rows.stride(1) != 1 and rows.shape[1] > 1:
-        raise TypeError('rows: a 2-d tensor of 64-bit integer words with unit stride along a row')
-    M, ld = int(rows.shape[0]), int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    M, ld = _packed_rows(rows)
     nbits = int(nbits)
     nwords = -(-nbits // (4 if lanes16 else 64))
     if rows.shape[1] < nwords:
         raise ValueError('rows hold %d words, %d bits take %d' % (rows.shape[1], nbits, nwords))
-    if weights is not None:
-        if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous() or weights.numel() != M:
-            raise TypeError('weights: a contiguous device tensor of M 32-bit integers')
-    L = lib()
-    wsb = int(L.tn_pair_hist_ws_bytes(M, nbits, int(bool(lanes16))))        # (not cached: it follows TN_PAIR_HIST_WGS)
-    ws = workspace(max(wsb, 16), 1)
-    out = torch.empty((max(nbits, 0) + 1, 2), dtype=torch.int64, device=rows.device)
-    check(L.tn_pair_hist(rows.data_ptr() if M else ws.data_ptr(), M, nbits, max(ld, nwords), weights.data_ptr() if weights is not None else None,
-                         int(bool(lanes16)), out.data_ptr(), ws.data_ptr(), wsb, _stream()))
+    d_w = _row_weights(weights, M)
+    l16 = int(bool(lanes16))
+    p_rows, out, ws, wsb = _stat_buffers('tn_pair_hist_ws_bytes', rows, M, (max(nbits, 0) + 1, 2), nbits, l16)
+    check(lib().tn_pair_hist(p_rows, M, nbits, max(ld, nwords), d_w, l16, out.data_ptr(), ws, wsb, _stream()))
     return out
 
 
@@ -1038,29 +1063,16 @@ def pair_moments(rows, G, wpg, weights=None, wmax=None, lanes16=False):
     (2^32 - 1) // dmax with dmax = (4 if lanes16 else 64) * wpg).  Returns the (G + 1, G + 1, 2) int64 device tensor of the limbs
     (lo, hi) of out[i][j] = sum_{a<b} w_a w_b d_i d_j, d_g the distance within group g and d_G = 1: exact integers (read them as
     unsigned)."""
-    if not rows.is_cuda:
-        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % rows.device)
-    if rows.dim() != 2 or rows.element_size() != 8 or rows.is_floating_point() or rows.stride(1) != 1 and rows.shape[1] > 1:
-        raise TypeError('rows: a 2-d tensor of 64-bit integer words with unit stride along a row')
-    M, ld = int(rows.shape[0]), int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    M, ld = _packed_rows(rows)
     G, wpg = int(G), int(wpg)
     nwords = max(G, 0) * max(wpg, 0)
     if rows.shape[1] < nwords:
         raise ValueError('rows hold %d words, %d groups of %d words take %d' % (rows.shape[1], G, wpg, nwords))
-    if weights is not None:
-        if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous() or weights.numel() != M:
-            raise TypeError('weights: a contiguous device tensor of M 32-bit integers')
-    if wmax is None:
-        wmax = (2 ** 32 - 1) // ((4 if lanes16 else 64) * max(wpg, 1))
-    wmax = int(wmax)
-    if not 0 <= wmax < 2 ** 32:
-        raise ValueError('wmax must fit 32 bits')
-    L = lib()
-    wsb = int(L.tn_pair_moments_ws_bytes(M, G, wpg, int(bool(lanes16))))    # (not cached: it follows TN_PAIR_MOMENTS_WGS)
-    ws = workspace(max(wsb, 16), 1)
-    out = torch.empty((max(G, 0) + 1, max(G, 0) + 1, 2), dtype=torch.int64, device=rows.device)
-    check(L.tn_pair_moments(rows.data_ptr() if M else ws.data_ptr(), M, G, wpg, max(ld, nwords), weights.data_ptr() if weights is not None else None,
-                            wmax, int(bool(lanes16)), out.data_ptr(), ws.data_ptr(), wsb, _stream()))
+    d_w = _row_weights(weights, M)
+    wmax = _wmax(wmax, (2 ** 32 - 1) // ((4 if lanes16 else 64) * max(wpg, 1)))
+    l16 = int(bool(lanes16))
+    p_rows, out, ws, wsb = _stat_buffers('tn_pair_moments_ws_bytes', rows, M, (max(G, 0) + 1, max(G, 0) + 1, 2), G, wpg, l16)
+    check(lib().tn_pair_moments(p_rows, M, G, wpg, max(ld, nwords), d_w, wmax, l16, out.data_ptr(), ws, wsb, _stream()))
     return out
 
 
@@ -1071,28 +1083,14 @@ def spin_moments(rows, nbits, weights=None, wmax=None):
     bit-planes of the weights up to the bit length of wmax are processed.  Returns the (nbits + 2, nbits + 2) int64 device tensor
     out[i][j] = sum_a w_a [x_a,i != x_a,j] with the constant pseudo-bits x_a,nbits = 0 and x_a,nbits+1 = 1: exact integers (read them
     as unsigned)."""
-    if not rows.is_cuda:
-        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % rows.device)
-    if rows.dim() != 2 or rows.element_size() != 8 or rows.is_floating_point() or rows.stride(1) != 1 and rows.shape[1] > 1:
-        raise TypeError('rows: a 2-d tensor of 64-bit integer words with unit stride along a row')
-    M, ld = int(rows.shape[0]), int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    M, ld = _packed_rows(rows)
     nbits = int(nbits)
     nwords = -(-max(nbits, 0) // 64)
     if rows.shape[1] < nwords:
         raise ValueError('rows hold %d words, %d bits take %d' % (rows.shape[1], nbits, nwords))
-    if weights is not None:
-        if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous() or weights.numel() != M:
-            raise TypeError('weights: a contiguous device tensor of M 32-bit integers')
-    if wmax is None:
-        wmax = 2 ** 32 - 1 if weights is not None else 1
-    wmax = int(wmax)
-    if not 0 <= wmax < 2 ** 32:
-        raise ValueError('wmax must fit 32 bits')
-    L = lib()
-    wsb = int(L.tn_spin_moments_ws_bytes(M, nbits, wmax))                   # (not cached: it follows TN_SPIN_MOMENTS_WGS)
-    ws = workspace(max(wsb, 16), 1)
+    d_w = _row_weights(weights, M)
+    wmax = _wmax(wmax, 2 ** 32 - 1 if weights is not None else 1)
     n2 = max(nbits, 0) + 2
-    out = torch.empty((n2, n2), dtype=torch.int64, device=rows.device)
-    check(L.tn_spin_moments(rows.data_ptr() if M else ws.data_ptr(), M, nbits, max(ld, nwords), weights.data_ptr() if weights is not None else None,
-                            wmax, out.data_ptr(), n2, ws.data_ptr(), wsb, _stream()))
+    p_rows, out, ws, wsb = _stat_buffers('tn_spin_moments_ws_bytes', rows, M, (n2, n2), nbits, wmax)
+    check(lib().tn_spin_moments(p_rows, M, nbits, max(ld, nwords), d_w, wmax, out.data_ptr(), n2, ws, wsb, _stream()))
     return out

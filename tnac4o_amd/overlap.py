@@ -5,8 +5,8 @@ over the configurations (tnac4o.calculate_sample_correlations).
 Plain numpy, importable without a GPU; the only device work is the pair histogram tn_pair_hist (ops.pair_hist), which the driver
 overlap_distribution calls once, the pair moments tn_pair_moments (ops.pair_moments), which overlap_correlations calls once per axis,
 and the spin moments tn_spin_moments (ops.spin_moments), which sample_correlations calls once.  Row layouts of the library: a row of
-n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at
-position i % 64; a row of n 16-bit lanes is ceil(n / 4) words, lane i in word i // 4 at bits 16 (i % 4) .. 16 (i % 4) + 15."""
+n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at position i % 64; a row of n 16-bit lanes is ceil(n / 4) words, lane i
+in word i // 4 at bits 16 (i % 4) .. 16 (i % 4) + 15."""
 import numpy as np
 
 MAX_NBITS = 9183                 # largest row tn_pair_hist takes: 16 bytes per bin and the staging in 160 KiB of LDS (include/tnpeps.h)
@@ -55,11 +55,15 @@ def _ising(solver, what):
         raise ValueError("%s is defined for mode 'Ising' only" % what)
 
 
+def active_spins(solver):
+    """The spins the cells of solver.ind0 list, sorted: int64."""
+    return np.sort(np.concatenate([np.asarray(a, dtype=np.int64) for row in solver.ind0 for a in row] + [np.zeros(0, dtype=np.int64)]))
+
+
 def spin_bits(solver):
     """binary_states() of solver.states restricted to the active spins, in model order: (M, solver.active) of 0 / 1.  Ising only."""
     _ising(solver, 'spin_bits')
-    act = np.sort(np.concatenate([np.asarray(a, dtype=np.int64) for row in solver.ind0 for a in row] + [np.zeros(0, dtype=np.int64)]))
-    return solver.binary_states()[:, act].astype(np.uint8)
+    return solver.binary_states()[:, active_spins(solver)].astype(np.uint8)
 
 
 def link_bits(solver):
@@ -121,6 +125,19 @@ def quantise(W, wmax=WMAX):
         _, wq, scale = best
     wq = wq.astype(np.uint32)
     return wq, wq > 0, float(scale)
+
+
+def prepare(rows, w, wmax=WMAX):
+    """(urows, wq, scale, D0): condense, then quantise with wmax; only the distinct rows that keep a weight wq > 0, contiguous."""
+    urows, W, D0 = condense(rows, w)
+    wq, keep, scale = quantise(W, wmax)
+    return np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep]), scale, D0
+
+
+def upload(urows, wq):
+    """(d_rows, d_w) on the device; d_w = None when every weight is 1."""
+    import torch
+    return torch.as_tensor(urows.view(np.int64)).cuda(), None if np.all(wq == 1) else torch.as_tensor(wq.view(np.int32)).cuda()
 
 
 def limbs_to_int(hist_limbs):
@@ -201,12 +218,16 @@ def check_arguments(solver, kind, weights):
     return kind, w
 
 
+def cell_states(solver):
+    """solver.states with the cell states read as unsigned: the solver keeps 256 states of a cell in int8."""
+    st = np.asarray(solver.states)
+    return st.view('u%d' % st.dtype.itemsize) if st.dtype.kind == 'i' and st.dtype.itemsize < 8 else st
+
+
 def rows_of(solver, kind):
     """(packed rows (M, nwords) uint64, n, lanes16) of solver.states for a kind."""
     if kind == 'cell':
-        st = np.asarray(solver.states)
-        if st.dtype.kind == 'i' and st.dtype.itemsize < 8:           # the solver keeps 256 states of a cell in int8: read them as unsigned
-            st = st.view('u%d' % st.dtype.itemsize)
+        st = cell_states(solver)
         return pack_lanes16(st), int(st.shape[1]), True
     bits = spin_bits(solver) if kind == 'spin' else link_bits(solver)
     return pack_bits(bits), int(bits.shape[1]), False
@@ -221,15 +242,10 @@ def overlap_distribution(solver, kind=None, weights='uniform'):
     if n > MAX_NBITS:
         raise NotImplementedError("kind '%s' compares %d %s per state; tn_pair_hist takes at most %d (its histogram must fit the 160 KiB of "
                                   'LDS); there is no host fallback' % (kind, n, 'cells' if lanes16 else 'bits', MAX_NBITS))
-    import torch
     from . import ops
-    M = rows.shape[0]
-    urows, W, D0 = condense(rows, w)
-    wq, keep, scale = quantise(W)
-    urows, wq = np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep])
+    urows, wq, scale, D0 = prepare(rows, w)
     if urows.shape[0] >= 2:
-        d_rows = torch.as_tensor(urows.view(np.int64)).cuda()
-        d_w = None if np.all(wq == 1) else torch.as_tensor(wq.view(np.int32)).cuda()
+        d_rows, d_w = upload(urows, wq)
         limbs = ops.pair_hist(d_rows, n, d_w, lanes16).cpu().numpy()
     else:                                            # one distinct row: every pair sits in D0
         limbs = np.zeros((n + 1, 2), dtype=np.int64)
@@ -241,7 +257,7 @@ def overlap_distribution(solver, kind=None, weights='uniform'):
     if kind == 'spin':
         solver.overlap_moments['chi_sg'] = n * solver.overlap_moments['q2']
     solver.overlap_ess = effective_sample_size(w)
-    solver.overlap_pairs = M * (M - 1) // 2
+    solver.overlap_pairs = rows.shape[0] * (rows.shape[0] - 1) // 2
     return P
 
 
@@ -265,10 +281,8 @@ def line_groups(solver, axis, kind):
         group = line.astype(np.int64)
     else:
         _ising(solver, "kind 'spin'")
-        spins = np.concatenate([np.asarray(a, dtype=np.int64) for row in solver.ind0 for a in row] + [np.zeros(0, dtype=np.int64)])
-        cells = np.concatenate([np.full(len(a), ny * Nx + nx, dtype=np.int64) for ny, row in enumerate(solver.ind0) for nx, a in enumerate(row)]
-                               + [np.zeros(0, dtype=np.int64)])
-        group = line[cells[np.argsort(spins, kind='stable')]].astype(np.int64)                   # spin_bits sorts the active spins
+        cell = {int(i): ny * Nx + nx for ny, row in enumerate(solver.ind0) for nx, a in enumerate(row) for i in a}
+        group = line[[cell[int(i)] for i in active_spins(solver)]].astype(np.int64)              # in the order of spin_bits
     return group, np.bincount(group, minlength=Nx if axis == 'x' else Ny).astype(np.int64)
 
 
@@ -355,12 +369,7 @@ def correlation_length(QQ, N):
 
 def _line_source(solver, kind):
     """(what is compared (M, n), lanes16)"""
-    if kind == 'cell':
-        st = np.asarray(solver.states)
-        if st.dtype.kind == 'i' and st.dtype.itemsize < 8:           # as rows_of: int8 cell states are read as unsigned
-            st = st.view('u%d' % st.dtype.itemsize)
-        return st.astype(np.int64), True
-    return spin_bits(solver), False
+    return (cell_states(solver).astype(np.int64), True) if kind == 'cell' else (spin_bits(solver), False)
 
 
 def overlap_correlations(solver, axis='both', kind=None, weights='uniform'):
@@ -387,7 +396,6 @@ def overlap_correlations(solver, axis='both', kind=None, weights='uniform'):
         if int(sizes.sum()) < 1:
             raise ValueError("kind '%s': the model has nothing to compare" % kind)
         plan[ax] = (group, sizes, G, wpg)
-    import torch
     from . import ops
     X, _ = _line_source(solver, kind)
     C, mean, chi, xi, xil, nsz = {}, {}, {}, {}, {}, {}
@@ -395,12 +403,9 @@ def overlap_correlations(solver, axis='both', kind=None, weights='uniform'):
         group, sizes, G, wpg = plan[ax]
         rows, wpg = pack_groups(X, group, G, lanes16)
         wmax = WMAX // (per * wpg)
-        urows, W, D0 = condense(rows, w)
-        wq, keep, scale = quantise(W, wmax)
-        urows, wq = np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep])
+        urows, wq, scale, D0 = prepare(rows, w, wmax)
         if urows.shape[0] >= 2:
-            d_rows = torch.as_tensor(urows.view(np.int64)).cuda()
-            d_w = None if np.all(wq == 1) else torch.as_tensor(wq.view(np.int32)).cuda()
+            d_rows, d_w = upload(urows, wq)
             limbs = ops.pair_moments(d_rows, G, wpg, d_w, wmax, lanes16).cpu().numpy()
         else:                                        # one distinct row: every pair sits in D0
             limbs = np.zeros((G + 1, G + 1, 2), dtype=np.int64)
@@ -511,21 +516,15 @@ def sample_correlations(solver, weights='uniform'):
     if n > MAX_SPIN_BITS:
         raise NotImplementedError('the model has %d active spins; tn_spin_moments takes at most %d; there is no host fallback' % (n, MAX_SPIN_BITS))
     gx, gy = line_groups(solver, 'x', 'spin')[0], line_groups(solver, 'y', 'spin')[0]
-    urows, W, _ = condense(pack_bits(bits), w)
-    wq, keep, scale = quantise(W, WMAX)
-    urows, wq = np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep])
+    urows, wq, scale, _ = prepare(pack_bits(bits), w)
     S2 = float(np.sum(w * w)) * scale * scale
-    Wt = int(wq.astype(np.uint64).sum(dtype=object)) if wq.size else 0
-    pair_weight(Wt, S2, scale)                                         # every refusal comes before any device work
-    import torch
+    pair_weight(int(wq.astype(np.uint64).sum(dtype=object)) if wq.size else 0, S2, scale)   # every refusal comes before any device work
     from . import ops
-    d_rows = torch.as_tensor(urows.view(np.int64)).cuda()
-    d_w = None if np.all(wq == 1) else torch.as_tensor(wq.view(np.int32)).cuda()
+    d_rows, d_w = upload(urows, wq)
     out = ops.spin_moments(d_rows, n, d_w, int(wq.max())).cpu().numpy()
     m, C, QQ = spin_estimators(out, S2, scale)
-    act = np.sort(np.concatenate([np.asarray(a, dtype=np.int64) for row in solver.ind0 for a in row] + [np.zeros(0, dtype=np.int64)]))
     chi = chi_sg_2d(QQ, gx, gy, int(solver.Nx_model), int(solver.Ny_model))
-    solver.sample_spins = act
+    solver.sample_spins = active_spins(solver)
     solver.sample_magnetization = m
     solver.sample_correlations = C
     solver.sample_overlap_correlations = QQ
