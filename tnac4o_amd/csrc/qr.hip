@@ -771,106 +771,58 @@ static int64_t qr_layout(int64_t m, int64_t n, int nb, char* base, QrWs* w) {
 }
 
 int64_t qr_ws_bytes(int64_t m, int64_t n, int nb) { return qr_layout(m, n, nb, nullptr, nullptr); }
-
-// rank_tol > 0 enables the early exit: every second panel the largest column norm of the not-yet-factored trailing block
-// is compared with the largest column norm of the input; once it is below rank_tol times that, the remaining rows of R
-// would be negligible on the scale of the leading singular value and the factorisation stops with k_eff columns
-// (A = Q[:, :k_eff] R[:k_eff, :] to rank_tol * max column norm).  Used by the truncating canonisation passes, whose centre
-// matrix is SVD-truncated at eps * S0 right afterwards (the Jacobi SVD deflates rows below 2^-56 anyway); it needs one
-// 16-byte read-back per check.  *keff_host receives the number of columns/rows produced.
-// ---- two-level blocked factorisation (nb = 32 inside outer blocks of `nbo` columns) ---------------------------------------
-// Single-level blocking applies every 32-wide reflector to the whole trailing matrix and again to Q: three passes over up to
-// 134 MB per panel at K = 32, i.e. HBM-bound work that fills the device (12.9 GB for one 16384 x 1024 call against 0.28 GB
-// compulsory) and, with several chains on the GPU, serialises them.  Here the panels of an outer block only update the
-// columns of that block; the columns to its right (and, afterwards, Q) see the block once, through the merged reflector
-//      H_1 ... H_q = I - Y_blk T_blk Y_blk^T,   T_blk = [[T_1, -T_1 (Y_1^T Y_2) T_2, ...], [0, T_2, ...], ...]   (dlarft by blocks)
-// built from the panels' own (Y_p, T_p) and one Gram matrix G = Y_blk^T Y_blk: rank-nbo GEMMs (K = 128 or 256) instead of
-// rank-32 ones, 4-8x fewer bytes.  Used for the plain factorisation only (rank_tol = 0): the rank-revealing early exit of the
-// truncating passes checks the trailing block after every second panel, which needs it up to date.
-static int qr_two_level(hipStream_t st, Mat Am, int64_t m, int64_t n, int64_t k, Mat Ym, QrWs& w, int nbo, int64_t rs, int64_t cs,
-                        int64_t yrs, int64_t ycs, int64_t wrs, int64_t wcs, double* Q, int64_t qrs, int64_t qcs, double* R, int64_t rrs,
-                        int64_t rcs, int* fused_base) {
-    const int nb = 32;
-    int rc;
-    const bool ru_on = env_flag_on("TN_QR_RANK_UPDATE");          // (as in qr_factor_impl)
-    const int nblk = (int)cdiv(k, nbo);
-    for (int bi = 0; bi < nblk; ++bi) {
-        const int64_t J0 = (int64_t)bi * nbo;
-        const int bw = (int)((k - J0 < nbo) ? k - J0 : nbo);
-        const int64_t Jend = J0 + bw, mb = m - J0;
-        Mat Yb = sub(Ym, J0, J0);
-        // rows of the block above each panel's own top block must read as zero in the merged reflector
-        if ((rc = fill_mat(st, Yb.p, yrs, ycs, bw, bw, 0.0))) return rc;
-        double* Tb = w.Tblk + (int64_t)bi * QR_NBO_MAX * QR_NBO_MAX;            // bw x bw, row-major, pitch bw
-        if ((rc = fill_mat(st, Tb, bw, 1, bw, bw, 0.0))) return rc;
-        const int npan = (int)cdiv(bw, nb);
-        for (int q = 0; q < npan; ++q) {
-            const int64_t j0 = J0 + (int64_t)q * nb;
-            const int b = (int)((Jend - j0 < nb) ? Jend - j0 : nb);
-            const int64_t mp = m - j0, nin = Jend - j0;                         // the panel's update stays inside the block
-            const int p = (int)(j0 / nb);
-            Mat Ap = sub(Am, j0, j0), Yp = sub(Ym, j0, j0);
-            double* Tp = w.T + (int64_t)p * nb * nb;
-            Mat Wp = mat(w.W, wrs, wcs);
-            // orthonormalisation + Householder reconstruction + the tall products in one chain of launches (cholqr.hip)
-            if ((rc = cholqr_panel(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.panel_ws, w.panel_bytes, (uint64_t)p + 1, 1, Tp, Wp.p, wrs, wcs,
-                                   nullptr, fused_base, w.cq_state)))
-                return rc;
-            Mat Xm = mat(w.X, nin, 1);
-            if ((rc = gemm(st, b, nin, mp, 1.0, tr(Yp), Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            if ((rc = ru_on ? rank_update(st, mp, nin, b, Wp, Xm, Ap) : gemm(st, mp, nin, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
-            // T_blk: diagonal block = T_p (its pitch is b); column block from the recurrence once the Gram matrix exists (below)
-            if ((rc = copy_mat(st, Tp, b, 1, Tb + (int64_t)(j0 - J0) * bw + (j0 - J0), bw, 1, b, b))) return rc;
-        }
-        // G = Y_blk^T Y_blk, then T_blk[0:c0, c0:c0+b] = -T_blk[0:c0, 0:c0] (G[0:c0, c0:c0+b] T_q)
-        Mat Gm = mat(w.G, bw, 1);
-        if (npan > 1) {
-            if ((rc = gemm(st, bw, bw, mb, 1.0, tr(Yb), Yb, 0.0, Gm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            for (int q = 1; q < npan; ++q) {
-                const int64_t c0 = (int64_t)q * nb;
-                const int b = (int)((bw - c0 < nb) ? bw - c0 : nb);
-                Mat Tq = mat(Tb + c0 * bw + c0, bw, 1), tmp = mat(w.tmpT, b, 1);
-                if ((rc = gemm(st, c0, b, b, 1.0, sub(Gm, 0, c0), Tq, 0.0, tmp))) return rc;
-                if ((rc = gemm(st, c0, b, c0, -1.0, mat(Tb, bw, 1), tmp, 0.0, mat(Tb + c0, bw, 1)))) return rc;
-            }
-        }
-        // outer update of everything to the right of the block:  A_r -= Y_blk (T_blk^T (Y_blk^T A_r))
-        const int64_t nr = n - Jend;
-        if (nr > 0) {
-            Mat Ar = sub(Am, J0, Jend), Z = mat(w.Zo, nr, 1), Z2 = mat(w.Zo2, nr, 1);
-            if ((rc = gemm(st, bw, nr, mb, 1.0, tr(Yb), Ar, 0.0, Z, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            if ((rc = gemm(st, bw, nr, bw, 1.0, tr(mat(Tb, bw, 1)), Z, 0.0, Z2))) return rc;
-            if ((rc = gemm(st, mb, nr, bw, -1.0, Yb, Z2, 1.0, Ar))) return rc;
-        }
-    }
-    // --- triangularise the diagonal blocks, assemble R (as in the single-level path)
-    const int P = (int)cdiv(k, nb);
-    TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL((diag_qr_kernel<32>), dim3(P), dim3(256), 0, st, Am.p, rs, cs, nb, k, w.Z, w.Tri, (int*)w.cq_state));
-    TN_CHECK_LAUNCH("diag_qr_kernel");
-    if (w.cq_state) cholqr_end_ok(st);
-    // --- Q = H_blk1 ... H_blkB [Z; 0]:  Q[J0:, J0:] -= Y_blk (T_blk (Y_blk^T Q[J0:, J0:]))
-    const int qcolfast = (qcs == 1) ? 1 : 0;
-    {
-        const unsigned nR = (unsigned)cdiv(k * n, 256), nQ = (unsigned)cdiv(m * k, 256);
-        TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(assemble_R_init_Q_kernel, dim3(nR + nQ), dim3(256), 0, st, Am.p, rs, cs, nb, k, n, w.Z, w.Tri, R,
-                           rrs, rcs, nR, Q, qrs, qcs, m, qcolfast, (const double*)nullptr, (const double*)nullptr, (int64_t)0, (int64_t)0, (int64_t)0, 0));
-        TN_CHECK_LAUNCH("assemble_R_init_Q_kernel");
-    }
-    Mat Qm = mat(Q, qrs, qcs);
-    for (int bi = nblk - 1; bi >= 0; --bi) {
-        const int64_t J0 = (int64_t)bi * nbo;
-        const int bw = (int)((k - J0 < nbo) ? k - J0 : nbo);
-        const int64_t mb = m - J0, nq = k - J0;
-        Mat Yb = sub(Ym, J0, J0), Qb = sub(Qm, J0, J0), Z = mat(w.Zo, nq, 1), Z2 = mat(w.Zo2, nq, 1);
-        double* Tb = w.Tblk + (int64_t)bi * QR_NBO_MAX * QR_NBO_MAX;
-        // (the last block meets [Z; 0]: only its top bw rows are non-zero, the product over the rest adds zeros)
-        if ((rc = gemm(st, bw, nq, bi == nblk - 1 ? (int64_t)bw : mb, 1.0, tr(Yb), Qb, 0.0, Z, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-        if ((rc = gemm(st, bw, nq, bw, 1.0, mat(Tb, bw, 1), Z, 0.0, Z2))) return rc;
-        if ((rc = gemm(st, mb, nq, bw, -1.0, Yb, Z2, 1.0, Qb))) return rc;
-    }
+// ------------------------------------------------------------------------------------------ host driver: a call record, stages, qr_factor_impl
+// One call of qr_factor: filled once, read by every stage below.
+struct QrCall {
+    hipStream_t st;
+    double* A; int64_t rs, cs, m, n; double* Q; int64_t qrs, qcs; double* R; int64_t rrs, rcs;
+    int nb; void* ws; int64_t ws_bytes; double rank_tol;
+    int64_t* keff_host; double* dropped2_host; int frob_exit; int64_t* pivot_perm_host; double* nf_out2; int* nf_done; bool* input_intact;
+};
+// What the blocked paths derive from the call, once (the single-launch exits leave before it is filled).
+struct QrState {
+    QrWs w;
+    bool pivot, reveal, rowmajor, ru_on, wform;      // pivot: panel pivoting; reveal: the rank-revealing check of every second panel
+    int64_t yrs, ycs, wrs, wcs;          // strides of Y (and of the m x k array of W) / of the one-panel W of the 64-wide and two-level paths
+    Mat Am, Ym, Wqm;
+    int fbase = 0;                       // arrivals booked by the single-launch panel steps of this call (cholqr.hip)
+    double scale2 = -1.0;                // measure of the input the exit tests compare with (lazily read back)
+};
+// The operands of one panel step
+struct QrPanel {
+    int p, b; int64_t j0, mp;            // number of the panel in the whole factorisation, its width; first row and column, rows from there on (m - j0)
+    Mat Ap, Yp, Wp, Wqp;                 // A[j0:, j0:], Y[j0:, j0:], the W = Y T^T of the trailing update, the panel's place in the m x k array
+    double* Tp;
+};
+static QrPanel panel_at(const QrCall& c, const QrState& s, int p, int64_t kend) {
+    QrPanel pn;
+    pn.p = p, pn.j0 = (int64_t)p * c.nb, pn.mp = c.m - pn.j0;
+    pn.b = (int)((kend - pn.j0 < c.nb) ? kend - pn.j0 : c.nb);
+    pn.Ap = sub(s.Am, pn.j0, pn.j0), pn.Yp = sub(s.Ym, pn.j0, pn.j0), pn.Wqp = sub(s.Wqm, pn.j0, pn.j0);
+    // fused: W_p = Y_p T_p^T of EVERY panel is kept (in the m x k array that holds Y T for nb = 64): besides the trailing update it
+    // serves the Q accumulation, H_p Q = Q - Y_p (W_p^T Q), so Y T is never formed (a third of the panel step's output)
+    pn.Wp = s.wform ? pn.Wqp : mat(s.w.W, s.wrs, s.wcs);
+    pn.Tp = s.w.T + (int64_t)p * c.nb * c.nb;
+    return pn;
+}
+// one launch of 256-thread workgroups on the call's stream, booked under PROF_QR_AUX; a launch error ends the stage that made it
+#define QR_LAUNCH(c, kernel, grid, ...) \
+    do { TN_PROF_LAUNCH((c).st, PROF_QR_AUX, hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (c).st, __VA_ARGS__)); TN_CHECK_LAUNCH(#kernel); } while (0)
+// ---- the ending: triangularise the diagonal blocks, assemble R, start Q (in front of the other stages: the file's kernels are emitted in order of first launch)
+static int triangularise_diag(const QrCall& c, QrState& s, int64_t k, int P) {      // (32-wide panels; the 64-wide path launches its own form)
+    QR_LAUNCH(c, (diag_qr_kernel<32>), dim3(P), c.A, c.rs, c.cs, c.nb, k, s.w.Z, s.w.Tri, (int*)s.w.cq_state);
+    if (s.w.cq_state) cholqr_end_ok(c.st);
     return 0;
 }
-
+// The last panel's reflector applied by the launch that writes [Z; 0]:  Q[jf:, jf:] = [Z; 0] - second (first_top^T Z),  b columns (0: none)
+struct QrFold { const double *first, *second; int64_t rs, cs, jf; int b; };
+static int assemble_R_init_Q(const QrCall& c, QrState& s, int64_t k, const QrFold& f) {
+    const int qcolfast = (c.qcs == 1) ? 1 : 0;
+    const unsigned nR = (unsigned)cdiv(k * c.n, 256), nQ = (unsigned)cdiv(c.m * k, 256);
+    QR_LAUNCH(c, assemble_R_init_Q_kernel, dim3(nR + nQ), c.A, c.rs, c.cs, c.nb, k, c.n, s.w.Z, s.w.Tri, c.R, c.rrs, c.rcs, nR, c.Q, c.qrs, c.qcs, c.m, qcolfast,
+              f.first, f.second, f.rs, f.cs, f.jf, f.b);
+    return 0;
+}
 // Selection of the b largest residuals among positions 0 .. ntr-1 by successive swaps (step t: the first maximum of positions
 // t .. ntr-1 goes to position t), through a tournament tree over the positions instead of b linear scans (the scans cost 30 us of
 // host time per panel with the device idle): leaf i = position i, a node keeps the position of the larger value, the left one on
@@ -1215,16 +1167,407 @@ struct QrTrace {
 };
 QrTrace g_qr_trace;
 }  // namespace
-
-static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
-                          int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-                          int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2,
-                          int* nf_done, bool* input_intact);
-static int qr_factor_traced(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
-              int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-              int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done,
-              bool* input_intact);
-
+// ---- the single-launch exits: all k columns, the input untouched ----------------------------------------------------------------------
+static int single_launch_done(const QrCall& c, int64_t k, bool* done) {
+    if (c.keff_host) *c.keff_host = k;
+    if (c.input_intact) *c.input_intact = true;
+    *done = true;
+    return 0;
+}
+// tiny matrices: the whole factorisation in one workgroup (TN_QR_TINY=0: the blocked path; read per call: the tests switch it)
+static int tiny_exit(const QrCall& c, int64_t k, bool* done) {
+    const bool tiny_on = env_flag_on("TN_QR_TINY");
+    if (!(tiny_on && c.nb == 32 && c.pivot_perm_host == nullptr && c.m * c.n <= 4096 && k <= 32)) return 0;
+    QR_LAUNCH(c, tiny_qr_kernel, dim3(1), (const double*)c.A, c.rs, c.cs, (int)c.m, (int)c.n, c.Q, c.qrs, c.qcs, c.R, c.rrs, c.rcs);
+    return single_launch_done(c, k, done);
+}
+// up to 64 columns (no pivoting; the rank-revealing exit only exists from three panels on): the whole factorisation in ONE launch,
+// explicit-Q iterated Cholesky-QR (smallqr.hip); it leaves the input untouched
+static int smallqr_exit(const QrCall& c, QrWs& w, int64_t k, bool* done) {
+    if (!(c.nb == 32 && c.pivot_perm_host == nullptr && c.Q != nullptr && smallqr_fits(c.m, c.n))) return 0;
+    const int rc = smallqr_factor(c.st, c.A, c.rs, c.cs, c.m, c.n, c.Q, c.qrs, c.qcs, c.R, c.rrs, c.rcs, c.nf_out2, w.gemm_ws, w.gemm_ws_bytes);
+    if (rc) return rc == 1 ? 0 : rc;     // 1: shape / stream not taken, the blocked path follows
+    if (c.nf_done) *c.nf_done = c.nf_out2 ? 1 : 0;
+    return single_launch_done(c, k, done);
+}
+// ---- device-side panel pivoting (see pivot_select_kernel): the host runs one panel ahead of the verdicts it reads back -----------------
+struct PivDev {
+    PivState* pst = nullptr; int* pperm = nullptr;      // state block and permutation in the workspace
+    const int* active = nullptr;         // DEVICE: 0 once the exit test has fired, what the later launches of the call look at (null: not in use)
+    PivMail* ring = nullptr; unsigned seq0 = 0;          // the host thread's mailbox ring and the stamp before the first one of this call
+    int begin(const QrCall& c, QrWs& w, int P) {
+        pst = (PivState*)w.piv, pperm = (int*)(w.piv + 1024), active = &pst->h.active;
+        ring = (PivMail*)pinned_host(4 * sizeof(PivMail), PIN_SHARED);
+        if (!ring) { set_error("tn_qr: no page-locked memory for the pivoting verdicts"); return 1; }
+        for (int i = 0; i < 4; ++i) __atomic_store_n(&ring[i].word, 0ull, __ATOMIC_RELAXED);       // (the slot is shared with other read-backs of this thread: no stale word may look like a stamp)
+        thread_local unsigned piv_seq = 0;                        // stamps are unique per host thread (the ring is the thread's own; wrap-around after 2^32 panels is harmless: four entries)
+        seq0 = piv_seq, piv_seq += (unsigned)P + 1u;
+        QR_LAUNCH(c, pivot_init_kernel, dim3((unsigned)cdiv(std::max<int64_t>(c.n, 256), 256)), pst, pperm, (int)c.n);
+        return 0;
+    }
+    // residual norms, selection and column moves in front of panel pn
+    int select(const QrCall& c, QrWs& w, const QrPanel& pn) {
+        const int64_t ntr = c.n - pn.j0;
+        QR_LAUNCH(c, colnorm2_kernel, dim3((unsigned)ntr), pn.Ap.p, c.rs, c.cs, pn.mp, ntr, w.cn);
+        QR_LAUNCH(c, pivot_select_kernel, dim3((unsigned)cdiv(ntr, PIV_CPB)), (const double*)w.cn, (int)ntr, pn.b, (int)pn.j0, pn.p, c.rank_tol * c.rank_tol, pst,
+                  &ring[pn.p & 3], seq0 + (unsigned)pn.p + 1u);
+        QR_LAUNCH(c, swap_columns_dev_kernel, dim3((unsigned)cdiv(c.m, 64) + 1), c.A, c.rs, c.cs, c.m, (const PivState*)pst, pperm);
+        return 0;
+    }
+    // verdict of panel q (the selection launch in front of it): *stop = the exit test fired there, with *k_exit columns accepted
+    int verdict(const QrCall& c, int q, bool* stop, int64_t* k_exit) {
+        const PivMail* h = &ring[q & 3];
+        const unsigned want = seq0 + (unsigned)q + 1u;
+        unsigned long long wd = __atomic_load_n(&h->word, __ATOMIC_ACQUIRE);
+        for (long spins = 0; (unsigned)(wd >> 32) != want; ++spins) {
+            if ((spins & 0xfffff) == 0xfffff && hipStreamQuery(c.st) != hipErrorNotReady) {          // the stream has drained (or failed): look once more, then give up
+                wd = __atomic_load_n(&h->word, __ATOMIC_ACQUIRE);
+                if ((unsigned)(wd >> 32) == want) break;
+                set_error("tn_qr: the pivoting verdict of panel %d never arrived", q);
+                return 1;
+            }
+            wd = __atomic_load_n(&h->word, __ATOMIC_ACQUIRE);
+        }
+        *stop = ((wd >> 31) & 1ull) == 0ull;
+        if (*stop) *k_exit = (int64_t)(wd & 0x7fffffffull);
+        return 0;
+    }
+    // the last panel's own verdict (it may have stopped the factorisation in front of itself) unless an earlier one has stopped it, then
+    // the permutation and the dropped norm (with device-side pivoting only a verdict stops the factorisation)
+    int finish(const QrCall& c, QrWs& w, int P, bool* stop, int64_t* k_exit) {
+        int rc;
+        if (P >= 1 && !*stop && (rc = verdict(c, P - 1, stop, k_exit))) return rc;
+        // state block (1024 bytes, for the dropped norm) and permutation are neighbours in the workspace: one copy
+        int* hp = nullptr;
+        if ((rc = read_back_staged(c.st, (void**)&hp, w.piv, 1024 + (size_t)c.n * 4, PIN_QR, "permutation"))) return rc;
+        for (int64_t j = 0; j < c.n; ++j) c.pivot_perm_host[j] = hp[256 + j];
+        if (((const PivState*)hp)->h.stamp < 0) {
+            set_error("tn_qr: the device-side pivot selection of panel %d was not a valid set of columns (TN_PIVOT_DEVICE=0 selects on the host)", -((const PivState*)hp)->h.stamp - 1);
+            return 1;
+        }
+        if (*stop && c.dropped2_host) *c.dropped2_host = ((const PivState*)hp)->h.dropped2;
+        return 0;
+    }
+};
+// ---- host-side pivoting of one panel (TN_PIVOT_DEVICE=0, or more than PIV_MAXN columns): *stop with j0 columns accepted when what is
+// left is below the threshold, otherwise the b columns with the largest residuals are swapped to the front
+static int pivot_on_host(const QrCall& c, QrState& s, const QrPanel& pn, bool* stop, int64_t* k_exit) {
+    const int64_t ntr = c.n - pn.j0;
+    int rc;
+    QR_LAUNCH(c, colnorm2_kernel, dim3((unsigned)ntr), pn.Ap.p, c.rs, c.cs, pn.mp, ntr, s.w.cn);
+    double* hcn = nullptr;
+    if ((rc = read_back_staged(c.st, (void**)&hcn, s.w.cn, (size_t)ntr * 8, PIN_QR, "norms"))) return rc;
+    double fro2 = 0.0;
+    for (int64_t j = 0; j < ntr; ++j) fro2 += hcn[j];
+    if (pn.p == 0) s.scale2 = fro2;
+    if (pn.p > 0 && fro2 <= c.rank_tol * c.rank_tol * s.scale2) {     // what is left is below the threshold: stop before this panel
+        if (c.dropped2_host) *c.dropped2_host = fro2;
+        *stop = true, *k_exit = pn.j0;
+        return 0;
+    }
+    int pairs[64];
+    select_pivots(hcn, ntr, pn.b, pn.j0, c.pivot_perm_host, pairs);
+    SwapList sl = {};
+    compose_swaps(pairs, pn.b, sl);
+    if (sl.n > 0)
+        TN_PROF_LAUNCH(c.st, PROF_QR_AUX, hipLaunchKernelGGL(swap_columns_kernel, dim3((unsigned)cdiv(c.m, 256)), dim3(256), 0, c.st, c.A, c.rs, c.cs, c.m, sl));
+    TN_CHECK_LAUNCH("swap_columns_kernel");
+    return 0;
+}
+// ---- panel step, 32-wide: orthonormalisation + reconstruction + the tall products in one chain of launches (cholqr.hip); W goes to pn.Wp
+static int panel_fused(const QrCall& c, QrState& s, const QrPanel& pn, const int* active) {
+    return cholqr_panel(c.st, pn.Ap.p, c.rs, c.cs, pn.Yp.p, s.yrs, s.ycs, pn.mp, pn.b, s.w.panel_ws, s.w.panel_bytes, (uint64_t)pn.p + 1, 1, pn.Tp, pn.Wp.p,
+                        pn.Wp.rs, pn.Wp.cs, nullptr, &s.fbase, s.w.cq_state, active);
+}
+static void dbg_check_factors(const QrCall& c, QrState& s, const QrPanel& pn) {
+    dbg_check(c.st, pn.Tp, pn.b, 1, pn.b, pn.b, "T", pn.p, 9), dbg_check(c.st, s.w.Uinv, pn.b, 1, pn.b, pn.b, "Uinv", pn.p, 9);
+}
+// 64-wide: five rounds of Jacobi orthonormalisation through the Gram matrix, then the reconstruction by lu_reconstruct_kernel
+static int panel_jacobi64(const QrCall& c, QrState& s, const QrPanel& pn) {
+    hipStream_t st = c.st;
+    QrWs& w = s.w;
+    const Mat Yp = pn.Yp, Wp = pn.Wp, Wqp = pn.Wqp;
+    const int64_t yrs = s.yrs, ycs = s.ycs, mp = pn.mp;
+    int rc, b = pn.b, p = pn.p;
+    if ((rc = copy_mat(st, pn.Ap.p, c.rs, c.cs, Yp.p, yrs, ycs, mp, b))) return rc;
+    const int nchunk = gram_nchunk(mp);
+    for (int it = 0; it < 5; ++it) {
+        if ((rc = gram_partial(st, Yp.p, ycs, yrs, mp, b, b, nullptr, 1, nchunk, w.part))) return rc;
+        const int mode = (it < 4) ? 0 : 1;
+        // after the first round the columns are images of unit columns under an orthogonal J: a squared norm below
+        // 1e-26 there is rounding noise (possibly structured, e.g. all parallel), so the column is refilled
+        if ((rc = eig_small(st, w.part, nchunk, b, 1, mode, 12, it == 0 ? 0.0 : 1e-26, w.Js, mode == 0 ? w.dead : nullptr, nullptr, nullptr))) return rc;
+        dbg_check(st, w.Js, b, 1, b, b, "Js", p, it);
+        if ((rc = rows_times_small(st, Yp.p, yrs, ycs, mp, b, w.Js))) return rc;
+        dbg_check(st, Yp.p, yrs, ycs, mp < 64 ? mp : 64, b, "W", p, it);
+        if (mode == 0)
+            QR_LAUNCH(c, refill_dead_kernel, dim3((unsigned)cdiv(mp, 256)), Yp.p, yrs, ycs, mp, b, w.dead, (uint64_t)(0x9E3779B97F4A7C15ULL * (uint64_t)(p * 4 + it + 1)));
+    }
+    TN_PROF_LAUNCH(st, PROF_LU, hipLaunchKernelGGL((lu_reconstruct_kernel<64>), dim3(1), dim3(256), 0, st, Yp.p, yrs, ycs, b, w.Uinv, pn.Tp, w.UT, w.UTq,
+                       Wp.p, s.wrs, s.wcs, Wqp.p));
+    TN_CHECK_LAUNCH("lu_reconstruct_kernel");
+    dbg_check_factors(c, s, pn);
+    if (mp > b) {            // rows below the top block: Y <- Q1 Uinv,  W <- Q1 (Uinv T^T),  Wq <- Q1 (Uinv T)
+        dim3 grid((unsigned)cdiv(mp - b, 256));
+        prof_begin(st, PROF_ROWS_SMALL);
+        hipLaunchKernelGGL((rows_times_small3_kernel<64>), grid, dim3(256), 0, st, sub(Yp, b, 0).p, yrs, ycs, mp - b, b,
+                           w.Uinv, w.UT, w.UTq, sub(Wp, b, 0).p, s.wrs, s.wcs, sub(Wqp, b, 0).p);
+        TN_CHECK_LAUNCH("rows_times_small3_kernel");
+        prof_end(st, PROF_ROWS_SMALL, 6.0 * (mp - b) * b * b, 32.0 * (mp - b) * b);
+    }
+    return 0;
+}
+// ---- trailing update  A[j0:, j0:j0+nc] -= (Y T^T) (Y^T A[j0:, j0:j0+nc]) -----------------------------------------------------------------
+// The rank-32 updates of the panels (trailing matrix and Q) go through rank_update (rank_update.hip) instead of a K = 32 launch of gemm: the
+// same bits (TN_QR_RANK_UPDATE=0 restores gemm).  The 64-wide panels keep gemm.  active (DEVICE, may be null): the same two products,
+// skipped on the device once the exit test of the device-side pivoting has fired.
+static int trailing_update(const QrCall& c, QrState& s, const QrPanel& pn, int64_t nc, const int* active) {
+    QrWs& w = s.w;
+    const Mat Ap = pn.Ap, Wp = pn.Wp, Xm = mat(w.X, nc, 1), Yt = tr(pn.Yp);
+    int rc;
+    if (!active) {
+        if ((rc = gemm(c.st, pn.b, nc, pn.mp, 1.0, Yt, Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
+        return s.ru_on ? rank_update(c.st, pn.mp, nc, pn.b, Wp, Xm, Ap) : gemm(c.st, pn.mp, nc, pn.b, -1.0, Wp, Xm, 1.0, Ap);
+    }
+    GemmExtra gx_active;                 // (the same two products, skipped on the device once the exit test has fired)
+    gx_active.skip = active;
+    if ((rc = gemm_ex(c.st, pn.b, nc, pn.mp, 1.0, Yt.p, Yt.rs, Yt.cs, Ap.p, Ap.rs, Ap.cs, 0.0, Xm.p, Xm.rs, Xm.cs, 1, 0, 0, 0, w.gemm_ws, w.gemm_ws_bytes, &gx_active)))
+        return rc;
+    return s.ru_on ? rank_update(c.st, pn.mp, nc, pn.b, Wp, Xm, Ap, active)
+                   : gemm_ex(c.st, pn.mp, nc, pn.b, -1.0, Wp.p, Wp.rs, Wp.cs, Xm.p, Xm.rs, Xm.cs, 1.0, Ap.p, Ap.rs, Ap.cs, 1, 0, 0, 0, nullptr, 0, &gx_active);
+}
+// ---- the rank-revealing exit (rank_tol > 0, no pivoting, from three panels on) -----------------------------------------------------------
+// Every second panel the largest column norm of the not-yet-factored trailing block is compared with the largest column norm of the
+// input; once it is below rank_tol times that, the remaining rows of R would be negligible on the scale of the leading singular value
+// and the factorisation stops with k_eff columns (A = Q[:, :k_eff] R[:k_eff, :] to rank_tol * max column norm).  Used by the truncating
+// canonisation passes, whose centre matrix is SVD-truncated at eps * S0 right afterwards (the Jacobi SVD deflates rows below 2^-56
+// anyway); it needs one 16-byte read-back per check.  After panel pn: *stop with the columns up to the end of pn accepted.
+static int reveal_check(const QrCall& c, QrState& s, const QrPanel& pn, bool* stop, int64_t* k_exit) {
+    double* cn = s.w.cn;
+    const int64_t n = c.n, j1 = pn.j0 + pn.b, nt = n - j1;
+    int rc;
+    QR_LAUNCH(c, colnorm2_kernel, dim3((unsigned)nt), sub(s.Am, j1, j1).p, c.rs, c.cs, c.m - j1, nt, cn + n);
+    // one read-back: the trailing norms, and (first check only) the input norms stored in front of them
+    const size_t nread = (size_t)(s.scale2 < 0.0 ? n + nt : nt);
+    double* hcn = nullptr;
+    if ((rc = read_back_staged(c.st, (void**)&hcn, s.scale2 < 0.0 ? cn : cn + n, nread * 8, PIN_QR, "norms"))) return rc;
+    const double* tr2 = hcn;
+    // measure of "what is left" against the input: largest column norm (default) or, frob_exit, the Frobenius norm
+    if (s.scale2 < 0.0) {
+        s.scale2 = 0.0;
+        for (int64_t j = 0; j < n; ++j) s.scale2 = c.frob_exit ? s.scale2 + hcn[j] : std::max(s.scale2, hcn[j]);
+        tr2 = hcn + n;
+    }
+    double left = 0.0;
+    for (int64_t j = 0; j < nt; ++j) left = c.frob_exit ? left + tr2[j] : std::max(left, tr2[j]);
+    if (!(left <= c.rank_tol * c.rank_tol * s.scale2)) return 0;      // (a NaN never stops the factorisation)
+    double fro2 = 0.0;                                       // nothing left above the threshold: the squared Frobenius norm of the block that is dropped
+    for (int64_t j = 0; c.dropped2_host && j < nt; ++j) fro2 += tr2[j];
+    if (c.dropped2_host) *c.dropped2_host = fro2;
+    *stop = true, *k_exit = j1;
+    return 0;
+}
+// ---- Q accumulation through merged reflectors, last outer block (bwo columns) to first:  Q[J0:, J0:] -= Y_blk (T_blk (Y_blk^T Q[J0:, J0:])).  T_blk is applied
+// either as the matrix the two-level factorisation has built (w.Tblk) or, merged_T, by the block back substitution of
+// apply_merged_T_kernel from the panels' own T_p and the Gram matrix of the block, which is formed first.
+static int accumulate_Q_blocks(const QrCall& c, QrState& s, int64_t k, int bwo, bool merged_T) {
+    hipStream_t st = c.st;
+    QrWs& w = s.w;
+    const int nb = c.nb, nblk = (int)cdiv(k, bwo);
+    const Mat Qm = mat(c.Q, c.qrs, c.qcs);
+    int rc;
+    if (merged_T) QR_LAUNCH(c, zero_above_panels_kernel, dim3(16, (unsigned)nblk), w.Y, s.yrs, s.ycs, k, nb);
+    for (int bi = nblk - 1; bi >= 0; --bi) {
+        const int64_t J0 = (int64_t)bi * bwo;
+        const int bw = (int)((k - J0 < bwo) ? k - J0 : bwo);
+        const int64_t mb = c.m - J0, nq = k - J0;
+        const int npan = (int)cdiv(bw, nb);
+        Mat Yb = sub(s.Ym, J0, J0), Qb = sub(Qm, J0, J0), Z = mat(w.Zo, nq, 1), X = mat(w.Zo2, nq, 1), Gm = mat(w.G, bw, 1);
+        if (merged_T && npan > 1 && (rc = gemm(st, bw, bw, mb, 1.0, tr(Yb), Yb, 0.0, Gm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
+        // (the last block meets [Z; 0]: only its top bw rows are non-zero, the product over the rest adds zeros)
+        if ((rc = gemm(st, bw, nq, bi == nblk - 1 ? (int64_t)bw : mb, 1.0, tr(Yb), Qb, 0.0, Z, w.gemm_ws, w.gemm_ws_bytes))) return rc;
+        if (merged_T)
+            QR_LAUNCH(c, apply_merged_T_kernel, dim3((unsigned)cdiv(nq, 32)), (const double*)Z.p, nq, (const double*)Gm.p, bw, (const double*)(w.T + (J0 / nb) * nb * nb), npan, X.p);
+        else if ((rc = gemm(st, bw, nq, bw, 1.0, mat(w.Tblk + (int64_t)bi * QR_NBO_MAX * QR_NBO_MAX, bw, 1), Z, 0.0, X))) return rc;
+        if ((rc = gemm(st, mb, nq, bw, -1.0, Yb, X, 1.0, Qb))) return rc;
+    }
+    return 0;
+}
+// Panel by panel, last to first; the last one is skipped when the launch that wrote [Z; 0] has applied it (what the m x k array holds: see panel_at)
+static int accumulate_Q_panels(const QrCall& c, QrState& s, int64_t k, int P, int fold_b) {
+    const Mat Qm = mat(c.Q, c.qrs, c.qcs);
+    int rc;
+    for (int p = P - 1 - (fold_b > 0 ? 1 : 0); p >= 0; --p) {
+        const QrPanel pn = panel_at(c, s, p, k);
+        const int64_t nq = k - pn.j0;
+        const Mat Qp = sub(Qm, pn.j0, pn.j0), Xm = mat(s.w.X, nq, 1), Lp = s.wform ? pn.Yp : pn.Wqp;
+        // Y^T Q (the last panel meets [Z; 0]: only its top b rows are non-zero, the product over the rest adds zeros)
+        if ((rc = gemm(c.st, pn.b, nq, p == P - 1 ? (int64_t)pn.b : pn.mp, 1.0, tr(s.wform ? pn.Wqp : pn.Yp), Qp, 0.0, Xm, s.w.gemm_ws, s.w.gemm_ws_bytes))) return rc;
+        // Q -= (Y T) (Y^T Q) = Y (W^T Q)
+        if ((rc = s.ru_on ? rank_update(c.st, pn.mp, nq, pn.b, Lp, Xm, Qp) : gemm(c.st, pn.mp, nq, pn.b, -1.0, Lp, Xm, 1.0, Qp))) return rc;
+    }
+    return 0;
+}
+// ---- two-level blocked factorisation (nb = 32 inside outer blocks of `nbo` columns) ---------------------------------------
+// Single-level blocking applies every 32-wide reflector to the whole trailing matrix and again to Q: three passes over up to
+// 134 MB per panel at K = 32, i.e. HBM-bound work that fills the device (12.9 GB for one 16384 x 1024 call against 0.28 GB
+// compulsory) and, with several chains on the GPU, serialises them.  Here the panels of an outer block only update the
+// columns of that block; the columns to its right (and, afterwards, Q) see the block once, through the merged reflector
+//      H_1 ... H_q = I - Y_blk T_blk Y_blk^T,   T_blk = [[T_1, -T_1 (Y_1^T Y_2) T_2, ...], [0, T_2, ...], ...]   (dlarft by blocks)
+// built from the panels' own (Y_p, T_p) and one Gram matrix G = Y_blk^T Y_blk: rank-nbo GEMMs (K = 128 or 256) instead of
+// rank-32 ones, 4-8x fewer bytes.  Used for the plain factorisation only (rank_tol = 0): the rank-revealing early exit of the
+// truncating passes checks the trailing block after every second panel, which needs it up to date.
+static int qr_two_level(const QrCall& c, QrState& s, int nbo) {
+    hipStream_t st = c.st;
+    QrWs& w = s.w;
+    const int64_t m = c.m, n = c.n, k = m < n ? m : n;
+    const int nb = 32, nblk = (int)cdiv(k, nbo);
+    int rc;
+    for (int bi = 0; bi < nblk; ++bi) {
+        const int64_t J0 = (int64_t)bi * nbo;
+        const int bw = (int)((k - J0 < nbo) ? k - J0 : nbo);
+        const int64_t Jend = J0 + bw, mb = m - J0;
+        Mat Yb = sub(s.Ym, J0, J0);
+        // rows of the block above each panel's own top block must read as zero in the merged reflector
+        if ((rc = fill_mat(st, Yb.p, s.yrs, s.ycs, bw, bw, 0.0))) return rc;
+        double* Tb = w.Tblk + (int64_t)bi * QR_NBO_MAX * QR_NBO_MAX;            // bw x bw, row-major, pitch bw
+        if ((rc = fill_mat(st, Tb, bw, 1, bw, bw, 0.0))) return rc;
+        const int npan = (int)cdiv(bw, nb);
+        for (int q = 0; q < npan; ++q) {
+            QrPanel pn = panel_at(c, s, (int)(J0 / nb) + q, Jend);
+            pn.Wp = mat(w.W, s.wrs, s.wcs);                                      // W of the current panel only: Q goes through T_blk
+            if ((rc = panel_fused(c, s, pn, nullptr))) return rc;
+            if ((rc = trailing_update(c, s, pn, Jend - pn.j0, nullptr))) return rc;   // the panel's update stays inside the block
+            // T_blk: diagonal block = T_p (its pitch is b); column block from the recurrence once the Gram matrix exists (below)
+            if ((rc = copy_mat(st, pn.Tp, pn.b, 1, Tb + (int64_t)(pn.j0 - J0) * bw + (pn.j0 - J0), bw, 1, pn.b, pn.b))) return rc;
+        }
+        // G = Y_blk^T Y_blk, then T_blk[0:c0, c0:c0+b] = -T_blk[0:c0, 0:c0] (G[0:c0, c0:c0+b] T_q)
+        Mat Gm = mat(w.G, bw, 1);
+        if (npan > 1) {
+            if ((rc = gemm(st, bw, bw, mb, 1.0, tr(Yb), Yb, 0.0, Gm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
+            for (int q = 1; q < npan; ++q) {
+                const int64_t c0 = (int64_t)q * nb;
+                const int b = (int)((bw - c0 < nb) ? bw - c0 : nb);
+                Mat Tq = mat(Tb + c0 * bw + c0, bw, 1), tmp = mat(w.tmpT, b, 1);
+                if ((rc = gemm(st, c0, b, b, 1.0, sub(Gm, 0, c0), Tq, 0.0, tmp))) return rc;
+                if ((rc = gemm(st, c0, b, c0, -1.0, mat(Tb, bw, 1), tmp, 0.0, mat(Tb + c0, bw, 1)))) return rc;
+            }
+        }
+        // outer update of everything to the right of the block:  A_r -= Y_blk (T_blk^T (Y_blk^T A_r))
+        const int64_t nr = n - Jend;
+        if (nr > 0) {
+            Mat Ar = sub(s.Am, J0, Jend), Z = mat(w.Zo, nr, 1), Z2 = mat(w.Zo2, nr, 1);
+            if ((rc = gemm(st, bw, nr, mb, 1.0, tr(Yb), Ar, 0.0, Z, w.gemm_ws, w.gemm_ws_bytes))) return rc;
+            if ((rc = gemm(st, bw, nr, bw, 1.0, tr(mat(Tb, bw, 1)), Z, 0.0, Z2))) return rc;
+            if ((rc = gemm(st, mb, nr, bw, -1.0, Yb, Z2, 1.0, Ar))) return rc;
+        }
+    }
+    // R, then Q = H_blk1 ... H_blkB [Z; 0] (no fold: every block goes through its T_blk)
+    if ((rc = triangularise_diag(c, s, k, (int)cdiv(k, nb)))) return rc;
+    if ((rc = assemble_R_init_Q(c, s, k, QrFold{}))) return rc;
+    return accumulate_Q_blocks(c, s, k, nbo, false);
+}
+// ---- dispatch, the loop over the panels, the ending
+static int qr_factor_impl(const QrCall& c) {
+    const int64_t m = c.m, n = c.n;
+    const int nb = c.nb;
+    TN_CHECK_ARG(m >= 1 && n >= 1, "empty matrix");
+    if (c.dropped2_host) *c.dropped2_host = 0.0;
+    TN_CHECK_ARG(nb == 32 || nb == 64, "nb must be 32 or 64");
+    TN_CHECK_ARG(c.ws_bytes >= qr_ws_bytes(m, n, nb), "workspace too small");
+    int64_t k = m < n ? m : n;           // columns of Q, rows of R: k and P only change where the loop below stops early
+    int rc;
+    bool done = false, stop = false;     // a single-launch exit has done the work / an exit test has ended the panel loop
+    if ((rc = tiny_exit(c, k, &done)) || done) return rc;
+    QrState s;
+    QrWs& w = s.w;
+    qr_layout(m, n, nb, (char*)c.ws, &w);
+    if ((rc = smallqr_exit(c, w, k, &done)) || done) return rc;
+    int P = (int)cdiv(k, nb);
+    const bool truncating = c.rank_tol > 0.0 && c.keff_host != nullptr;
+    // Panel pivoting (pivot_perm_host != NULL; nb = 32, rank_tol > 0): before every panel the residual norms of all remaining
+    // columns are read back, the factorisation stops when their Frobenius norm is below rank_tol x the input's, otherwise the
+    // 32 columns with the largest residuals are swapped to the front and form the next panel (column-pivoted QR at panel
+    // granularity: a strong rank revealer at one extra read-back per panel).  pivot_perm_host[j] = input column now at j.
+    s.pivot = c.pivot_perm_host != nullptr && truncating && nb == 32;
+    for (int64_t j = 0; c.pivot_perm_host && j < n; ++j) c.pivot_perm_host[j] = j;
+    s.reveal = !s.pivot && truncating && P > 2 && nb == 32;
+    if (s.reveal) QR_LAUNCH(c, colnorm2_kernel, dim3((unsigned)n), c.A, c.rs, c.cs, m, n, w.cn);      // the input's column norms (see reveal_check)
+    // Y shares A's fast direction so panel kernels coalesce the same way
+    s.rowmajor = (c.cs == 1 && c.rs != 1);
+    s.yrs = s.rowmajor ? k : 1, s.ycs = s.rowmajor ? 1 : m, s.wrs = s.rowmajor ? nb : 1, s.wcs = s.rowmajor ? 1 : m;
+    s.Am = mat(c.A, c.rs, c.cs), s.Ym = mat(w.Y, s.yrs, s.ycs), s.Wqm = mat(w.Wq, s.yrs, s.ycs);
+    s.wform = (nb == 32);                // the fused panel step, whose W = Y T^T serves the Q accumulation too (see panel_at)
+    if (nb == 32 && (rc = cholqr_begin(c.st, w.panel_ws, &w.cq_state))) return rc;
+    s.ru_on = nb == 32 && env_flag_on("TN_QR_RANK_UPDATE");          // (see trailing_update; read per call: the tests switch it)
+    {   // two-level blocking for the plain factorisation of matrices with several outer blocks (TN_QR_NBO = 0 disables it)
+        const int v_nbo = env_int("TN_QR_NBO", 256), nbo = (v_nbo == 128 || v_nbo == 256) ? v_nbo : 0;      // read per call: the tests switch it
+        if (nbo > 0 && nb == 32 && !truncating && k >= 2 * nbo && m >= 4 * nbo) {
+            if (c.keff_host) *c.keff_host = k;
+            return qr_two_level(c, s, nbo);
+        }
+    }
+    const bool piv_dev = s.pivot && env_flag_on("TN_PIVOT_DEVICE") && n <= PIV_MAXN;      // (read per call: the tests switch it)
+    PivDev piv;
+    if (piv_dev && (rc = piv.begin(c, w, P))) return rc;
+    int64_t k_exit = k;
+    for (int p = 0; p < P && !stop; ++p) {
+        const QrPanel pn = panel_at(c, s, p, k);
+        if (piv_dev) {
+            if (p >= 1 && (rc = piv.verdict(c, p - 1, &stop, &k_exit))) return rc;
+            if (!stop && (rc = piv.select(c, w, pn))) return rc;
+        } else if (s.pivot && (rc = pivot_on_host(c, s, pn, &stop, &k_exit))) return rc;
+        if (stop) break;
+        if ((rc = s.wform ? panel_fused(c, s, pn, piv.active) : panel_jacobi64(c, s, pn))) return rc;
+        if (s.wform) dbg_check_factors(c, s, pn);
+        if ((rc = trailing_update(c, s, pn, n - pn.j0, piv.active))) return rc;
+        if (s.reveal && (p & 1) == 1 && p + 1 < P && (rc = reveal_check(c, s, pn, &stop, &k_exit))) return rc;
+    }
+    if (piv_dev && (rc = piv.finish(c, w, P, &stop, &k_exit))) return rc;
+    if (stop) k = k_exit, P = (int)(k / nb);      // the one place where k and P change (every exit leaves whole panels)
+    if (c.keff_host) *c.keff_host = k;
+    // --- triangularise the diagonal blocks, assemble R
+    if (nb == 64) QR_LAUNCH(c, (diag_qr_kernel<64>), dim3(P), c.A, c.rs, c.cs, nb, k, w.Z, w.Tri, (int*)nullptr);
+    else if ((rc = triangularise_diag(c, s, k, P))) return rc;
+    dbg_check(c.st, w.Z, nb, 1, (int64_t)P * nb, nb, "Z", -1, 0);
+    dbg_check(c.st, w.Tri, nb, 1, (int64_t)P * nb, nb, "Tri", -1, 0);
+    // --- Q = H_1 ... H_P [Z; 0]; the last panel's reflector is applied by the launch that writes [Z; 0] (nb = 32)
+    const int64_t jf = (int64_t)(P - 1) * nb;
+    // (every workgroup of the Q part recomputes the b x b product: worth it while there are few of them, i.e. for the small
+    //  factorisations whose time is launches; the large ones keep the two GEMMs)
+    const int fold_b = (nb == 32 && P >= 1 && m * k <= 256 * 512) ? (int)(k - jf) : 0;
+    // fused panel step: the m x k array holds W = Y T^T of every panel and  H_p Q = Q - Y_p (W_p^T Q);  otherwise it holds Y T and
+    // H_p Q = Q - (Y_p T_p) (Y_p^T Q).  The kernel forms  second (first_top^T Z)  either way.
+    if ((rc = assemble_R_init_Q(c, s, k, QrFold{s.wform ? w.Wq : w.Y, s.wform ? w.Y : w.Wq, s.yrs, s.ycs, jf, fold_b}))) return rc;
+    // merged reflectors (see apply_merged_T_kernel): from two panels on, unless the small-matrix fold above already took the last one
+    // (TN_QR_MERGED_Q=0 keeps the panel-by-panel accumulation; read per call: the tests switch it)
+    const bool merged_q = s.wform && c.Q != nullptr && P >= 2 && fold_b == 0 && env_flag_on("TN_QR_MERGED_Q");
+    return merged_q ? accumulate_Q_blocks(c, s, k, QMB, true) : accumulate_Q_panels(c, s, k, P, fold_b);
+}
+static int qr_factor_traced(const QrCall& c) {
+    if (c.nf_done) *c.nf_done = 0;
+    if (!g_qr_trace.on) return qr_factor_impl(c);
+    thread_local hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (!e0) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); }
+    (void)hipEventRecord(e0, c.st);
+    const int rc = qr_factor_impl(c);
+    (void)hipEventRecord(e1, c.st);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    std::lock_guard<std::mutex> lk(g_qr_trace.mu);
+    const bool truncating = c.rank_tol > 0.0 && c.keff_host;
+    const auto key = std::make_tuple(c.m, c.n, c.Q ? 1 : 0, truncating ? 1 : 0, c.pivot_perm_host ? 1 : 0);
+    auto& ss = g_qr_trace.tab[key];
+    ss.first += ms, ss.second += 1;
+    const double kr = c.keff_host ? (double)*c.keff_host : (double)(c.m < c.n ? c.m : c.n);
+    g_qr_trace.ranks[key] += kr;
+    const int cat = c.pivot_perm_host ? (c.m > 8192 ? 6 : 5) : truncating ? 4 : (c.n <= 32 ? 0 : c.n <= 64 ? 1 : c.n <= 128 ? 2 : 3);
+    g_qr_trace.cat_ms[cat] += ms; g_qr_trace.cat_rank[cat] += kr; g_qr_trace.cat_calls[cat] += 1; g_qr_trace.cat_m[cat] += (double)c.m;
+    return rc;
+}
+// rank_tol > 0 enables the early exits (reveal_check; with pivot_perm_host, the panel pivoting): *keff_host receives the number of
+// columns/rows produced.
 // nf_out2 != NULL (device, 2 doubles): a path that can divide R by its power-of-two norm factor in the launch that produces it does
 // so and sets *nf_done (the one-launch factorisation of smallqr.hip); otherwise *nf_done = 0 and the caller normalises.
 // Launches with in-kernel barriers (single-launch panel steps, smallqr.hip) may give up when the co-residency they rely on does not
@@ -1235,8 +1578,9 @@ int qr_factor(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int6
               int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
               int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done) {
     bool intact = false;
-    int rc = qr_factor_traced(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host, frob_exit,
-                              pivot_perm_host, nf_out2, nf_done, &intact);
+    const QrCall c = {st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol,
+                      keff_host, dropped2_host, frob_exit, pivot_perm_host, nf_out2, nf_done, &intact};
+    int rc = qr_factor_traced(c);
     if (fused_check_deferred() || !fused_check_needed()) return rc;
     int gave_up = 0;
     const int rc2 = fused_timeouts(st, &gave_up);
@@ -1247,353 +1591,7 @@ int qr_factor(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int6
                   "results are invalid and the input was overwritten -- rerun from a copy (this stream now takes the six-launch panel chain)", gave_up);
         return -7;
     }
-    return qr_factor_traced(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host, frob_exit,
-                            pivot_perm_host, nf_out2, nf_done, &intact);
-}
-
-static int qr_factor_traced(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
-              int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-              int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2, int* nf_done,
-              bool* input_intact) {
-    if (nf_done) *nf_done = 0;
-    if (!g_qr_trace.on)
-        return qr_factor_impl(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host, frob_exit,
-                              pivot_perm_host, nf_out2, nf_done, input_intact);
-    thread_local hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!e0) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); }
-    (void)hipEventRecord(e0, st);
-    const int rc = qr_factor_impl(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nb, ws, ws_bytes, rank_tol, keff_host, dropped2_host,
-                                  frob_exit, pivot_perm_host, nf_out2, nf_done, input_intact);
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    std::lock_guard<std::mutex> lk(g_qr_trace.mu);
-    const auto key = std::make_tuple(m, n, Q ? 1 : 0, (rank_tol > 0.0 && keff_host) ? 1 : 0, pivot_perm_host ? 1 : 0);
-    auto& ss = g_qr_trace.tab[key];
-    ss.first += ms;
-    ss.second += 1;
-    const double kr = keff_host ? (double)*keff_host : (double)(m < n ? m : n);
-    g_qr_trace.ranks[key] += kr;
-    const int c = pivot_perm_host ? (m > 8192 ? 6 : 5) : (rank_tol > 0.0 && keff_host) ? 4 : (n <= 32 ? 0 : n <= 64 ? 1 : n <= 128 ? 2 : 3);
-    g_qr_trace.cat_ms[c] += ms; g_qr_trace.cat_rank[c] += kr; g_qr_trace.cat_calls[c] += 1; g_qr_trace.cat_m[c] += (double)m;
-    return rc;
-}
-
-static int qr_factor_impl(hipStream_t st, double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs,
-                          int64_t qcs, double* R, int64_t rrs, int64_t rcs, int nb, void* ws, int64_t ws_bytes, double rank_tol,
-                          int64_t* keff_host, double* dropped2_host, int frob_exit, int64_t* pivot_perm_host, double* nf_out2,
-                          int* nf_done, bool* input_intact) {
-    TN_CHECK_ARG(m >= 1 && n >= 1, "empty matrix");
-    if (dropped2_host) *dropped2_host = 0.0;
-    TN_CHECK_ARG(nb == 32 || nb == 64, "nb must be 32 or 64");
-    TN_CHECK_ARG(ws_bytes >= qr_ws_bytes(m, n, nb), "workspace too small");
-    int64_t k = m < n ? m : n;
-    {   // tiny matrices: the whole factorisation in one workgroup (TN_QR_TINY=0: the blocked path; read per call: the tests switch it)
-        const bool tiny_on = env_flag_on("TN_QR_TINY");
-        if (tiny_on && nb == 32 && pivot_perm_host == nullptr && m * n <= 4096 && k <= 32) {
-            TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(tiny_qr_kernel, dim3(1), dim3(256), 0, st, (const double*)A, rs, cs, (int)m, (int)n, Q, qrs, qcs,
-                               R, rrs, rcs));
-            TN_CHECK_LAUNCH("tiny_qr_kernel");
-            if (keff_host) *keff_host = k;
-            if (input_intact) *input_intact = true;
-            return 0;
-        }
-    }
-    QrWs w;
-    qr_layout(m, n, nb, (char*)ws, &w);
-    // up to 64 columns (no pivoting; the rank-revealing exit only exists from three panels on): the whole factorisation in ONE launch,
-    // explicit-Q iterated Cholesky-QR (smallqr.hip); it leaves the input untouched
-    if (nb == 32 && pivot_perm_host == nullptr && Q != nullptr && smallqr_fits(m, n)) {
-        const int rcs_ = smallqr_factor(st, A, rs, cs, m, n, Q, qrs, qcs, R, rrs, rcs, nf_out2, w.gemm_ws, w.gemm_ws_bytes);
-        if (rcs_ == 0) {
-            if (keff_host) *keff_host = k;
-            if (nf_done) *nf_done = nf_out2 ? 1 : 0;
-            if (input_intact) *input_intact = true;
-            return 0;
-        }
-        if (rcs_ != 1) return rcs_;
-    }
-    int P = (int)cdiv(k, nb);
-    const int64_t kfull = k;
-    double scale2 = -1.0;                                            // largest squared column norm of the input (lazily read back)
-    // Panel pivoting (pivot_perm_host != NULL; nb = 32, rank_tol > 0): before every panel the residual norms of all remaining
-    // columns are read back, the factorisation stops when their Frobenius norm is below rank_tol x the input's, otherwise the
-    // 32 columns with the largest residuals are swapped to the front and form the next panel (column-pivoted QR at panel
-    // granularity: a strong rank revealer at one extra read-back per panel).  pivot_perm_host[j] = input column now at j.
-    const bool pivot = pivot_perm_host != nullptr && rank_tol > 0.0 && keff_host != nullptr && nb == 32;
-    if (pivot_perm_host)
-        for (int64_t j = 0; j < n; ++j) pivot_perm_host[j] = j;
-    const bool reveal = !pivot && rank_tol > 0.0 && keff_host != nullptr && P > 2 && nb == 32;
-    if (reveal) {
-        TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(colnorm2_kernel, dim3((unsigned)n), dim3(256), 0, st, A, rs, cs, m, n, w.cn));
-        TN_CHECK_LAUNCH("colnorm2_kernel");
-    }
-    // Y shares A's fast direction so panel kernels coalesce the same way
-    const bool rowmajor = (cs == 1 && rs != 1);
-    const int64_t yrs = rowmajor ? kfull : 1, ycs = rowmajor ? 1 : m;
-    const int64_t wrs = rowmajor ? nb : 1, wcs = rowmajor ? 1 : m;
-    Mat Am = mat(A, rs, cs), Ym = mat(w.Y, yrs, ycs), Wqm = mat(w.Wq, yrs, ycs);
-    int rc;
-    if (nb == 32 && (rc = cholqr_begin(st, w.panel_ws, &w.cq_state))) return rc;
-    int fbase = 0;                            // arrivals booked by the single-launch panel steps of this call (cholqr.hip)
-    {   // two-level blocking for the plain factorisation of matrices with several outer blocks (TN_QR_NBO = 0 disables it)
-        const int v_nbo = env_int("TN_QR_NBO", 256), nbo = (v_nbo == 128 || v_nbo == 256) ? v_nbo : 0;      // read per call: the tests switch it
-        if (nbo > 0 && nb == 32 && !(rank_tol > 0.0 && keff_host != nullptr) && k >= 2 * nbo && m >= 4 * nbo) {
-            if (keff_host) *keff_host = k;
-            return qr_two_level(st, Am, m, n, k, Ym, w, nbo, rs, cs, yrs, ycs, wrs, wcs, Q, qrs, qcs, R, rrs, rcs, &fbase);
-        }
-    }
-    // device-side panel pivoting (see pivot_select_kernel): the host runs one panel ahead of the verdicts it reads back
-    const bool piv_dev_on = env_flag_on("TN_PIVOT_DEVICE");      // (read per call: the tests switch it)
-    // the rank-32 updates of the panels (trailing matrix and Q) through rank_update (rank_update.hip) instead of a K = 32 launch of gemm:
-    // the same bits (TN_QR_RANK_UPDATE=0 restores gemm; read per call: the tests switch it).  The 64-wide panels keep gemm.
-    const bool ru_on = nb == 32 && env_flag_on("TN_QR_RANK_UPDATE");
-    const bool piv_dev = pivot && piv_dev_on && n <= PIV_MAXN;
-    PivState* pst = (PivState*)w.piv;
-    int* pperm = (int*)(w.piv + 1024);
-    const int* active = piv_dev ? &pst->h.active : nullptr;
-    PivMail* ring = piv_dev ? (PivMail*)pinned_host(4 * sizeof(PivMail), PIN_SHARED) : nullptr;
-    if (piv_dev && !ring) { set_error("tn_qr: no page-locked memory for the pivoting verdicts"); return 1; }
-    if (piv_dev) for (int i = 0; i < 4; ++i) __atomic_store_n(&ring[i].word, 0ull, __ATOMIC_RELAXED);       // (the slot is shared with other read-backs of this thread: no stale word may look like a stamp)
-    thread_local unsigned piv_seq = 0;                        // stamps are unique per host thread (the ring is the thread's own; wrap-around after 2^32 panels is harmless: four entries)
-    const unsigned seq0 = piv_seq;
-    if (piv_dev) piv_seq += (unsigned)P + 1u;
-    bool piv_stopped = false;
-    GemmExtra gx_active;
-    gx_active.skip = active;
-    // verdict of panel q (the selection launch in front of it): true = the exit test fired there
-    auto piv_verdict = [&](int q, bool& stop) -> int {
-        const PivMail* h = &ring[q & 3];
-        const unsigned want = seq0 + (unsigned)q + 1u;
-        unsigned long long wd = __atomic_load_n(&h->word, __ATOMIC_ACQUIRE);
-        for (long spins = 0; (unsigned)(wd >> 32) != want; ++spins) {
-            if ((spins & 0xfffff) == 0xfffff && hipStreamQuery(st) != hipErrorNotReady) {          // the stream has drained (or failed): look once more, then give up
-                wd = __atomic_load_n(&h->word, __ATOMIC_ACQUIRE);
-                if ((unsigned)(wd >> 32) == want) break;
-                set_error("tn_qr: the pivoting verdict of panel %d never arrived", q);
-                return 1;
-            }
-            wd = __atomic_load_n(&h->word, __ATOMIC_ACQUIRE);
-        }
-        stop = ((wd >> 31) & 1ull) == 0ull;
-        if (stop) {
-            k = (int64_t)(wd & 0x7fffffffull);
-            P = (int)(k / nb);
-            piv_stopped = true;
-        }
-        return 0;
-    };
-    if (piv_dev) {
-        TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(pivot_init_kernel, dim3((unsigned)cdiv(std::max<int64_t>(n, 256), 256)), dim3(256), 0, st, pst, pperm, (int)n));
-        TN_CHECK_LAUNCH("pivot_init_kernel");
-    }
-    for (int p = 0; p < P; ++p) {
-        const int64_t j0 = (int64_t)p * nb;
-        const int b = (int)((k - j0 < nb) ? k - j0 : nb);
-        const int64_t mp = m - j0, ntr = n - j0;
-        Mat Ap = sub(Am, j0, j0), Yp = sub(Ym, j0, j0);
-        if (piv_dev) {
-            if (p >= 1) {
-                bool stop = false;
-                if ((rc = piv_verdict(p - 1, stop))) return rc;
-                if (stop) break;
-            }
-            TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(colnorm2_kernel, dim3((unsigned)ntr), dim3(256), 0, st, Ap.p, rs, cs, mp, ntr, w.cn));
-            TN_CHECK_LAUNCH("colnorm2_kernel");
-            TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(pivot_select_kernel, dim3((unsigned)cdiv(ntr, PIV_CPB)), dim3(256), 0, st, (const double*)w.cn, (int)ntr, b, (int)j0, p,
-                               rank_tol * rank_tol, pst, &ring[p & 3], seq0 + (unsigned)p + 1u));
-            TN_CHECK_LAUNCH("pivot_select_kernel");
-            TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(swap_columns_dev_kernel, dim3((unsigned)cdiv(m, 64) + 1), dim3(256), 0, st, A, rs, cs, m,
-                               (const PivState*)pst, pperm));
-            TN_CHECK_LAUNCH("swap_columns_dev_kernel");
-        } else if (pivot) {
-            TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(colnorm2_kernel, dim3((unsigned)ntr), dim3(256), 0, st, Ap.p, rs, cs, mp, ntr, w.cn));
-            TN_CHECK_LAUNCH("colnorm2_kernel");
-            double* hcn = nullptr;
-            if ((rc = read_back_staged(st, (void**)&hcn, w.cn, (size_t)ntr * 8, PIN_QR, "norms"))) return rc;
-            double fro2 = 0.0;
-            for (int64_t j = 0; j < ntr; ++j) fro2 += hcn[j];
-            if (p == 0) scale2 = fro2;
-            if (p > 0 && fro2 <= rank_tol * rank_tol * scale2) {     // what is left is below the threshold: stop before this panel
-                if (dropped2_host) *dropped2_host = fro2;
-                k = j0;
-                P = p;
-                break;
-            }
-            int pairs[64];
-            select_pivots(hcn, ntr, b, j0, pivot_perm_host, pairs);
-            SwapList sl = {};
-            compose_swaps(pairs, b, sl);
-            if (sl.n > 0)
-                TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(swap_columns_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, A, rs, cs, m, sl));
-            TN_CHECK_LAUNCH("swap_columns_kernel");
-        }
-        // --- panel orthonormalisation and Householder reconstruction
-        const bool fused_panel = (nb == 32);     // orthonormalisation + reconstruction + tall products in one chain (cholqr.hip)
-        double* Tp = w.T + (int64_t)p * nb * nb;
-        // fused: W_p = Y_p T_p^T of EVERY panel is kept (in the m x k array that holds Y T for nb = 64): besides the trailing update it
-        // serves the Q accumulation, H_p Q = Q - Y_p (W_p^T Q), so Y T is never formed (a third of the panel step's output)
-        Mat Wqp = sub(Wqm, j0, j0), Wp = fused_panel ? Wqp : mat(w.W, wrs, wcs);
-        if (fused_panel) {
-            if ((rc = cholqr_panel(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b, w.panel_ws, w.panel_bytes, (uint64_t)p + 1, 1, Tp, Wp.p, yrs, ycs,
-                                   nullptr, &fbase, w.cq_state, active)))
-                return rc;
-        } else {
-            if ((rc = copy_mat(st, Ap.p, rs, cs, Yp.p, yrs, ycs, mp, b))) return rc;
-            const int nchunk = gram_nchunk(mp);
-            for (int it = 0; it < 5; ++it) {
-                if ((rc = gram_partial(st, Yp.p, ycs, yrs, mp, b, b, nullptr, 1, nchunk, w.part))) return rc;
-                const int mode = (it < 4) ? 0 : 1;
-                // after the first round the columns are images of unit columns under an orthogonal J: a squared norm below
-                // 1e-26 there is rounding noise (possibly structured, e.g. all parallel), so the column is refilled
-                if ((rc = eig_small(st, w.part, nchunk, b, 1, mode, 12, it == 0 ? 0.0 : 1e-26, w.Js, mode == 0 ? w.dead : nullptr,
-                                    nullptr, nullptr)))
-                    return rc;
-                dbg_check(st, w.Js, b, 1, b, b, "Js", p, it);
-                if ((rc = rows_times_small(st, Yp.p, yrs, ycs, mp, b, w.Js))) return rc;
-                dbg_check(st, Yp.p, yrs, ycs, mp < 64 ? mp : 64, b, "W", p, it);
-                if (mode == 0) {
-                    TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(refill_dead_kernel, dim3((unsigned)cdiv(mp, 256)), dim3(256), 0, st, Yp.p, yrs, ycs, mp,
-                                       b, w.dead, (uint64_t)(0x9E3779B97F4A7C15ULL * (uint64_t)(p * 4 + it + 1))));
-                    TN_CHECK_LAUNCH("refill_dead_kernel");
-                }
-            }
-            TN_PROF_LAUNCH(st, PROF_LU, hipLaunchKernelGGL((lu_reconstruct_kernel<64>), dim3(1), dim3(256), 0, st, Yp.p, yrs, ycs, b, w.Uinv, Tp, w.UT, w.UTq,
-                               Wp.p, wrs, wcs, Wqp.p));
-            TN_CHECK_LAUNCH("lu_reconstruct_kernel");
-        }
-        dbg_check(st, Tp, b, 1, b, b, "T", p, 9);
-        dbg_check(st, w.Uinv, b, 1, b, b, "Uinv", p, 9);
-        if (mp > b && !fused_panel) {            // rows below the top block: Y <- Q1 Uinv,  W <- Q1 (Uinv T^T),  Wq <- Q1 (Uinv T)
-            dim3 grid((unsigned)cdiv(mp - b, 256));
-            prof_begin(st, PROF_ROWS_SMALL);
-            hipLaunchKernelGGL((rows_times_small3_kernel<64>), grid, dim3(256), 0, st, sub(Yp, b, 0).p, yrs, ycs, mp - b, b,
-                               w.Uinv, w.UT, w.UTq, sub(Wp, b, 0).p, wrs, wcs, sub(Wqp, b, 0).p);
-            TN_CHECK_LAUNCH("rows_times_small3_kernel");
-            prof_end(st, PROF_ROWS_SMALL, 6.0 * (mp - b) * b * b, 32.0 * (mp - b) * b);
-        }
-        // --- trailing update  A[j0:, j0:] -= (Y T^T) (Y^T A[j0:, j0:])
-        Mat Xm = mat(w.X, ntr, 1);
-        if (piv_dev) {         // (the same two products, skipped on the device once the exit test has fired)
-            const Mat Yt = tr(Yp);
-            if ((rc = gemm_ex(st, b, ntr, mp, 1.0, Yt.p, Yt.rs, Yt.cs, Ap.p, Ap.rs, Ap.cs, 0.0, Xm.p, Xm.rs, Xm.cs, 1, 0, 0, 0, w.gemm_ws, w.gemm_ws_bytes,
-                              &gx_active)))
-                return rc;
-            if ((rc = ru_on ? rank_update(st, mp, ntr, b, Wp, Xm, Ap, active)
-                            : gemm_ex(st, mp, ntr, b, -1.0, Wp.p, Wp.rs, Wp.cs, Xm.p, Xm.rs, Xm.cs, 1.0, Ap.p, Ap.rs, Ap.cs, 1, 0, 0, 0, nullptr, 0, &gx_active)))
-                return rc;
-        } else {
-            if ((rc = gemm(st, b, ntr, mp, 1.0, tr(Yp), Ap, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            if ((rc = ru_on ? rank_update(st, mp, ntr, b, Wp, Xm, Ap) : gemm(st, mp, ntr, b, -1.0, Wp, Xm, 1.0, Ap))) return rc;
-        }
-        if (reveal && (p & 1) == 1 && p + 1 < P) {
-            const int64_t j1 = j0 + b;
-            const int64_t nt = n - j1;
-            TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(colnorm2_kernel, dim3((unsigned)nt), dim3(256), 0, st, sub(Am, j1, j1).p, rs, cs, m - j1,
-                               nt, w.cn + n));
-            TN_CHECK_LAUNCH("colnorm2_kernel");
-            // one read-back: the trailing norms, and (first check only) the input norms stored in front of them
-            const size_t nread = (size_t)(scale2 < 0.0 ? n + nt : nt);
-            double* hcn = nullptr;
-            if ((rc = read_back_staged(st, (void**)&hcn, scale2 < 0.0 ? w.cn : w.cn + n, nread * 8, PIN_QR, "norms"))) return rc;
-            const double* tr2 = hcn;
-            // measure of "what is left" against the input: largest column norm (default) or, frob_exit, the Frobenius norm
-            if (scale2 < 0.0) {
-                scale2 = 0.0;
-                for (int64_t j = 0; j < n; ++j) scale2 = frob_exit ? scale2 + hcn[j] : std::max(scale2, hcn[j]);
-                tr2 = hcn + n;
-            }
-            double h[2] = {scale2, 0.0};
-            for (int64_t j = 0; j < nt; ++j) h[1] = frob_exit ? h[1] + tr2[j] : std::max(h[1], tr2[j]);
-            if (h[1] <= rank_tol * rank_tol * scale2) {       // nothing left above the threshold: stop here
-                if (dropped2_host) {                           // squared Frobenius norm of the block that is dropped
-                    double fro2 = 0.0;
-                    for (int64_t j = 0; j < nt; ++j) fro2 += tr2[j];
-                    *dropped2_host = fro2;
-                }
-                k = j1;
-                P = p + 1;
-                break;
-            }
-        }
-    }
-    if (piv_dev) {
-        // the last panel's own verdict (it may have stopped the factorisation in front of itself), then the permutation
-        if (P >= 1 && k == kfull) {
-            bool stop = false;
-            if ((rc = piv_verdict(P - 1, stop))) return rc;
-        }
-        // state block (1024 bytes, for the dropped norm) and permutation are neighbours in the workspace: one copy
-        int* hp = nullptr;
-        if ((rc = read_back_staged(st, (void**)&hp, w.piv, 1024 + (size_t)n * 4, PIN_QR, "permutation"))) return rc;
-        for (int64_t j = 0; j < n; ++j) pivot_perm_host[j] = hp[256 + j];
-        if (((const PivState*)hp)->h.stamp < 0) {
-            set_error("tn_qr: the device-side pivot selection of panel %d was not a valid set of columns (TN_PIVOT_DEVICE=0 selects on the host)",
-                      -((const PivState*)hp)->h.stamp - 1);
-            return 1;
-        }
-        if (piv_stopped && dropped2_host) *dropped2_host = ((const PivState*)hp)->h.dropped2;
-    }
-    if (keff_host) *keff_host = k;
-    // --- triangularise the diagonal blocks, assemble R
-    if (nb == 32) TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL((diag_qr_kernel<32>), dim3(P), dim3(256), 0, st, A, rs, cs, nb, k, w.Z, w.Tri, (int*)w.cq_state));
-    else TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL((diag_qr_kernel<64>), dim3(P), dim3(256), 0, st, A, rs, cs, nb, k, w.Z, w.Tri, (int*)nullptr));
-    TN_CHECK_LAUNCH("diag_qr_kernel");
-    if (w.cq_state) cholqr_end_ok(st);
-    dbg_check(st, w.Z, nb, 1, (int64_t)P * nb, nb, "Z", -1, 0);
-    dbg_check(st, w.Tri, nb, 1, (int64_t)P * nb, nb, "Tri", -1, 0);
-    // --- Q = H_1 ... H_P [Z; 0]; the last panel's reflector is applied by the launch that writes [Z; 0] (nb = 32)
-    const int qcolfast = (qcs == 1) ? 1 : 0;
-    const int64_t jf = (int64_t)(P - 1) * nb;
-    // (every workgroup of the Q part recomputes the b x b product: worth it while there are few of them, i.e. for the small
-    //  factorisations whose time is launches; the large ones keep the two GEMMs)
-    const int fold_b = (nb == 32 && P >= 1 && m * k <= 256 * 512) ? (int)(k - jf) : 0;
-    // fused panel step: the m x k array holds W = Y T^T of every panel and  H_p Q = Q - Y_p (W_p^T Q);  otherwise it holds Y T and
-    // H_p Q = Q - (Y_p T_p) (Y_p^T Q).  The kernel below forms  second (first_top^T Z)  either way.
-    const bool wform = (nb == 32);
-    {
-        const unsigned nR = (unsigned)cdiv(k * n, 256), nQ = (unsigned)cdiv(m * k, 256);
-        TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(assemble_R_init_Q_kernel, dim3(nR + nQ), dim3(256), 0, st, A, rs, cs, nb, k, n, w.Z, w.Tri, R, rrs,
-                           rcs, nR, Q, qrs, qcs, m, qcolfast, (const double*)(wform ? w.Wq : w.Y), (const double*)(wform ? w.Y : w.Wq), yrs, ycs, jf, fold_b));
-        TN_CHECK_LAUNCH("assemble_R_init_Q_kernel");
-    }
-    Mat Qm = mat(Q, qrs, qcs);
-    // merged reflectors (see apply_merged_T_kernel): from two panels on, unless the small-matrix fold above already took the last one
-    // (TN_QR_MERGED_Q=0 keeps the panel-by-panel accumulation; read per call: the tests switch it)
-    const bool merged_q = wform && Q != nullptr && P >= 2 && fold_b == 0 && env_flag_on("TN_QR_MERGED_Q");
-    if (merged_q) {
-        const int nblk = (int)cdiv(k, QMB);
-        TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(zero_above_panels_kernel, dim3(16, (unsigned)nblk), dim3(256), 0, st, w.Y, yrs, ycs, k, nb));
-        TN_CHECK_LAUNCH("zero_above_panels_kernel");
-        for (int bi = nblk - 1; bi >= 0; --bi) {
-            const int64_t J0 = (int64_t)bi * QMB;
-            const int bw = (int)((k - J0 < QMB) ? k - J0 : QMB);
-            const int64_t mb = m - J0, nq = k - J0;
-            const int npan = (int)cdiv(bw, nb);
-            Mat Yb = sub(Ym, J0, J0), Qb = sub(Qm, J0, J0), Z = mat(w.Zo, nq, 1), X = mat(w.Zo2, nq, 1), Gm = mat(w.G, bw, 1);
-            if (npan > 1 && (rc = gemm(st, bw, bw, mb, 1.0, tr(Yb), Yb, 0.0, Gm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            // (the last block meets [Z; 0]: only its top bw rows are non-zero, the product over the rest adds zeros)
-            if ((rc = gemm(st, bw, nq, bi == nblk - 1 ? (int64_t)bw : mb, 1.0, tr(Yb), Qb, 0.0, Z, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-            TN_PROF_LAUNCH(st, PROF_QR_AUX, hipLaunchKernelGGL(apply_merged_T_kernel, dim3((unsigned)cdiv(nq, 32)), dim3(256), 0, st, (const double*)Z.p, nq,
-                               (const double*)Gm.p, bw, (const double*)(w.T + (J0 / nb) * nb * nb), npan, X.p));
-            TN_CHECK_LAUNCH("apply_merged_T_kernel");
-            if ((rc = gemm(st, mb, nq, bw, -1.0, Yb, X, 1.0, Qb))) return rc;
-        }
-        return 0;
-    }
-    for (int p = P - 1 - (fold_b > 0 ? 1 : 0); p >= 0; --p) {
-        const int64_t j0 = (int64_t)p * nb;
-        const int b = (int)((k - j0 < nb) ? k - j0 : nb);
-        const int64_t mp = m - j0, nq = k - j0;
-        Mat Qp = sub(Qm, j0, j0), Yp = sub(Ym, j0, j0), Wqp = sub(Wqm, j0, j0);
-        Mat Xm = mat(w.X, nq, 1);
-        // Y^T Q (the last panel meets [Z; 0]: only its top b rows are non-zero, the product over the rest adds zeros)
-        if ((rc = gemm(st, b, nq, p == P - 1 ? (int64_t)b : mp, 1.0, tr(wform ? Wqp : Yp), Qp, 0.0, Xm, w.gemm_ws, w.gemm_ws_bytes))) return rc;
-        // Q -= (Y T) (Y^T Q) = Y (W^T Q)
-        if ((rc = ru_on ? rank_update(st, mp, nq, b, wform ? Yp : Wqp, Xm, Qp) : gemm(st, mp, nq, b, -1.0, wform ? Yp : Wqp, Xm, 1.0, Qp))) return rc;
-    }
-    return 0;
+    return qr_factor_traced(c);
 }
 
 }  // namespace tn
