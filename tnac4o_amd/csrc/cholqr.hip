@@ -1217,12 +1217,26 @@ __global__ __launch_bounds__(256) void cq_fused_kernel(const double* X, int64_t 
 // workspace layout: as for the single-launch form up to 2 x CQ_FUSED_MAXBLK workgroups (whether a launch of more than CQ_FUSED_MAXBLK
 // takes that form is decided per call, see FusedTallLaunch in fused.hip)
 static inline bool cq_fused_fits(int64_t nblk) { return nblk <= 2 * CQ_FUSED_MAXBLK; }
+static_assert(CQ_STATE_BYTES % 256 == 0, "the state block is the first region of the workspace: R must start right behind it");
+struct CqWs { double *Rg, *part, *lu, *topblk, *gsum; int* bexp; };
+static int64_t cholqr_layout(int64_t nrows, char* base, CqWs* out) {
+    const int64_t nblk = cdiv(nrows, CQ_RB);
+    const bool fits = cq_fused_fits(nblk);
+    CqWs w;
+    WsCarve ws{base};
+    ws.take(CQ_STATE_BYTES);                                        // state (cholqr_reset, cholqr_begin and the diagnostics address it as ws)
+    w.Rg = ws.take<double>((1024 + 32) * 8);
+    w.part = ws.take<double>((fits ? 2 * nblk : nblk) * CQ_PART * 8);
+    w.bexp = ws.take<int>(nblk * 4);
+    w.lu = ws.take<double>((fits ? nblk : 1) * CQ_LU_DOUBLES * 8);
+    w.topblk = ws.take<double>(2 * 1024 * 8);
+    w.gsum = ws.take<double>(2 * CQ_PART * 8);                      // the summed Gram matrix of the sliced reduction (pass parity)
+    if (out) *out = w;
+    return ws.total() + 256;                                        // (the query has always asked for 256 bytes past the last region)
+}
 int64_t cholqr_ws_bytes(int64_t nrows, int b) {
     (void)b;
-    const int64_t nblk = cdiv(nrows, CQ_RB);
-    const int64_t nlu = cq_fused_fits(nblk) ? nblk : 1, npart = cq_fused_fits(nblk) ? 2 * nblk : nblk;
-    return CQ_STATE_BYTES + align_up((1024 + 32) * 8, 256) + align_up(npart * CQ_PART * 8, 256) + align_up(nblk * 4, 256) +
-           align_up(nlu * CQ_LU_DOUBLES * 8, 256) + align_up(2 * 1024 * 8, 256) + align_up(2 * CQ_PART * 8, 256) + 256;
+    return cholqr_layout(nrows, nullptr, nullptr);
 }
 
 // the stream's sticky count of single-launch panels that gave up at a barrier (cq_stats[10]), for fused_timeouts: one 8-byte read-back
@@ -1321,19 +1335,15 @@ int cholqr_panel(hipStream_t st, const double* X, int64_t irs, int64_t ics, doub
                  void* state, const int* active) {
     TN_CHECK_ARG(b >= 1 && b <= 32, "panel width must be <= 32");
     TN_CHECK_ARG(nrows >= b, "panel must have at least b rows");
-    TN_CHECK_ARG(ws_bytes >= cholqr_ws_bytes(nrows, b), "workspace too small");
+    CqWs w;
+    TN_CHECK_ARG(ws_bytes >= cholqr_layout(nrows, (char*)ws, &w), "workspace too small");
     TN_CHECK_ARG(X != Y, "panel and basis must not alias");
     TN_CHECK_ARG(!reconstruct || (Tp && W), "reconstruction needs T and W");
     const int nblk = (int)cdiv(nrows, CQ_RB);
-    char* p = (char*)ws;
-    CqState* stt = (CqState*)(state ? state : ws); p += CQ_STATE_BYTES;       // (state: the stream's own block, see cholqr_begin)
-    double* Rg = (double*)p; p += align_up((1024 + 32) * 8, 256);
     const bool fits = cq_fused_fits(nblk);
-    double* part = (double*)p; p += align_up((int64_t)(fits ? 2 * nblk : nblk) * CQ_PART * 8, 256);
-    int* bexp = (int*)p; p += align_up((int64_t)nblk * 4, 256);
-    double* lu = reconstruct ? (double*)p : nullptr; p += align_up((int64_t)(fits ? nblk : 1) * CQ_LU_DOUBLES * 8, 256);
-    double* topblk = (double*)p; p += align_up(2 * 1024 * 8, 256);
-    double* gsum = (double*)p;                                      // 2 x CQ_PART: the summed Gram matrix of the sliced reduction (pass parity)
+    CqState* stt = (CqState*)(state ? state : ws);                  // (state: the stream's own block, see cholqr_begin)
+    double *Rg = w.Rg, *part = w.part, *lu = reconstruct ? w.lu : nullptr, *topblk = w.topblk, *gsum = w.gsum;
+    int* bexp = w.bexp;
     const int maxpass = panel_maxpass();                           // (TN_PANEL_MAXPASS: fewer passes, to drive the Householder fallback in tests)
     const int slot = cholqr_stream_slot(st);
     const int maxblk = fused_maxblk();                             // ordinary single-launch panels: at most this many workgroups

@@ -70,6 +70,23 @@ int upload(hipStream_t st, void* dev, const void* host, size_t bytes, PinSlot sl
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 
+// ---- workspace layouts -------------------------------------------------------------------------------------------------------
+// The regions of a step's workspace are written down once, in its *_layout function, as a sequence of take() calls.  Run with a
+// null base the sequence only adds the sizes up (the *_ws_bytes query), with the caller's workspace it hands out the pointers.
+// Every region is rounded up to 256 bytes.
+struct WsCarve {
+    char* base;                     // nullptr: size run, every take() returns nullptr
+    int64_t off = 0;
+    template <typename T = char>
+    T* take(int64_t bytes) {
+        char* p = base ? base + off : nullptr;
+        off += align_up(bytes, 256);
+        return (T*)p;
+    }
+    int64_t total() const { return off; }
+};
+constexpr int64_t NORMALIZE_SCRATCH_BYTES = 8192;      // the scratch normalize_pow2 asks for (misc.hip; tn_normalize_pow2 in tnpeps.h)
+
 // ---- optional event timing per kernel family (prof.hip) ---------------------------------------------
 enum { PROF_GEMM_128x128 = 0, PROF_GEMM_128x32, PROF_GEMM_32x128, PROF_GEMM_64x64, PROF_SPLITK_REDUCE, PROF_ABSORB,
        PROF_GRAM, PROF_EIG, PROF_ROWS_SMALL, PROF_VECS_SMALL,

@@ -29,44 +29,52 @@
 #include "common.h"
 #include "devprim.h"
 
+#include <algorithm>
+#include <initializer_list>
+
 namespace tn {
 
-static inline int64_t up256m(int64_t b) { return align_up(b, 256); }
-constexpr int64_t NF_SCRATCH = 8192 + 256;          // normalize_pow2 scratch + the [nf, 1/nf] pair
+static bool dims_ok(std::initializer_list<int64_t> dims) {
+    for (int64_t d : dims)
+        if (d < 1) return false;
+    return true;
+}
 
-struct Env3Plan {
-    int64_t half, y, wp;                  // doubles: first product, second product, permuted W (side 1)
-    int64_t g1, g2, g3;                   // split-K scratch of the three GEMMs
+// workspace of env3: first product (unused with half_out) | second product | permuted W (side 1) | split-K scratch of the three
+// GEMMs | [nf, 1/nf] | scratch of normalize_pow2
+struct Env3Ws {
+    double *H, *Y, *Wp, *g, *nf2;
+    void* scratch;
+    int64_t g1, g2, g3;                   // bytes of g each of the three GEMMs asks for
 };
-
-static Env3Plan env3_plan(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2) {
-    Env3Plan p;
+static int64_t env3_layout(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2,
+                           char* base, Env3Ws* out) {
+    Env3Ws w;
+    int64_t half, y, wp;                  // doubles of H, Y, Wp
     if (side == 0) {
-        p.half = bl * pd * Dt2 * Db;
-        p.y = br * Dt2 * Db * pu;
-        p.wp = 0;
-        p.g1 = gemm_ws_bytes(pd * Dt2, Db, Dt, bl);
-        p.g2 = gemm_ws_bytes(Dt2 * Db, pu, bl * pd, br);
-        p.g3 = gemm_ws_bytes(br * Dt2, Db2, Db * pu, 1);
+        half = bl * pd * Dt2 * Db;
+        y = br * Dt2 * Db * pu;
+        wp = 0;
+        w.g1 = gemm_ws_bytes(pd * Dt2, Db, Dt, bl);
+        w.g2 = gemm_ws_bytes(Dt2 * Db, pu, bl * pd, br);
+        w.g3 = gemm_ws_bytes(br * Dt2, Db2, Db * pu, 1);
     } else {
-        p.half = pu * br * Dt2 * Db;
-        p.y = bl * pd * Dt2 * Db;
-        p.wp = bl * pd * pu * br;
-        p.g1 = gemm_ws_bytes(br * Dt2, Db, Db2, pu);
-        p.g2 = gemm_ws_bytes(bl * pd, Dt2 * Db, pu * br, 1);
-        p.g3 = gemm_ws_bytes(Dt, Db, pd * Dt2, bl);
+        half = pu * br * Dt2 * Db;
+        y = bl * pd * Dt2 * Db;
+        wp = bl * pd * pu * br;
+        w.g1 = gemm_ws_bytes(br * Dt2, Db, Db2, pu);
+        w.g2 = gemm_ws_bytes(bl * pd, Dt2 * Db, pu * br, 1);
+        w.g3 = gemm_ws_bytes(Dt, Db, pd * Dt2, bl);
     }
-    return p;
-}
-
-static int64_t env3_ws(const Env3Plan& p) {
-    int64_t g = p.g1 > p.g2 ? p.g1 : p.g2;
-    g = g > p.g3 ? g : p.g3;
-    return up256m(p.half * 8) + up256m(p.y * 8) + up256m(p.wp * 8) + up256m(g) + NF_SCRATCH;
-}
-
-static bool dims_ok(int64_t a, int64_t b, int64_t c, int64_t d, int64_t e, int64_t f, int64_t g, int64_t h) {
-    return a >= 1 && b >= 1 && c >= 1 && d >= 1 && e >= 1 && f >= 1 && g >= 1 && h >= 1;
+    WsCarve ws{base};
+    w.H = ws.take<double>(half * 8);
+    w.Y = ws.take<double>(y * 8);
+    w.Wp = ws.take<double>(wp * 8);
+    w.g = ws.take<double>(std::max({w.g1, w.g2, w.g3}));
+    w.nf2 = ws.take<double>(256);
+    w.scratch = ws.take(NORMALIZE_SCRATCH_BYTES);
+    if (out) *out = w;
+    return ws.total();
 }
 
 // W[l][d][r][u] -> Wp[l][d][u][r]
@@ -84,69 +92,43 @@ __global__ void log2_acc_kernel(const double* __restrict__ nf2, const double* __
     if (threadIdx.x == 0 && blockIdx.x == 0) acc_out[0] = (acc_in ? acc_in[0] : 0.0) + (double)ilogb(nf2[0]);
 }
 
-int64_t env3_ws_bytes(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2) {
-    if ((side != 0 && side != 1) || !dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2)) return 0;
-    return env3_ws(env3_plan(side, Dt, pd, Dt2, bl, br, pu, Db, Db2));
-}
-
-int env3(hipStream_t st, int side, const double* E, const double* At, const double* W, const double* Ab, int64_t Dt, int64_t pd, int64_t Dt2,
-         int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out, double* log2nf_out,
-         double* half_out, void* ws, int64_t ws_bytes) {
-    TN_CHECK_ARG(side == 0 || side == 1, "side must be 0 (left step) or 1 (right step)");
-    TN_CHECK_ARG(E && At && W && Ab && out && log2nf_out && ws, "null operand");
-    TN_CHECK_ARG(dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2), "non-positive dimension");
-    const Env3Plan p = env3_plan(side, Dt, pd, Dt2, bl, br, pu, Db, Db2);
-    TN_CHECK_ARG(ws_bytes >= env3_ws(p), "workspace too small");
-    char* w = (char*)ws;
-    double* H = (double*)w;
-    w += up256m(p.half * 8);
-    if (half_out) H = half_out;
-    double* Y = (double*)w;
-    w += up256m(p.y * 8);
-    double* Wp = (double*)w;
-    w += up256m(p.wp * 8);
-    double* g = (double*)w;
-    int64_t gb = p.g1 > p.g2 ? p.g1 : p.g2;
-    gb = gb > p.g3 ? gb : p.g3;
-    w += up256m(gb);
-    double* nf2 = (double*)w;
-    void* scratch = w + 256;
-    int rc;
-    if (side == 0) {
-        // HL_l[(d,t'), b] = At^T[(d,t'), t] . EL_l[t, b]
-        if ((rc = gemm(st, pd * Dt2, Db, Dt, 1.0, At, 1, pd * Dt2, E, Db, 1, 0.0, H, Db, 1, bl, 0, Dt * Db, pd * Dt2 * Db,
-                       p.g1 > 0 ? g : nullptr, p.g1))) return rc;
-        // Y_r[(t',b), u] = HL^T[(t',b), (l,d)] . W_r[(l,d), u]
-        if ((rc = gemm(st, Dt2 * Db, pu, bl * pd, 1.0, H, 1, Dt2 * Db, W, br * pu, 1, 0.0, Y, pu, 1, br, 0, pu, Dt2 * Db * pu,
-                       p.g2 > 0 ? g : nullptr, p.g2))) return rc;
-        // EL'[(r,t'), b'] = Y[(r,t'), (b,u)] . Ab[(b,u), b']
-        if ((rc = gemm(st, br * Dt2, Db2, Db * pu, 1.0, Y, Db * pu, 1, Ab, Db2, 1, 0.0, out, Db2, 1, 1, 0, 0, 0, p.g3 > 0 ? g : nullptr, p.g3)))
-            return rc;
-        if ((rc = normalize_pow2(st, out, br * Dt2 * Db2, nf2, scratch, 8192))) return rc;
-    } else {
-        // HR_u[(r,t'), b] = ER[(r,t'), b'] . Ab_u[b', b]     (Ab_u[b', b] = Ab[b, u, b'])
-        if ((rc = gemm(st, br * Dt2, Db, Db2, 1.0, E, Db2, 1, Ab, 1, pu * Db2, 0.0, H, Db, 1, pu, 0, Db2, br * Dt2 * Db,
-                       p.g1 > 0 ? g : nullptr, p.g1))) return rc;
-        const int64_t nw = bl * pd * pu * br;
-        int64_t nbk = cdiv(nw, 256);
-        if (nbk > 1024) nbk = 1024;
-        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(mpo_swap_ru_kernel, dim3((unsigned)nbk), dim3(256), 0, st, W, bl * pd, (int)br, (int)pu, Wp));
-        TN_CHECK_LAUNCH("mpo_swap_ru_kernel");
-        // Y[(l,d), (t',b)] = W'[(l,d), (u,r)] . HR[(u,r), (t',b)]
-        if ((rc = gemm(st, bl * pd, Dt2 * Db, pu * br, 1.0, Wp, pu * br, 1, H, Dt2 * Db, 1, 0.0, Y, Dt2 * Db, 1, 1, 0, 0, 0,
-                       p.g2 > 0 ? g : nullptr, p.g2))) return rc;
-        // ER_l[t, b] = At[t, (d,t')] . Y_l[(d,t'), b]
-        if ((rc = gemm(st, Dt, Db, pd * Dt2, 1.0, At, pd * Dt2, 1, Y, Db, 1, 0.0, out, Db, 1, bl, 0, pd * Dt2 * Db, Dt * Db,
-                       p.g3 > 0 ? g : nullptr, p.g3))) return rc;
-        if ((rc = normalize_pow2(st, out, bl * Dt * Db, nf2, scratch, 8192))) return rc;
-    }
-    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(log2_acc_kernel, dim3(1), dim3(64), 0, st, nf2, log2nf_in, log2nf_out));
-    TN_CHECK_LAUNCH("log2_acc_kernel");
-    return 0;
-}
-
 // ---- cell marginal -----------------------------------------------------------------------------------------------------
 constexpr int64_t CM_QMAX = 16384;       // LDS holds the q entries of the table
+
+// workspace of a cell closing: X (rows x ncols) | split-K scratch of its product
+struct CellWs {
+    double *X, *g;
+    int64_t gb;                           // bytes of g the product asks for
+};
+static int64_t cell_layout(int64_t rows, int64_t ncols, int64_t K, char* base, CellWs* out) {
+    const int64_t gb = gemm_ws_bytes(rows, ncols, K, 1);
+    WsCarve ws{base};
+    double* X = ws.take<double>(rows * ncols * 8);
+    double* g = ws.take<double>(gb);
+    if (out) *out = CellWs{X, g, gb};
+    return ws.total();
+}
+// X[rows, (u,r)] = HL[rows, K] . HR[(u,r), K]^T
+static int cell_product(hipStream_t st, const double* HL, const double* HR, int64_t rows, int64_t ncols, int64_t K, const CellWs& w) {
+    return gemm(st, rows, ncols, K, 1.0, HL, K, 1, HR, 1, K, 0.0, w.X, ncols, 1, 1, 0, 0, 0, w.gb > 0 ? w.g : nullptr, w.gb);
+}
+
+// sum_{l,u} f[l,u] x[l,d,u,r] by one wave (every lane returns it; 0 for d or r outside the cell).  Lane i adds the products
+// i, i + 64, ... of the (l,u) plane in that order, then the lanes are added in a butterfly: the order depends on nl nu alone.
+__device__ __forceinline__ double cell_gather(const double* __restrict__ x, const double* __restrict__ f, int d, int r, int nl, int pd,
+                                              int br, int nu, int lane) {
+    const int nlu = nl * nu;
+    double acc = 0.0;
+    if (d >= 0 && d < pd && r >= 0 && r < br) {
+        for (int i = lane; i < nlu; i += 64) {
+            const int l = i / nu, u = i - l * nu;
+            acc += f[i] * x[(((int64_t)l * pd + d) * nu + u) * br + r];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    return acc;
+}
 
 // one workgroup: wave w gathers the states s = w, w+4, ..., its lanes split the (l,u) sum
 __global__ __launch_bounds__(256) void cluster_marginal_kernel(const double* __restrict__ X, const double* __restrict__ F,
@@ -157,19 +139,8 @@ __global__ __launch_bounds__(256) void cluster_marginal_kernel(const double* __r
     extern __shared__ double sP[];
     __shared__ double red[256];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int nlu = nl * nu;
     for (int s = wv; s < q; s += 4) {
-        const int d = dmap[s], r = rmap[s];
-        double acc = 0.0;
-        if (d >= 0 && d < pd && r >= 0 && r < br) {
-            const double* f = F + (int64_t)s * nlu;
-            for (int e = lane; e < nlu; e += 64) {
-                const int l = e / nu, u = e - l * nu;
-                acc += f[e] * X[(((int64_t)l * pd + d) * nu + u) * br + r];
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        const double acc = cell_gather(X, F + (int64_t)s * nl * nu, dmap[s], rmap[s], nl, pd, br, nu, lane);
         if (lane == 0) sP[s] = acc;
     }
     __syncthreads();
@@ -199,33 +170,6 @@ __global__ __launch_bounds__(256) void cluster_marginal_kernel(const double* __r
         minP[0] = mPn;
         log2z[0] = log2(raw) + (log2L ? log2L[0] : 0.0) + (log2R ? log2R[0] : 0.0);
     }
-}
-
-int64_t cluster_marginal_ws_bytes(int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
-    if (!dims_ok(bl, pd, br, pu, K, 1, 1, 1)) return 0;
-    return up256m(bl * pd * pu * br * 8) + up256m(gemm_ws_bytes(bl * pd, pu * br, K, 1));
-}
-
-int cluster_marginal(hipStream_t st, const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
-                     int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* P,
-                     double* minP, double* log2z, void* ws, int64_t ws_bytes) {
-    TN_CHECK_ARG(HL && HR && F && dmap && rmap && P && minP && log2z && ws, "null operand");
-    TN_CHECK_ARG(dims_ok(q, bl, pd, br, pu, K, 1, 1), "non-positive dimension");
-    TN_CHECK_ARG(q <= CM_QMAX, "more than 16384 cell states");
-    TN_CHECK_ARG(ws_bytes >= cluster_marginal_ws_bytes(bl, pd, br, pu, K), "workspace too small");
-    double* X = (double*)ws;
-    const int64_t gb = gemm_ws_bytes(bl * pd, pu * br, K, 1);
-    double* g = (double*)((char*)ws + up256m(bl * pd * pu * br * 8));
-    int rc;
-    // X[(l,d), (u,r)] = HL[(l,d), K] . HR[(u,r), K]^T
-    if ((rc = gemm(st, bl * pd, pu * br, K, 1.0, HL, K, 1, HR, 1, K, 0.0, X, pu * br, 1, 1, 0, 0, 0, gb > 0 ? g : nullptr, gb))) return rc;
-    const size_t lds = (size_t)q * 8;
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)cluster_marginal_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(cluster_marginal_kernel, dim3(1), dim3(256), lds, st, X, F, dmap, rmap, (int)q, (int)bl,
-                                                     (int)pd, (int)br, (int)pu, log2L, log2R, P, minP, log2z));
-    TN_CHECK_LAUNCH("cluster_marginal_kernel");
-    return 0;
 }
 
 // ---- nearest-neighbour bond marginals ----------------------------------------------------------------------------------
@@ -297,37 +241,18 @@ __global__ __launch_bounds__(256) void bond_finish_kernel(const double* __restri
     }
 }
 
-int64_t cluster_bond_marginal_ws_bytes(int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
-    if (!dims_ok(q, bl, pd, br, pu, K, 1, 1)) return 0;
-    return cluster_marginal_ws_bytes(bl, pd, br, pu, K) + up256m(q * bl * 8) + up256m(q * pu * 8);
-}
-
-int cluster_bond_marginal(hipStream_t st, const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap,
-                          int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R,
-                          double* Pl, double* Pu, double* minB, double* log2z, void* ws, int64_t ws_bytes) {
-    TN_CHECK_ARG(HL && HR && F && dmap && rmap && Pl && Pu && minB && log2z && ws, "null operand");
-    TN_CHECK_ARG(dims_ok(q, bl, pd, br, pu, K, 1, 1), "non-positive dimension");
-    TN_CHECK_ARG(q <= CM_QMAX, "more than 16384 cell states");
-    TN_CHECK_ARG(ws_bytes >= cluster_bond_marginal_ws_bytes(q, bl, pd, br, pu, K), "workspace too small");
-    char* w = (char*)ws;
-    double* X = (double*)w;
-    w += up256m(bl * pd * pu * br * 8);
-    const int64_t gb = gemm_ws_bytes(bl * pd, pu * br, K, 1);
-    double* g = (double*)w;
-    w += up256m(gb);
-    double* Rl = (double*)w;
-    w += up256m(q * bl * 8);
-    double* Ru = (double*)w;
-    int rc;
-    // X[(l,d), (u,r)] = HL[(l,d), K] . HR[(u,r), K]^T      (as cluster_marginal)
-    if ((rc = gemm(st, bl * pd, pu * br, K, 1.0, HL, K, 1, HR, 1, K, 0.0, X, pu * br, 1, 1, 0, 0, 0, gb > 0 ? g : nullptr, gb))) return rc;
-    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(bond_gather_kernel, dim3((unsigned)q), dim3(256), 0, st, X, F, dmap, rmap, (int)bl,
-                                                     (int)pd, (int)br, (int)pu, Rl, Ru));
-    TN_CHECK_LAUNCH("bond_gather_kernel");
-    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(bond_finish_kernel, dim3(1), dim3(256), 0, st, Rl, Ru, q * bl, q * pu, log2L, log2R,
-                                                     Pl, Pu, minB, log2z));
-    TN_CHECK_LAUNCH("bond_finish_kernel");
-    return 0;
+// workspace of the bond marginal: the cell's | raw Pl (q x bl) | raw Pu (q x pu)
+struct BondWs {
+    CellWs cell;
+    double *Rl, *Ru;
+};
+static int64_t bond_layout(int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, char* base, BondWs* out) {
+    WsCarve ws{base};
+    ws.take(cell_layout(bl * pd, pu * br, K, base, out ? &out->cell : nullptr));
+    double* Rl = ws.take<double>(q * bl * 8);
+    double* Ru = ws.take<double>(q * pu * 8);
+    if (out) { out->Rl = Rl; out->Ru = Ru; }
+    return ws.total();
 }
 
 // ---- in-line two-point functions: a stack of left environments (tnac4o.calculate_correlation_function) -----------------
@@ -343,34 +268,31 @@ int cluster_bond_marginal(hipStream_t st, const double* HL, const double* HR, co
 //   out[(e,r,t'), b']    = Y[(e,r,t'), (b,u)] . Ab[(b,u), b']        ONE launch:  M = (nE + nop) br Dt2, N = Db2, K = Db pu
 // Every slot is divided by the power-of-two nfactor of slot 0 (exact), whose log2 is added to the running total: ratios between
 // slots carry no factor.  No step depends on the number of slots through anything but the batch counts.
-struct Env3StackPlan {
-    int64_t half, y, wq;                  // doubles: first products, second products, permuted operator planes
-    int64_t g1, g2, g2o, g3;              // split-K scratch of the GEMMs
+struct Env3StackWs {
+    double *H, *Y, *Wq, *g, *nf2;         // first products (own_half), second products, permuted operator planes, split-K scratch, [nf, 1/nf]
+    void* scratch;                        // of normalize_pow2
+    int64_t wq;                           // doubles of Wq
+    int64_t g1, g2, g2o, g3;              // bytes of g each GEMM asks for
     bool walk_u;                          // the middle product walks u (pu < br) instead of r
 };
-
-static Env3StackPlan env3_stack_plan(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu,
-                                     int64_t Db, int64_t Db2) {
-    Env3StackPlan p;
-    p.half = nE * bl * pd * Dt2 * Db;
-    p.y = (nE + nop) * br * Dt2 * Db * pu;
-    p.wq = nop * br * bl * pd * pu;
-    p.walk_u = pu < br;
-    p.g1 = gemm_ws_bytes(pd * Dt2, Db, Dt, nE * bl);
-    p.g2 = gemm_ws_bytes(Dt2 * Db, p.walk_u ? br : pu, bl * pd, nE);
-    p.g2o = nop > 0 ? gemm_ws_bytes(Dt2 * Db, pu, bl * pd, nop * br) : 0;
-    p.g3 = gemm_ws_bytes((nE + nop) * br * Dt2, Db2, Db * pu, 1);
-    return p;
-}
-
-static int64_t env3_stack_gemm_ws(const Env3StackPlan& p) {
-    int64_t g = p.g1 > p.g2 ? p.g1 : p.g2;
-    g = g > p.g2o ? g : p.g2o;
-    return g > p.g3 ? g : p.g3;
-}
-
-static int64_t env3_stack_ws(const Env3StackPlan& p, bool own_half) {
-    return (own_half ? up256m(p.half * 8) : 0) + up256m(p.y * 8) + up256m(p.wq * 8) + up256m(env3_stack_gemm_ws(p)) + NF_SCRATCH;
+static int64_t env3_stack_layout(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db,
+                                 int64_t Db2, bool own_half, char* base, Env3StackWs* out) {
+    Env3StackWs w;
+    w.wq = nop * br * bl * pd * pu;
+    w.walk_u = pu < br;
+    w.g1 = gemm_ws_bytes(pd * Dt2, Db, Dt, nE * bl);
+    w.g2 = gemm_ws_bytes(Dt2 * Db, w.walk_u ? br : pu, bl * pd, nE);
+    w.g2o = nop > 0 ? gemm_ws_bytes(Dt2 * Db, pu, bl * pd, nop * br) : 0;
+    w.g3 = gemm_ws_bytes((nE + nop) * br * Dt2, Db2, Db * pu, 1);
+    WsCarve ws{base};
+    w.H = own_half ? ws.take<double>(nE * bl * pd * Dt2 * Db * 8) : nullptr;
+    w.Y = ws.take<double>((nE + nop) * br * Dt2 * Db * pu * 8);
+    w.Wq = ws.take<double>(w.wq * 8);
+    w.g = ws.take<double>(std::max({w.g1, w.g2, w.g2o, w.g3}));
+    w.nf2 = ws.take<double>(256);
+    w.scratch = ws.take(NORMALIZE_SCRATCH_BYTES);
+    if (out) *out = w;
+    return ws.total();
 }
 
 // Wops[1 + a][l][d][r][u] -> Wq[a][r][(l,d)][u]
@@ -386,113 +308,19 @@ __global__ __launch_bounds__(256) void mpo_ops_by_r_kernel(const double* __restr
 
 static bool stack_dims_ok(int64_t nE, int64_t nop) { return nE >= 1 && nop >= 0; }
 
-int64_t env3_stack_ws_bytes(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db,
-                            int64_t Db2, int own_half) {
-    if (!stack_dims_ok(nE, nop) || !dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2)) return 0;
-    return env3_stack_ws(env3_stack_plan(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2), own_half != 0);
-}
-
-int env3_stack(hipStream_t st, const double* E, const double* At, const double* Wops, const double* Ab, int64_t nE, int64_t nop, int64_t Dt,
-               int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out,
-               double* log2nf_out, double* half_out, void* ws, int64_t ws_bytes) {
-    TN_CHECK_ARG(E && At && Wops && Ab && out && log2nf_out && ws, "null operand");
-    TN_CHECK_ARG(stack_dims_ok(nE, nop), "the stack needs at least the plain slot and a non-negative operator count");
-    TN_CHECK_ARG(dims_ok(Dt, pd, Dt2, bl, br, pu, Db, Db2), "non-positive dimension");
-    const Env3StackPlan p = env3_stack_plan(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2);
-    TN_CHECK_ARG(ws_bytes >= env3_stack_ws(p, half_out == nullptr), "workspace too small");
-    char* w = (char*)ws;
-    double* H = half_out;
-    if (!H) { H = (double*)w; w += up256m(p.half * 8); }
-    double* Y = (double*)w;
-    w += up256m(p.y * 8);
-    double* Wq = (double*)w;
-    w += up256m(p.wq * 8);
-    double* g = (double*)w;
-    w += up256m(env3_stack_gemm_ws(p));
-    double* nf2 = (double*)w;
-    void* scratch = w + 256;
-    const int64_t KD = Dt2 * Db, LD = bl * pd, slotY = br * KD * pu, slotO = br * Dt2 * Db2;
-    int rc;
-    // HL[(e,l)][(d,t'), b] = At^T[(d,t'), t] . E[(e,l)][t, b]
-    if ((rc = gemm(st, pd * Dt2, Db, Dt, 1.0, At, 1, pd * Dt2, E, Db, 1, 0.0, H, Db, 1, nE * bl, 0, Dt * Db, pd * KD, p.g1 > 0 ? g : nullptr,
-                   p.g1))) return rc;
-    // Y[e][r][(t',b), u] = HL[e]^T[(t',b), (l,d)] . W0[(l,d), r, u]
-    if (p.walk_u) {
-        for (int64_t u = 0; u < pu; ++u)
-            if ((rc = gemm(st, KD, br, LD, 1.0, H, 1, KD, Wops + u, br * pu, pu, 0.0, Y + u, pu, KD * pu, nE, LD * KD, 0, slotY,
-                           p.g2 > 0 ? g : nullptr, p.g2))) return rc;
-    } else {
-        for (int64_t r = 0; r < br; ++r)
-            if ((rc = gemm(st, KD, pu, LD, 1.0, H, 1, KD, Wops + r * pu, br * pu, 1, 0.0, Y + r * KD * pu, pu, 1, nE, LD * KD, 0, slotY,
-                           p.g2 > 0 ? g : nullptr, p.g2))) return rc;
-    }
-    if (nop > 0) {
-        int64_t nbk = cdiv(p.wq, 256);
-        if (nbk > 1024) nbk = 1024;
-        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(mpo_ops_by_r_kernel, dim3((unsigned)nbk), dim3(256), 0, st, Wops, nop, LD, (int)br, (int)pu, Wq));
-        TN_CHECK_LAUNCH("mpo_ops_by_r_kernel");
-        // Y[nE + a][r][(t',b), u] = HL[0]^T[(t',b), (l,d)] . Wq[a][r][(l,d), u]
-        if ((rc = gemm(st, KD, pu, LD, 1.0, H, 1, KD, Wq, pu, 1, 0.0, Y + nE * slotY, pu, 1, nop * br, 0, LD * pu, KD * pu,
-                       p.g2o > 0 ? g : nullptr, p.g2o))) return rc;
-    }
-    // out[(e,r,t'), b'] = Y[(e,r,t'), (b,u)] . Ab[(b,u), b']
-    if ((rc = gemm(st, (nE + nop) * br * Dt2, Db2, Db * pu, 1.0, Y, Db * pu, 1, Ab, Db2, 1, 0.0, out, Db2, 1, 1, 0, 0, 0, p.g3 > 0 ? g : nullptr,
-                   p.g3))) return rc;
-    if ((rc = normalize_pow2(st, out, slotO, nf2, scratch, 8192))) return rc;
-    if ((rc = scale_by(st, out + slotO, (nE + nop - 1) * slotO, nf2 + 1))) return rc;
-    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(log2_acc_kernel, dim3(1), dim3(64), 0, st, nf2, log2nf_in, log2nf_out));
-    TN_CHECK_LAUNCH("log2_acc_kernel");
-    return 0;
-}
-
 // ---- closing every slot of a stack at one cell -------------------------------------------------------------------------
 //   X[e][l,d,u,r] = sum_K HL[e][(l,d),K] HR[(u,r),K]                 ONE launch:  M = nE bl pd, N = pu br, K = Dt2 Db
 //   D[e][s] = sum_{l,u} F[s,l,u] X[e][l,dmap[s],u,rmap[s]]           raw: no negativity rule, no division
-// One wave per (slot, state), the four waves of a workgroup take four slots of one state (they share the row of F).  Lane i adds
-// the products i, i + 64, ... of the (l,u) plane in that order, then the lanes are added in a butterfly: the order of every sum
-// depends on bl pu alone.  X is read once in all (a chimera cell sends every (d,r) to one state), at the stride of its r index.
+// One wave per (slot, state) runs cell_gather, the four waves of a workgroup take four slots of one state (they share the row of F).
+// X is read once in all (a chimera cell sends every (d,r) to one state), at the stride of its r index.
 __global__ __launch_bounds__(256) void stack_gather_kernel(const double* __restrict__ X, const double* __restrict__ F,
                                                            const int32_t* __restrict__ dmap, const int32_t* __restrict__ rmap, int q, int nE,
                                                            int nl, int pd, int br, int nu, double* __restrict__ D) {
     const int s = blockIdx.x, lane = threadIdx.x & 63;
     const int e = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (e >= nE) return;                                   // whole wave leaves together
-    const int d = dmap[s], r = rmap[s], nlu = nl * nu;
-    double acc = 0.0;
-    if (d >= 0 && d < pd && r >= 0 && r < br) {
-        const double* f = F + (int64_t)s * nlu;
-        const double* x = X + (int64_t)e * nl * pd * nu * br;
-        for (int i = lane; i < nlu; i += 64) {
-            const int l = i / nu, u = i - l * nu;
-            acc += f[i] * x[(((int64_t)l * pd + d) * nu + u) * br + r];
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    const double acc = cell_gather(X + (int64_t)e * nl * pd * nu * br, F + (int64_t)s * nl * nu, dmap[s], rmap[s], nl, pd, br, nu, lane);
     if (lane == 0) D[(int64_t)e * q + s] = acc;
-}
-
-int64_t stack_cell_law_ws_bytes(int64_t nE, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
-    if (!dims_ok(nE, bl, pd, br, pu, K, 1, 1)) return 0;
-    return up256m(nE * bl * pd * pu * br * 8) + up256m(gemm_ws_bytes(nE * bl * pd, pu * br, K, 1));
-}
-
-int stack_cell_law(hipStream_t st, const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
-                   int64_t nE, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, double* D, void* ws, int64_t ws_bytes) {
-    TN_CHECK_ARG(HL && HR && F && dmap && rmap && D && ws, "null operand");
-    TN_CHECK_ARG(dims_ok(q, nE, bl, pd, br, pu, K, 1), "non-positive dimension");
-    TN_CHECK_ARG(q < (int64_t)1 << 31 && cdiv(nE, 4) <= 65535 && bl * pu < (int64_t)1 << 31, "too many states or slots for one launch");
-    TN_CHECK_ARG(ws_bytes >= stack_cell_law_ws_bytes(nE, bl, pd, br, pu, K), "workspace too small");
-    double* X = (double*)ws;
-    const int64_t gb = gemm_ws_bytes(nE * bl * pd, pu * br, K, 1);
-    double* g = (double*)((char*)ws + up256m(nE * bl * pd * pu * br * 8));
-    int rc;
-    // X[(e,l,d), (u,r)] = HL[(e,l,d), K] . HR[(u,r), K]^T
-    if ((rc = gemm(st, nE * bl * pd, pu * br, K, 1.0, HL, K, 1, HR, 1, K, 0.0, X, pu * br, 1, 1, 0, 0, 0, gb > 0 ? g : nullptr, gb))) return rc;
-    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(stack_gather_kernel, dim3((unsigned)q, (unsigned)cdiv(nE, 4)), dim3(256), 0, st, X, F, dmap,
-                                                     rmap, (int)q, (int)nE, (int)bl, (int)pd, (int)br, (int)pu, D));
-    TN_CHECK_LAUNCH("stack_gather_kernel");
-    return 0;
 }
 
 }  // namespace tn
@@ -502,55 +330,175 @@ using namespace tn;
 extern "C" {
 
 int64_t tn_env3_ws_bytes(int side, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2) {
-    return env3_ws_bytes(side, Dt, pd, Dt2, bl, br, pu, Db, Db2);
+    if ((side != 0 && side != 1) || !dims_ok({Dt, pd, Dt2, bl, br, pu, Db, Db2})) return 0;
+    return env3_layout(side, Dt, pd, Dt2, bl, br, pu, Db, Db2, nullptr, nullptr);
 }
 
 int tn_env3(int side, const double* E, const double* At, const double* W, const double* Ab, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl,
             int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out, double* log2nf_out, double* half_out,
             void* ws, int64_t ws_bytes, void* stream) {
-    return env3((hipStream_t)stream, side, E, At, W, Ab, Dt, pd, Dt2, bl, br, pu, Db, Db2, log2nf_in, out, log2nf_out, half_out, ws, ws_bytes);
+    TN_CHECK_ARG(side == 0 || side == 1, "side must be 0 (left step) or 1 (right step)");
+    TN_CHECK_ARG(E && At && W && Ab && out && log2nf_out && ws, "null operand");
+    TN_CHECK_ARG(dims_ok({Dt, pd, Dt2, bl, br, pu, Db, Db2}), "non-positive dimension");
+    Env3Ws w;
+    TN_CHECK_ARG(ws_bytes >= env3_layout(side, Dt, pd, Dt2, bl, br, pu, Db, Db2, (char*)ws, &w), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    double* H = half_out ? half_out : w.H;
+    double* g1 = w.g1 > 0 ? w.g : nullptr;
+    double* g2 = w.g2 > 0 ? w.g : nullptr;
+    double* g3 = w.g3 > 0 ? w.g : nullptr;
+    int rc;
+    if (side == 0) {
+        // HL_l[(d,t'), b] = At^T[(d,t'), t] . EL_l[t, b]
+        if ((rc = gemm(st, pd * Dt2, Db, Dt, 1.0, At, 1, pd * Dt2, E, Db, 1, 0.0, H, Db, 1, bl, 0, Dt * Db, pd * Dt2 * Db, g1, w.g1))) return rc;
+        // Y_r[(t',b), u] = HL^T[(t',b), (l,d)] . W_r[(l,d), u]
+        if ((rc = gemm(st, Dt2 * Db, pu, bl * pd, 1.0, H, 1, Dt2 * Db, W, br * pu, 1, 0.0, w.Y, pu, 1, br, 0, pu, Dt2 * Db * pu, g2, w.g2)))
+            return rc;
+        // EL'[(r,t'), b'] = Y[(r,t'), (b,u)] . Ab[(b,u), b']
+        if ((rc = gemm(st, br * Dt2, Db2, Db * pu, 1.0, w.Y, Db * pu, 1, Ab, Db2, 1, 0.0, out, Db2, 1, 1, 0, 0, 0, g3, w.g3))) return rc;
+        if ((rc = normalize_pow2(st, out, br * Dt2 * Db2, w.nf2, w.scratch, NORMALIZE_SCRATCH_BYTES))) return rc;
+    } else {
+        // HR_u[(r,t'), b] = ER[(r,t'), b'] . Ab_u[b', b]     (Ab_u[b', b] = Ab[b, u, b'])
+        if ((rc = gemm(st, br * Dt2, Db, Db2, 1.0, E, Db2, 1, Ab, 1, pu * Db2, 0.0, H, Db, 1, pu, 0, Db2, br * Dt2 * Db, g1, w.g1))) return rc;
+        const int64_t nw = bl * pd * pu * br;
+        int64_t nbk = cdiv(nw, 256);
+        if (nbk > 1024) nbk = 1024;
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(mpo_swap_ru_kernel, dim3((unsigned)nbk), dim3(256), 0, st, W, bl * pd, (int)br, (int)pu, w.Wp));
+        TN_CHECK_LAUNCH("mpo_swap_ru_kernel");
+        // Y[(l,d), (t',b)] = W'[(l,d), (u,r)] . HR[(u,r), (t',b)]
+        if ((rc = gemm(st, bl * pd, Dt2 * Db, pu * br, 1.0, w.Wp, pu * br, 1, H, Dt2 * Db, 1, 0.0, w.Y, Dt2 * Db, 1, 1, 0, 0, 0, g2, w.g2))) return rc;
+        // ER_l[t, b] = At[t, (d,t')] . Y_l[(d,t'), b]
+        if ((rc = gemm(st, Dt, Db, pd * Dt2, 1.0, At, pd * Dt2, 1, w.Y, Db, 1, 0.0, out, Db, 1, bl, 0, pd * Dt2 * Db, Dt * Db, g3, w.g3))) return rc;
+        if ((rc = normalize_pow2(st, out, bl * Dt * Db, w.nf2, w.scratch, NORMALIZE_SCRATCH_BYTES))) return rc;
+    }
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(log2_acc_kernel, dim3(1), dim3(64), 0, st, w.nf2, log2nf_in, log2nf_out));
+    TN_CHECK_LAUNCH("log2_acc_kernel");
+    return 0;
 }
 
 int64_t tn_cluster_marginal_ws_bytes(int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
-    return cluster_marginal_ws_bytes(bl, pd, br, pu, K);
+    if (!dims_ok({bl, pd, br, pu, K})) return 0;
+    return cell_layout(bl * pd, pu * br, K, nullptr, nullptr);
 }
 
 int tn_cluster_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t bl,
                         int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* P, double* minP,
                         double* log2z, void* ws, int64_t ws_bytes, void* stream) {
-    return cluster_marginal((hipStream_t)stream, HL, HR, F, dmap, rmap, q, bl, pd, br, pu, K, log2L, log2R, P, minP, log2z, ws, ws_bytes);
+    TN_CHECK_ARG(HL && HR && F && dmap && rmap && P && minP && log2z && ws, "null operand");
+    TN_CHECK_ARG(dims_ok({q, bl, pd, br, pu, K}), "non-positive dimension");
+    TN_CHECK_ARG(q <= CM_QMAX, "more than 16384 cell states");
+    CellWs w;
+    TN_CHECK_ARG(ws_bytes >= cell_layout(bl * pd, pu * br, K, (char*)ws, &w), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = cell_product(st, HL, HR, bl * pd, pu * br, K, w))) return rc;
+    const size_t lds = (size_t)q * 8;
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)cluster_marginal_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(cluster_marginal_kernel, dim3(1), dim3(256), lds, st, w.X, F, dmap, rmap, (int)q, (int)bl,
+                                                     (int)pd, (int)br, (int)pu, log2L, log2R, P, minP, log2z));
+    TN_CHECK_LAUNCH("cluster_marginal_kernel");
+    return 0;
 }
 
 int64_t tn_cluster_bond_marginal_ws_bytes(int64_t q, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
-    return cluster_bond_marginal_ws_bytes(q, bl, pd, br, pu, K);
+    if (!dims_ok({q, bl, pd, br, pu, K})) return 0;
+    return bond_layout(q, bl, pd, br, pu, K, nullptr, nullptr);
 }
 
 int tn_cluster_bond_marginal(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q,
                              int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, const double* log2L, const double* log2R, double* Pl,
                              double* Pu, double* minB, double* log2z, void* ws, int64_t ws_bytes, void* stream) {
-    return cluster_bond_marginal((hipStream_t)stream, HL, HR, F, dmap, rmap, q, bl, pd, br, pu, K, log2L, log2R, Pl, Pu, minB, log2z, ws,
-                                 ws_bytes);
+    TN_CHECK_ARG(HL && HR && F && dmap && rmap && Pl && Pu && minB && log2z && ws, "null operand");
+    TN_CHECK_ARG(dims_ok({q, bl, pd, br, pu, K}), "non-positive dimension");
+    TN_CHECK_ARG(q <= CM_QMAX, "more than 16384 cell states");
+    BondWs w;
+    TN_CHECK_ARG(ws_bytes >= bond_layout(q, bl, pd, br, pu, K, (char*)ws, &w), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = cell_product(st, HL, HR, bl * pd, pu * br, K, w.cell))) return rc;
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(bond_gather_kernel, dim3((unsigned)q), dim3(256), 0, st, w.cell.X, F, dmap, rmap, (int)bl,
+                                                     (int)pd, (int)br, (int)pu, w.Rl, w.Ru));
+    TN_CHECK_LAUNCH("bond_gather_kernel");
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(bond_finish_kernel, dim3(1), dim3(256), 0, st, w.Rl, w.Ru, q * bl, q * pu, log2L, log2R,
+                                                     Pl, Pu, minB, log2z));
+    TN_CHECK_LAUNCH("bond_finish_kernel");
+    return 0;
 }
 
 int64_t tn_env3_stack_ws_bytes(int64_t nE, int64_t nop, int64_t Dt, int64_t pd, int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db,
                                int64_t Db2, int own_half) {
-    return env3_stack_ws_bytes(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2, own_half);
+    if (!stack_dims_ok(nE, nop) || !dims_ok({Dt, pd, Dt2, bl, br, pu, Db, Db2})) return 0;
+    return env3_stack_layout(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2, own_half != 0, nullptr, nullptr);
 }
 
 int tn_env3_stack(const double* E, const double* At, const double* Wops, const double* Ab, int64_t nE, int64_t nop, int64_t Dt, int64_t pd,
                   int64_t Dt2, int64_t bl, int64_t br, int64_t pu, int64_t Db, int64_t Db2, const double* log2nf_in, double* out,
                   double* log2nf_out, double* half_out, void* ws, int64_t ws_bytes, void* stream) {
-    return env3_stack((hipStream_t)stream, E, At, Wops, Ab, nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2, log2nf_in, out, log2nf_out, half_out, ws,
-                      ws_bytes);
+    TN_CHECK_ARG(E && At && Wops && Ab && out && log2nf_out && ws, "null operand");
+    TN_CHECK_ARG(stack_dims_ok(nE, nop), "the stack needs at least the plain slot and a non-negative operator count");
+    TN_CHECK_ARG(dims_ok({Dt, pd, Dt2, bl, br, pu, Db, Db2}), "non-positive dimension");
+    Env3StackWs w;
+    TN_CHECK_ARG(ws_bytes >= env3_stack_layout(nE, nop, Dt, pd, Dt2, bl, br, pu, Db, Db2, half_out == nullptr, (char*)ws, &w),
+                 "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    double* H = half_out ? half_out : w.H;
+    double* g1 = w.g1 > 0 ? w.g : nullptr;
+    double* g2 = w.g2 > 0 ? w.g : nullptr;
+    double* g2o = w.g2o > 0 ? w.g : nullptr;
+    double* g3 = w.g3 > 0 ? w.g : nullptr;
+    double* Y = w.Y;
+    const int64_t KD = Dt2 * Db, LD = bl * pd, slotY = br * KD * pu, slotO = br * Dt2 * Db2;
+    int rc;
+    // HL[(e,l)][(d,t'), b] = At^T[(d,t'), t] . E[(e,l)][t, b]
+    if ((rc = gemm(st, pd * Dt2, Db, Dt, 1.0, At, 1, pd * Dt2, E, Db, 1, 0.0, H, Db, 1, nE * bl, 0, Dt * Db, pd * KD, g1, w.g1))) return rc;
+    // Y[e][r][(t',b), u] = HL[e]^T[(t',b), (l,d)] . W0[(l,d), r, u]
+    if (w.walk_u) {
+        for (int64_t u = 0; u < pu; ++u)
+            if ((rc = gemm(st, KD, br, LD, 1.0, H, 1, KD, Wops + u, br * pu, pu, 0.0, Y + u, pu, KD * pu, nE, LD * KD, 0, slotY, g2, w.g2)))
+                return rc;
+    } else {
+        for (int64_t r = 0; r < br; ++r)
+            if ((rc = gemm(st, KD, pu, LD, 1.0, H, 1, KD, Wops + r * pu, br * pu, 1, 0.0, Y + r * KD * pu, pu, 1, nE, LD * KD, 0, slotY, g2, w.g2)))
+                return rc;
+    }
+    if (nop > 0) {
+        int64_t nbk = cdiv(w.wq, 256);
+        if (nbk > 1024) nbk = 1024;
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(mpo_ops_by_r_kernel, dim3((unsigned)nbk), dim3(256), 0, st, Wops, nop, LD, (int)br, (int)pu, w.Wq));
+        TN_CHECK_LAUNCH("mpo_ops_by_r_kernel");
+        // Y[nE + a][r][(t',b), u] = HL[0]^T[(t',b), (l,d)] . Wq[a][r][(l,d), u]
+        if ((rc = gemm(st, KD, pu, LD, 1.0, H, 1, KD, w.Wq, pu, 1, 0.0, Y + nE * slotY, pu, 1, nop * br, 0, LD * pu, KD * pu, g2o, w.g2o)))
+            return rc;
+    }
+    // out[(e,r,t'), b'] = Y[(e,r,t'), (b,u)] . Ab[(b,u), b']
+    if ((rc = gemm(st, (nE + nop) * br * Dt2, Db2, Db * pu, 1.0, Y, Db * pu, 1, Ab, Db2, 1, 0.0, out, Db2, 1, 1, 0, 0, 0, g3, w.g3))) return rc;
+    if ((rc = normalize_pow2(st, out, slotO, w.nf2, w.scratch, NORMALIZE_SCRATCH_BYTES))) return rc;
+    if ((rc = scale_by(st, out + slotO, (nE + nop - 1) * slotO, w.nf2 + 1))) return rc;
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(log2_acc_kernel, dim3(1), dim3(64), 0, st, w.nf2, log2nf_in, log2nf_out));
+    TN_CHECK_LAUNCH("log2_acc_kernel");
+    return 0;
 }
 
 int64_t tn_stack_cell_law_ws_bytes(int64_t nE, int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K) {
-    return stack_cell_law_ws_bytes(nE, bl, pd, br, pu, K);
+    if (!dims_ok({nE, bl, pd, br, pu, K})) return 0;
+    return cell_layout(nE * bl * pd, pu * br, K, nullptr, nullptr);
 }
 
 int tn_stack_cell_law(const double* HL, const double* HR, const double* F, const int32_t* dmap, const int32_t* rmap, int64_t q, int64_t nE,
                       int64_t bl, int64_t pd, int64_t br, int64_t pu, int64_t K, double* D, void* ws, int64_t ws_bytes, void* stream) {
-    return stack_cell_law((hipStream_t)stream, HL, HR, F, dmap, rmap, q, nE, bl, pd, br, pu, K, D, ws, ws_bytes);
+    TN_CHECK_ARG(HL && HR && F && dmap && rmap && D && ws, "null operand");
+    TN_CHECK_ARG(dims_ok({q, nE, bl, pd, br, pu, K}), "non-positive dimension");
+    TN_CHECK_ARG(q < (int64_t)1 << 31 && cdiv(nE, 4) <= 65535 && bl * pu < (int64_t)1 << 31, "too many states or slots for one launch");
+    CellWs w;
+    TN_CHECK_ARG(ws_bytes >= cell_layout(nE * bl * pd, pu * br, K, (char*)ws, &w), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = cell_product(st, HL, HR, nE * bl * pd, pu * br, K, w))) return rc;
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(stack_gather_kernel, dim3((unsigned)q, (unsigned)cdiv(nE, 4)), dim3(256), 0, st, w.X, F, dmap,
+                                                     rmap, (int)q, (int)nE, (int)bl, (int)pd, (int)br, (int)pu, D));
+    TN_CHECK_LAUNCH("stack_gather_kernel");
+    return 0;
 }
 
 }  // extern "C"

@@ -725,24 +725,23 @@ struct QrWs {
 
 static int64_t qr_layout(int64_t m, int64_t n, int nb, char* base, QrWs* w) {
     const int64_t k = m < n ? m : n, P = cdiv(k, nb);
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { int64_t o = off; off += align_up(bytes, 256); return base ? base + o : nullptr; };
-    double* Y = (double*)take(m * k * 8);
-    double* Wq = (double*)take(m * k * 8);            // Y T of every panel (Q accumulation)
-    double* Wp = (double*)take(m * nb * 8);           // Y T^T of the current panel (trailing update)
-    double* UT = (double*)take((int64_t)nb * nb * 8);
-    double* UTq = (double*)take((int64_t)nb * nb * 8);
-    double* T = (double*)take(P * nb * nb * 8);
-    double* X = (double*)take((int64_t)nb * (n > k ? n : k) * 8);
-    double* part = (double*)take((int64_t)64 * nb * nb * 8);
-    double* Js = (double*)take((int64_t)nb * nb * 8);
-    double* Uinv = (double*)take((int64_t)nb * nb * 8);
-    double* Z = (double*)take(P * nb * nb * 8);
-    double* Tri = (double*)take(P * nb * nb * 8);
-    int* dead = (int*)take(nb * 4);
-    double* cn = (double*)take(2 * n * 8);            // column norms^2: [input | current trailing block]
-    int* pairs = (int*)take((int64_t)2 * nb * 4);
-    char* piv = (char*)take(1024 + n * 4);           // PivState | permutation (int) of the device-side panel pivoting
+    WsCarve ws{base};
+    double* Y = ws.take<double>(m * k * 8);
+    double* Wq = ws.take<double>(m * k * 8);            // Y T of every panel (Q accumulation)
+    double* Wp = ws.take<double>(m * nb * 8);           // Y T^T of the current panel (trailing update)
+    double* UT = ws.take<double>((int64_t)nb * nb * 8);
+    double* UTq = ws.take<double>((int64_t)nb * nb * 8);
+    double* T = ws.take<double>(P * nb * nb * 8);
+    double* X = ws.take<double>((int64_t)nb * (n > k ? n : k) * 8);
+    double* part = ws.take<double>((int64_t)64 * nb * nb * 8);
+    double* Js = ws.take<double>((int64_t)nb * nb * 8);
+    double* Uinv = ws.take<double>((int64_t)nb * nb * 8);
+    double* Z = ws.take<double>(P * nb * nb * 8);
+    double* Tri = ws.take<double>(P * nb * nb * 8);
+    int* dead = ws.take<int>(nb * 4);
+    double* cn = ws.take<double>(2 * n * 8);            // column norms^2: [input | current trailing block]
+    int* pairs = ws.take<int>((int64_t)2 * nb * 4);
+    char* piv = ws.take<char>(1024 + n * 4);           // PivState | permutation (int) of the device-side panel pivoting
     // split-K scratch for the tall TN products (b x n, K = m)
     int64_t gw = (int64_t)64 * nb * (n > k ? n : k) * 8;      // upper bound of pick_splitk's partial buffers
     {   // ... and of the outer-block products (NBO x n', K = m) of the two-level path: pick_splitk asks for about 512 tiles of
@@ -751,23 +750,23 @@ static int64_t qr_layout(int64_t m, int64_t n, int nb, char* base, QrWs* w) {
         const int64_t g2 = (512 + 2 * tiles) * 128 * 128 * 8;
         if (g2 > gw) gw = g2;
     }
-    double* gws = (double*)take(gw + 256);
+    double* gws = ws.take<double>(gw + 256);
     // two-level blocking: Gram of an outer block, its merged T factors (one per block), the two (NBO x n) operands of the
     // outer update and a scratch for the T recurrence
     const int64_t nblk_o = cdiv(k, QR_NBO_MAX / 2);           // enough for the narrowest outer width used (128)
-    double* Gm = (double*)take((int64_t)QR_NBO_MAX * QR_NBO_MAX * 8);
-    double* Tblk = (double*)take(nblk_o * QR_NBO_MAX * QR_NBO_MAX * 8);
-    double* Zb = (double*)take((int64_t)QR_NBO_MAX * (n > k ? n : k) * 8);
-    double* Zb2 = (double*)take((int64_t)QR_NBO_MAX * (n > k ? n : k) * 8);
-    double* tmpT = (double*)take((int64_t)QR_NBO_MAX * 64 * 8);
+    double* Gm = ws.take<double>((int64_t)QR_NBO_MAX * QR_NBO_MAX * 8);
+    double* Tblk = ws.take<double>(nblk_o * QR_NBO_MAX * QR_NBO_MAX * 8);
+    double* Zb = ws.take<double>((int64_t)QR_NBO_MAX * (n > k ? n : k) * 8);
+    double* Zb2 = ws.take<double>((int64_t)QR_NBO_MAX * (n > k ? n : k) * 8);
+    double* tmpT = ws.take<double>((int64_t)QR_NBO_MAX * 64 * 8);
     if (w) { w->G = Gm; w->Tblk = Tblk; w->Zo = Zb; w->Zo2 = Zb2; w->tmpT = tmpT; }
     const int64_t pb = cholqr_ws_bytes(m, nb < 32 ? nb : 32);
-    void* pw = (void*)take(pb);
+    void* pw = ws.take(pb);
     if (w) { w->panel_ws = pw; w->panel_bytes = pb; }
     if (w) { w->Wq = Wq; w->W = Wp; w->UT = UT; w->UTq = UTq; }
     if (w) { w->Y = Y; w->T = T; w->X = X; w->part = part; w->Js = Js; w->Uinv = Uinv; w->Z = Z; w->Tri = Tri;
              w->dead = dead; w->gemm_ws = gws; w->gemm_ws_bytes = gw; w->cn = cn; w->pairs = pairs; w->piv = piv; }
-    return off;
+    return ws.total();
 }
 
 int64_t qr_ws_bytes(int64_t m, int64_t n, int nb) { return qr_layout(m, n, nb, nullptr, nullptr); }

@@ -14,121 +14,133 @@
 
 namespace tn {
 
-static inline int64_t up256(int64_t b) { return align_up(b, 256); }
-
 // ---- attach + QR + nfactor ---------------------------------------------------------------------------------------------
 // side 0: M = C (kc x Dl) . A (Dl x p Dr), factored as the (kc p) x Dr matrix  -> Q (kc p x k), R (k x Dr), both row-major
 // side 1: M = A (Dl p x Dr) . C (Dr x kc), factored through its transposed (p kc) x Dl view -> Qt (k x p kc) = Q^T, Ct (Dl x k) = R^T
 // C == nullptr: no attach, A itself is factored (and destroyed); kc is then ignored (kc = Dl resp. Dr).
-struct SiteQrDims { int64_t m, n, k, tmp, rows_l, cols_l; };
+struct SiteQrDims { int64_t m, n, k, tmp; };
 static SiteQrDims site_qr_dims(int side, int64_t Dl, int64_t p, int64_t Dr, int64_t kc, bool attach) {
     SiteQrDims d;
     if (side == 0) { const int64_t l = attach ? kc : Dl; d.m = l * p; d.n = Dr; d.tmp = attach ? l * p * Dr : 0; }
     else { const int64_t r = attach ? kc : Dr; d.m = p * r; d.n = Dl; d.tmp = attach ? Dl * p * r : 0; }
     d.k = d.m < d.n ? d.m : d.n;
-    d.rows_l = 0; d.cols_l = 0;
     return d;
 }
 
-int64_t site_qr_ws_bytes(int side, int64_t Dl, int64_t p, int64_t Dr, int64_t kc, int attach) {
-    const SiteQrDims d = site_qr_dims(side, Dl, p, Dr, kc, attach != 0);
-    int64_t g = 0;
-    if (attach) g = side == 0 ? gemm_ws_bytes(kc, p * Dr, Dl, 1) : gemm_ws_bytes(Dl * p, kc, Dr, 1);
-    return up256(d.tmp * 8) + up256(g) + up256(qr_ws_bytes(d.m, d.n, 32)) + 8192;
+// workspace: attached site M (attach only) | split-K scratch of the attach product (attach only) | qr_factor | normalize_pow2
+struct SiteQrWs { SiteQrDims d; double *M, *gws; int64_t g; void* qw; int64_t qws; void* nf_scratch; };     // g, qws: bytes of gws, qw
+static int64_t site_qr_layout(int side, int64_t Dl, int64_t p, int64_t Dr, int64_t kc, bool attach, char* base, SiteQrWs* out) {
+    const SiteQrDims d = site_qr_dims(side, Dl, p, Dr, kc, attach);
+    const int64_t g = !attach ? 0 : side == 0 ? gemm_ws_bytes(kc, p * Dr, Dl, 1) : gemm_ws_bytes(Dl * p, kc, Dr, 1);
+    const int64_t qws = qr_ws_bytes(d.m, d.n, 32);            // (a sum of 256-byte regions itself)
+    WsCarve ws{base};
+    double* M = ws.take<double>(d.tmp * 8);
+    double* gws = ws.take<double>(g);
+    void* qw = ws.take(qws);
+    void* nf_scratch = ws.take(NORMALIZE_SCRATCH_BYTES);
+    if (out) *out = SiteQrWs{d, M, gws, g, qw, qws, nf_scratch};
+    return ws.total();
 }
-
+int64_t site_qr_ws_bytes(int side, int64_t Dl, int64_t p, int64_t Dr, int64_t kc, int attach) {
+    return site_qr_layout(side, Dl, p, Dr, kc, attach != 0, nullptr, nullptr);
+}
 int site_qr(hipStream_t st, int side, double* A, int64_t Dl, int64_t p, int64_t Dr, const double* C, int64_t kc, double* Q, double* R,
             double rank_tol, int64_t* keff_host, double* nf_out2, int* normalised_host, void* ws, int64_t ws_bytes,
             double* dropped2_host, int frob_exit, int64_t* pivot_perm_host) {
     TN_CHECK_ARG(side == 0 || side == 1, "side must be 0 (left sweep) or 1 (right sweep)");
     TN_CHECK_ARG(Dl >= 1 && p >= 1 && Dr >= 1 && (C == nullptr || kc >= 1), "non-positive dimension");
     const bool attach = C != nullptr;
-    TN_CHECK_ARG(ws_bytes >= site_qr_ws_bytes(side, Dl, p, Dr, kc, attach ? 1 : 0), "workspace too small");
-    const SiteQrDims d = site_qr_dims(side, Dl, p, Dr, kc, attach);
-    char* w = (char*)ws;
+    SiteQrWs w;
+    TN_CHECK_ARG(ws_bytes >= site_qr_layout(side, Dl, p, Dr, kc, attach, (char*)ws, &w), "workspace too small");
+    const SiteQrDims& d = w.d;
     double* M = A;
     int rc;
     if (attach) {
-        M = (double*)w;
-        w += up256(d.tmp * 8);
-        const int64_t g = side == 0 ? gemm_ws_bytes(kc, p * Dr, Dl, 1) : gemm_ws_bytes(Dl * p, kc, Dr, 1);
-        double* gws = g > 0 ? (double*)w : nullptr;
-        w += up256(g);
-        if (side == 0) rc = gemm(st, kc, p * Dr, Dl, 1.0, C, Dl, 1, A, p * Dr, 1, 0.0, M, p * Dr, 1, 1, 0, 0, 0, gws, g);
-        else rc = gemm(st, Dl * p, kc, Dr, 1.0, A, Dr, 1, C, kc, 1, 0.0, M, kc, 1, 1, 0, 0, 0, gws, g);
+        M = w.M;
+        double* gws = w.g > 0 ? w.gws : nullptr;
+        if (side == 0) rc = gemm(st, kc, p * Dr, Dl, 1.0, C, Dl, 1, A, p * Dr, 1, 0.0, M, p * Dr, 1, 1, 0, 0, 0, gws, w.g);
+        else rc = gemm(st, Dl * p, kc, Dr, 1.0, A, Dr, 1, C, kc, 1, 0.0, M, kc, 1, 1, 0, 0, 0, gws, w.g);
         if (rc) return rc;
     }
-    const int64_t qws = up256(qr_ws_bytes(d.m, d.n, 32));
-    void* qw = w;
-    w += qws;
     int64_t keff = d.k;
     int nf_done = 0;
     {
         ProfPhase ph(PH_QR);
         prof_note_qr(d.m, d.n, 1);
         if (side == 0)      // M (m x n) row-major; Q (m x k) row-major; R (k x n) row-major
-            rc = qr_factor(st, M, d.n, 1, d.m, d.n, Q, d.k, 1, R, d.n, 1, 32, qw, qws, rank_tol, &keff, dropped2_host, frob_exit, pivot_perm_host,
+            rc = qr_factor(st, M, d.n, 1, d.m, d.n, Q, d.k, 1, R, d.n, 1, 32, w.qw, w.qws, rank_tol, &keff, dropped2_host, frob_exit, pivot_perm_host,
                            nf_out2, &nf_done);
         else                // the (p r) x Dl view of the row-major (Dl, p r) array; Q = Qt^T, R = Ct^T
-            rc = qr_factor(st, M, 1, d.m, d.m, d.n, Q, 1, d.m, R, 1, d.k, 32, qw, qws, rank_tol, &keff, dropped2_host, frob_exit, pivot_perm_host,
+            rc = qr_factor(st, M, 1, d.m, d.m, d.n, Q, 1, d.m, R, 1, d.k, 32, w.qw, w.qws, rank_tol, &keff, dropped2_host, frob_exit, pivot_perm_host,
                            nf_out2, &nf_done);
     }
     if (rc) return rc;
     if (keff_host) *keff_host = keff;
     int normalised = nf_done;            // (the one-launch factorisation divides R by its norm factor itself)
     if (!normalised && nf_out2 && keff == d.k) {      // the triangular factor is complete and contiguous: C = R / nfactor(R) (mps.py:781-782, 796-797)
-        if ((rc = normalize_pow2(st, R, d.k * d.n, nf_out2, w, 8192))) return rc;
+        if ((rc = normalize_pow2(st, R, d.k * d.n, nf_out2, w.nf_scratch, NORMALIZE_SCRATCH_BYTES))) return rc;
         normalised = 1;
     }
     if (normalised_host) *normalised_host = normalised;
     return 0;
 }
 
-// ---- RL . A . RR -------------------------------------------------------------------------------------------------------
-int64_t rar_ws_bytes(int64_t c, int64_t a, int64_t s, int64_t a2, int64_t c2) {
-    const int64_t g1 = gemm_ws_bytes(c, s * a2, a, 1), g2 = gemm_ws_bytes(c * s, c2, a2, 1);
-    return up256(c * s * a2 * 8) + up256(g1 > g2 ? g1 : g2);
+// ---- the steps made of two products ------------------------------------------------------------------------------------
+// workspace: temporary T between the products (t doubles) | split-K scratch shared by the two (g1 resp. g2 bytes of it)
+struct TwoGemmWs {
+    double *T, *gws;
+    int64_t g1, g2;
+    double* gws1() const { return g1 > 0 ? gws : nullptr; }       // (a product that asks for no scratch gets none)
+    double* gws2() const { return g2 > 0 ? gws : nullptr; }
+};
+static int64_t two_gemm_layout(int64_t t, int64_t g1, int64_t g2, char* base, TwoGemmWs* out) {
+    WsCarve ws{base};
+    double* T = ws.take<double>(t * 8);
+    double* gws = ws.take<double>(g1 > g2 ? g1 : g2);
+    if (out) *out = TwoGemmWs{T, gws, g1, g2};
+    return ws.total();
 }
+
+// ---- RL . A . RR -------------------------------------------------------------------------------------------------------
+static int64_t rar_layout(int64_t c, int64_t a, int64_t s, int64_t a2, int64_t c2, char* base, TwoGemmWs* out) {
+    return two_gemm_layout(c * s * a2, gemm_ws_bytes(c, s * a2, a, 1), gemm_ws_bytes(c * s, c2, a2, 1), base, out);
+}
+int64_t rar_ws_bytes(int64_t c, int64_t a, int64_t s, int64_t a2, int64_t c2) { return rar_layout(c, a, s, a2, c2, nullptr, nullptr); }
 int rar(hipStream_t st, const double* RL, const double* A, const double* RR, int64_t c, int64_t a, int64_t s, int64_t a2, int64_t c2,
         double* out, void* ws, int64_t ws_bytes) {
     TN_CHECK_ARG(c >= 1 && a >= 1 && s >= 1 && a2 >= 1 && c2 >= 1, "non-positive dimension");
-    TN_CHECK_ARG(ws_bytes >= rar_ws_bytes(c, a, s, a2, c2), "workspace too small");
-    double* T = (double*)ws;
-    double* gws = (double*)((char*)ws + up256(c * s * a2 * 8));
-    const int64_t g1 = gemm_ws_bytes(c, s * a2, a, 1), g2 = gemm_ws_bytes(c * s, c2, a2, 1);
+    TwoGemmWs w;
+    TN_CHECK_ARG(ws_bytes >= rar_layout(c, a, s, a2, c2, (char*)ws, &w), "workspace too small");
     int rc;
-    if ((rc = gemm(st, c, s * a2, a, 1.0, RL, a, 1, A, s * a2, 1, 0.0, T, s * a2, 1, 1, 0, 0, 0, g1 > 0 ? gws : nullptr, g1))) return rc;
-    return gemm(st, c * s, c2, a2, 1.0, T, a2, 1, RR, c2, 1, 0.0, out, c2, 1, 1, 0, 0, 0, g2 > 0 ? gws : nullptr, g2);
+    if ((rc = gemm(st, c, s * a2, a, 1.0, RL, a, 1, A, s * a2, 1, 0.0, w.T, s * a2, 1, 1, 0, 0, 0, w.gws1(), w.g1))) return rc;
+    return gemm(st, c * s, c2, a2, 1.0, w.T, a2, 1, RR, c2, 1, 0.0, out, c2, 1, 1, 0, 0, 0, w.gws2(), w.g2);
 }
 
 // ---- mixed environments ------------------------------------------------------------------------------------------------
 // side 0 (left):  out[c2, a2] = sum_{c,s,a} Ac[c,s,c2] R[c,a] A[a,s,a2]       R: (c x a)
 // side 1 (right): out[a, c]   = sum_{s,a2,c2} A[a,s,a2] R[a2,c2] Ac[c,s,c2]   R: (a2 x c2)
+static int64_t env_mix_layout(int side, int64_t a, int64_t s, int64_t a2, int64_t c, int64_t c2, char* base, TwoGemmWs* out) {
+    if (side == 0) return two_gemm_layout(c * s * a2, gemm_ws_bytes(c, s * a2, a, 1), gemm_ws_bytes(c2, a2, c * s, 1), base, out);
+    return two_gemm_layout(a * s * c2, gemm_ws_bytes(a * s, c2, a2, 1), gemm_ws_bytes(a, c, s * c2, 1), base, out);
+}
 int64_t env_mix_ws_bytes(int side, int64_t a, int64_t s, int64_t a2, int64_t c, int64_t c2) {
-    int64_t t, g1, g2;
-    if (side == 0) { t = c * s * a2; g1 = gemm_ws_bytes(c, s * a2, a, 1); g2 = gemm_ws_bytes(c2, a2, c * s, 1); }
-    else { t = a * s * c2; g1 = gemm_ws_bytes(a * s, c2, a2, 1); g2 = gemm_ws_bytes(a, c, s * c2, 1); }
-    return up256(t * 8) + up256(g1 > g2 ? g1 : g2);
+    return env_mix_layout(side, a, s, a2, c, c2, nullptr, nullptr);
 }
 int env_mix(hipStream_t st, int side, const double* R, const double* A, const double* Ac, int64_t a, int64_t s, int64_t a2, int64_t c,
             int64_t c2, double* out, void* ws, int64_t ws_bytes) {
     TN_CHECK_ARG(side == 0 || side == 1, "side must be 0 (left) or 1 (right)");
     TN_CHECK_ARG(a >= 1 && s >= 1 && a2 >= 1 && c >= 1 && c2 >= 1, "non-positive dimension");
-    TN_CHECK_ARG(ws_bytes >= env_mix_ws_bytes(side, a, s, a2, c, c2), "workspace too small");
-    double* T = (double*)ws;
+    TwoGemmWs w;
+    TN_CHECK_ARG(ws_bytes >= env_mix_layout(side, a, s, a2, c, c2, (char*)ws, &w), "workspace too small");
     int rc;
     if (side == 0) {
-        double* gws = (double*)((char*)ws + up256(c * s * a2 * 8));
-        const int64_t g1 = gemm_ws_bytes(c, s * a2, a, 1), g2 = gemm_ws_bytes(c2, a2, c * s, 1);
-        if ((rc = gemm(st, c, s * a2, a, 1.0, R, a, 1, A, s * a2, 1, 0.0, T, s * a2, 1, 1, 0, 0, 0, g1 > 0 ? gws : nullptr, g1))) return rc;
+        if ((rc = gemm(st, c, s * a2, a, 1.0, R, a, 1, A, s * a2, 1, 0.0, w.T, s * a2, 1, 1, 0, 0, 0, w.gws1(), w.g1))) return rc;
         // out = Ac(c s, c2)^T . T(c s, a2)
-        return gemm(st, c2, a2, c * s, 1.0, Ac, 1, c2, T, a2, 1, 0.0, out, a2, 1, 1, 0, 0, 0, g2 > 0 ? gws : nullptr, g2);
+        return gemm(st, c2, a2, c * s, 1.0, Ac, 1, c2, w.T, a2, 1, 0.0, out, a2, 1, 1, 0, 0, 0, w.gws2(), w.g2);
     }
-    double* gws = (double*)((char*)ws + up256(a * s * c2 * 8));
-    const int64_t g1 = gemm_ws_bytes(a * s, c2, a2, 1), g2 = gemm_ws_bytes(a, c, s * c2, 1);
-    if ((rc = gemm(st, a * s, c2, a2, 1.0, A, a2, 1, R, c2, 1, 0.0, T, c2, 1, 1, 0, 0, 0, g1 > 0 ? gws : nullptr, g1))) return rc;
+    if ((rc = gemm(st, a * s, c2, a2, 1.0, A, a2, 1, R, c2, 1, 0.0, w.T, c2, 1, 1, 0, 0, 0, w.gws1(), w.g1))) return rc;
     // out = T(a, s c2) . Ac(c, s c2)^T
-    return gemm(st, a, c, s * c2, 1.0, T, s * c2, 1, Ac, 1, s * c2, 0.0, out, c, 1, 1, 0, 0, 0, g2 > 0 ? gws : nullptr, g2);
+    return gemm(st, a, c, s * c2, 1.0, w.T, s * c2, 1, Ac, 1, s * c2, 0.0, out, c, 1, 1, 0, 0, 0, w.gws2(), w.g2);
 }
 
 // ---- projectors of a truncation ----------------------------------------------------------------------------------------
@@ -136,19 +148,21 @@ __global__ __launch_bounds__(256) void diag_from_vec_kernel(const double* __rest
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e < k * k) D[e] = (e / k == e % k) ? S[e / k] : 0.0;
 }
+static int64_t apply_truncation_layout(int64_t ml, int64_t k0, int64_t keep, int64_t k1, int64_t nr, char* base, TwoGemmWs* out) {
+    return two_gemm_layout(0, gemm_ws_bytes(ml, keep, k0, 1), gemm_ws_bytes(keep, nr, k1, 1), base, out);      // (no temporary)
+}
 int64_t apply_truncation_ws_bytes(int64_t ml, int64_t k0, int64_t keep, int64_t k1, int64_t nr) {
-    const int64_t g1 = gemm_ws_bytes(ml, keep, k0, 1), g2 = gemm_ws_bytes(keep, nr, k1, 1);
-    return up256(g1 > g2 ? g1 : g2);
+    return apply_truncation_layout(ml, k0, keep, k1, nr, nullptr, nullptr);
 }
 int apply_truncation(hipStream_t st, const double* Al, int64_t ml, int64_t k0, const double* U, int64_t urs, int64_t ucs, int64_t keep,
                      const double* Vt, int64_t vrs, int64_t vcs, const double* Ar, int64_t k1, int64_t nr, const double* S, double* Al_new,
                      double* Ar_new, double* Cdiag, void* ws, int64_t ws_bytes) {
     TN_CHECK_ARG(ml >= 1 && k0 >= 1 && keep >= 1 && k1 >= 1 && nr >= 1, "non-positive dimension");
-    TN_CHECK_ARG(ws_bytes >= apply_truncation_ws_bytes(ml, k0, keep, k1, nr), "workspace too small");
-    const int64_t g1 = gemm_ws_bytes(ml, keep, k0, 1), g2 = gemm_ws_bytes(keep, nr, k1, 1);
+    TwoGemmWs w;
+    TN_CHECK_ARG(ws_bytes >= apply_truncation_layout(ml, k0, keep, k1, nr, (char*)ws, &w), "workspace too small");
     int rc;
-    if ((rc = gemm(st, ml, keep, k0, 1.0, Al, k0, 1, U, urs, ucs, 0.0, Al_new, keep, 1, 1, 0, 0, 0, g1 > 0 ? (double*)ws : nullptr, g1))) return rc;
-    if ((rc = gemm(st, keep, nr, k1, 1.0, Vt, vrs, vcs, Ar, nr, 1, 0.0, Ar_new, nr, 1, 1, 0, 0, 0, g2 > 0 ? (double*)ws : nullptr, g2))) return rc;
+    if ((rc = gemm(st, ml, keep, k0, 1.0, Al, k0, 1, U, urs, ucs, 0.0, Al_new, keep, 1, 1, 0, 0, 0, w.gws1(), w.g1))) return rc;
+    if ((rc = gemm(st, keep, nr, k1, 1.0, Vt, vrs, vcs, Ar, nr, 1, 0.0, Ar_new, nr, 1, 1, 0, 0, 0, w.gws2(), w.g2))) return rc;
     TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(diag_from_vec_kernel, dim3((unsigned)cdiv(keep * keep, 256)), dim3(256), 0, st, S, keep, Cdiag));
     TN_CHECK_LAUNCH("diag_from_vec_kernel");
     return 0;

@@ -699,10 +699,17 @@ __global__ __launch_bounds__(256) void sq_kernel(SqArgs a) {
 static SqState* sq_state_of(int slot) { return (SqState*)device_pool_slot(HIP_SYMBOL(sq_state_pool), sizeof(SqState), slot); }
 static unsigned long long* sq_stats_of(int slot) { return (unsigned long long*)device_pool_slot(HIP_SYMBOL(sq_stats), 4 * sizeof(unsigned long long), slot); }
 
-int64_t smallqr_ws_bytes(int64_t m, int64_t n) {
+// workspace: partial Gram matrices (2 x SQ_MAXBLK) | their sum (x 2) | block exponents
+static int64_t smallqr_layout(int64_t n, char* base, SqArgs* a) {
     const int N = n <= 32 ? 32 : 64;
-    return (int64_t)(2 * SQ_MAXBLK + 2) * N * N * 8 + 1024;
+    WsCarve ws{base};
+    double* part = ws.take<double>((int64_t)2 * SQ_MAXBLK * N * N * 8);
+    double* gsum = ws.take<double>((int64_t)2 * N * N * 8);
+    int* bexp = ws.take<int>(1024);
+    if (a) { a->part = part; a->gsum = gsum; a->bexp = bexp; }
+    return ws.total();
 }
+int64_t smallqr_ws_bytes(int64_t m, int64_t n) { return smallqr_layout(n, nullptr, nullptr); }
 
 // whether smallqr_factor takes this shape (the caller then needs smallqr_ws_bytes of scratch)
 bool smallqr_fits(int64_t m, int64_t n) {
@@ -717,19 +724,15 @@ bool smallqr_fits(int64_t m, int64_t n) {
 int smallqr_factor(hipStream_t st, const double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, double* Q, int64_t qrs, int64_t qcs, double* R,
                    int64_t rrs, int64_t rcs, double* nf_out2, void* ws, int64_t ws_bytes) {
     if (!env_flag_on("TN_QR_SMALL")) return 1;                        // read per call: the tests switch it
-    if (!smallqr_fits(m, n) || !Q || !R || ws_bytes < smallqr_ws_bytes(m, n)) return 1;
+    SqArgs a;
+    if (!smallqr_fits(m, n) || !Q || !R || ws_bytes < smallqr_layout(n, (char*)ws, &a)) return 1;
     const int slot = cholqr_stream_slot(st);
     if (slot >= CHOLQR_SLOTS) return 1;
     const int N = n <= 32 ? 32 : 64, TR = n <= 32 ? 256 : 128;
     const int nblk = (int)cdiv(m, TR);
     if (nblk > 1 && !fused_forms_allowed(st, nblk)) return 1;
-    SqArgs a;
     a.A = A; a.ars = rs; a.acs = cs; a.m = m; a.n = (int)n;
     a.Q = Q; a.qrs = qrs; a.qcs = qcs; a.R = R; a.rrs = rrs; a.rcs = rcs; a.nf_out2 = nf_out2;
-    char* p = (char*)ws;
-    a.part = (double*)p; p += (int64_t)2 * SQ_MAXBLK * N * N * 8;
-    a.gsum = (double*)p; p += (int64_t)2 * N * N * 8;
-    a.bexp = (int*)p;
     a.stt = sq_state_of(slot);
     a.stats = sq_stats_of(slot);
     if (!a.stt || !a.stats) return 1;

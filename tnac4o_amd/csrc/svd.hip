@@ -478,24 +478,23 @@ struct SvdWs {
 static int64_t svd_layout(int64_t nv, int64_t L, bool vectors, char* base, SvdWs* w) {
     const int64_t nvp = align_up(nv, 2 * SVD_W), nblk = nvp / SVD_W, ng = nblk / 2, nr = nblk - 1;
     const int nchunk = gram_nchunk(L);
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { int64_t o = off; off += align_up(bytes, 256); return base ? base + o : nullptr; };
+    WsCarve ws{base};
     // X (nvp x L) and the accumulator P (nvp x nv) share rows of one (nvp x (L + nv)) array, so that one GEMM applies a
     // round's rotations to both
-    double* X = (double*)take(nvp * (L + (vectors ? nv : 0)) * 8);
+    double* X = ws.take<double>(nvp * (L + (vectors ? nv : 0)) * 8);
     double* P = X ? X + L : nullptr;        // size queries run the layout with a null base
-    double* part = (double*)take(ng * nchunk * 4 * SVD_W * SVD_W * 8);
-    double* Js = (double*)take(ng * 4 * SVD_W * SVD_W * 8);
-    double* maxoff = (double*)take(nr * ng * 8);
-    double* norms = (double*)take(nvp * 8);
-    double* Ss = (double*)take(nvp * 8);
-    int* live = (int*)take(nvp * 4);
-    int* pairs = (int*)take(nr * ng * 2 * 4);
-    int* nrot = (int*)take(ng * 4);
-    int* order = (int*)take(nvp * 4);
+    double* part = ws.take<double>(ng * nchunk * 4 * SVD_W * SVD_W * 8);
+    double* Js = ws.take<double>(ng * 4 * SVD_W * SVD_W * 8);
+    double* maxoff = ws.take<double>(nr * ng * 8);
+    double* norms = ws.take<double>(nvp * 8);
+    double* Ss = ws.take<double>(nvp * 8);
+    int* live = ws.take<int>(nvp * 4);
+    int* pairs = ws.take<int>(nr * ng * 2 * 4);
+    int* nrot = ws.take<int>(ng * 4);
+    int* order = ws.take<int>(nvp * 4);
     if (w) { w->X = X; w->P = P; w->part = part; w->Js = Js; w->maxoff = maxoff; w->norms = norms; w->Ssorted = Ss;
              w->live = live; w->pairs = pairs; w->nrot = nrot; w->order = order; }
-    return off;
+    return ws.total();
 }
 
 int64_t svd_ws_bytes(int64_t k, int64_t n, int vectors) {

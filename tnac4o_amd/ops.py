@@ -894,22 +894,28 @@ def env3(side, E, At, W, Ab, log2nf_in=None, keep_half=False):
     return (out, lg, half) if keep_half else (out, lg)
 
 
-def cluster_marginal(HL, HR, F, dmap, rmap, log2L=None, log2R=None):
-    """Marginal of one cell from the half-products of env3 at that cell (tn_cluster_marginal).  Returns device tensors
-    (P (q,), minP (1,), log2z (1,)): P normalised after the negative-probability rule of calc_pn, minP its relative magnitude
-    (<= 0), log2z the log2 of the row contraction <rhoB|row|rhoT> when log2L / log2R are the environments' running log2 factors."""
-    bl, pd, Dt2, Db = HL.shape
+def _cell_dims(HL, HR, F, dmap, rmap, stacked=False):
+    """The operands of a cell closing checked against each other: HL (bl, pd, Dt2, Db), or (nE, bl, pd, Dt2, Db) when stacked,
+    HR (pu, br, Dt2, Db), F (q, bl, pu) and the int32 maps of the q states.  Returns (nE, q, bl, pd, br, pu, K) with K = Dt2 Db."""
+    nE, bl, pd, Dt2, Db = HL.shape if stacked else (1,) + tuple(HL.shape)
     pu, br, Dt2b, Dbb = HR.shape
     q, nl, nu = F.shape
     assert (Dt2b, Dbb) == (Dt2, Db) and (nl, nu) == (bl, pu), (HL.shape, HR.shape, F.shape)
     for t in (HL, HR, F, dmap, rmap):
         assert t.is_contiguous() and t.is_cuda
     assert dmap.dtype == torch.int32 and rmap.dtype == torch.int32 and dmap.numel() == q and rmap.numel() == q
+    return nE, q, bl, pd, br, pu, Dt2 * Db
+
+
+def cluster_marginal(HL, HR, F, dmap, rmap, log2L=None, log2R=None):
+    """Marginal of one cell from the half-products of env3 at that cell (tn_cluster_marginal).  Returns device tensors
+    (P (q,), minP (1,), log2z (1,)): P normalised after the negative-probability rule of calc_pn, minP its relative magnitude
+    (<= 0), log2z the log2 of the row contraction <rhoB|row|rhoT> when log2L / log2R are the environments' running log2 factors."""
+    _, q, bl, pd, br, pu, K = _cell_dims(HL, HR, F, dmap, rmap)
     dev = HL.device
     P = torch.empty(q, dtype=torch.float64, device=dev)
     mP = torch.empty(1, dtype=torch.float64, device=dev)
     lz = torch.empty(1, dtype=torch.float64, device=dev)
-    K = Dt2 * Db
     wsb = _ws_query('tn_cluster_marginal_ws_bytes', bl, pd, br, pu, K)
     ws = workspace(wsb, 1)
     check(lib().tn_cluster_marginal(HL.data_ptr(), HR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, bl, pd, br, pu, K,
@@ -923,19 +929,12 @@ def cluster_bond_marginal(HL, HR, F, dmap, rmap, log2L=None, log2R=None):
     Returns device tensors (Pl (q, bl), Pu (q, pu), minB (1,), log2z (1,)): Pl[s,l] / Pu[s,u] the joint law of the cell's state
     with its left / upper bond index, both divided by the same raw total (no negative-probability rule), minB = min(0, smallest
     entry), log2z the log2 of the row contraction as cluster_marginal."""
-    bl, pd, Dt2, Db = HL.shape
-    pu, br, Dt2b, Dbb = HR.shape
-    q, nl, nu = F.shape
-    assert (Dt2b, Dbb) == (Dt2, Db) and (nl, nu) == (bl, pu), (HL.shape, HR.shape, F.shape)
-    for t in (HL, HR, F, dmap, rmap):
-        assert t.is_contiguous() and t.is_cuda
-    assert dmap.dtype == torch.int32 and rmap.dtype == torch.int32 and dmap.numel() == q and rmap.numel() == q
+    _, q, bl, pd, br, pu, K = _cell_dims(HL, HR, F, dmap, rmap)
     dev = HL.device
     Pl = torch.empty((q, bl), dtype=torch.float64, device=dev)
     Pu = torch.empty((q, pu), dtype=torch.float64, device=dev)
     mB = torch.empty(1, dtype=torch.float64, device=dev)
     lz = torch.empty(1, dtype=torch.float64, device=dev)
-    K = Dt2 * Db
     wsb = _ws_query('tn_cluster_bond_marginal_ws_bytes', q, bl, pd, br, pu, K)
     ws = workspace(wsb, 1)
     check(lib().tn_cluster_bond_marginal(HL.data_ptr(), HR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, bl, pd, br, pu,
@@ -989,15 +988,8 @@ def env3_stack(E, At, Wops, Ab, log2nf_in=None, keep_half=False):
 def stack_cell_law(HL, HR, F, dmap, rmap):
     """Every slot of a stack closed at one cell (tn_stack_cell_law): HL (nE, bl, pd, Dt2, Db) from env3_stack, HR (pu, br, Dt2, Db)
     from env3.  Returns D (nE, q), raw: D[e, s] = sum_{l,u} F[s,l,u] X_e[l, dmap[s], u, rmap[s]] with X_e = HL[e] . HR^T."""
-    nE, bl, pd, Dt2, Db = HL.shape
-    pu, br, Dt2b, Dbb = HR.shape
-    q, nl, nu = F.shape
-    assert (Dt2b, Dbb) == (Dt2, Db) and (nl, nu) == (bl, pu), (HL.shape, HR.shape, F.shape)
-    for t in (HL, HR, F, dmap, rmap):
-        assert t.is_contiguous() and t.is_cuda
-    assert dmap.dtype == torch.int32 and rmap.dtype == torch.int32 and dmap.numel() == q and rmap.numel() == q
+    nE, q, bl, pd, br, pu, K = _cell_dims(HL, HR, F, dmap, rmap, stacked=True)
     D = torch.empty((nE, q), dtype=torch.float64, device=HL.device)
-    K = Dt2 * Db
     wsb = _ws_query('tn_stack_cell_law_ws_bytes', nE, bl, pd, br, pu, K)
     ws = workspace(wsb, 1)
     check(lib().tn_stack_cell_law(HL.data_ptr(), HR.data_ptr(), F.data_ptr(), dmap.data_ptr(), rmap.data_ptr(), q, nE, bl, pd, br, pu, K,
