@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 16 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 18 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -61,6 +61,21 @@ int tn_gemm(int64_t M, int64_t N, int64_t K, double alpha, const double* A, int6
             const double* B, int64_t rsb, int64_t csb, double beta, double* C, int64_t rsc, int64_t csc,
             int64_t batch, int64_t bsa, int64_t bsb, int64_t bsc, void* ws, int64_t ws_bytes, void* stream);
 int64_t tn_gemm_ws_bytes(int64_t M, int64_t N, int64_t K, int64_t batch);
+
+/* ---- a pair of products through the MPS (x) MPO factors (csrc/factor_products.hip), element strides throughout:
+ *     S_z[(i, j), n] = sum_{k < K1} P[z pz + i pi + k pk] X[k xk + j xj + n xn]                      z < Z, i < I, j < J, n < N
+ *     Out[z oz + m_hi ohi + m_lo olo + n on] = sum_{q < I J} W[m wm + q wq] S_z[q, n]         q = i J + j, m = m_hi Mlo + m_lo
+ * Bit for bit what two tn_gemm calls compute: the first product as ONE product (Z I) x (J N) x K1 with the workspace
+ * tn_gemm_ws_bytes asks for (first_batched = 0; needs pz = I pi and xj = N xn) or as J products (Z I) x N x K1 without a workspace
+ * (first_batched = 1), the second as Z products (Mhi Mlo) x N x (I J) without one.  Where tn_factor_products_eligible says 1 (the
+ * shape fits the kernel and the launch plan does not split K1 of the first product) and TN_FACTOR_FUSED is not 0 this is one launch
+ * that never writes S; otherwise the entry runs those tn_gemm launches itself, with S in ws (tn_factor_products_ws_bytes). */
+int tn_factor_products_eligible(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int64_t M, int first_batched);
+int64_t tn_factor_products_ws_bytes(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int first_batched);
+int tn_factor_products(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int64_t Mhi, int64_t Mlo, const double* P, int64_t pz,
+                       int64_t pi, int64_t pk, const double* X, int64_t xk, int64_t xj, int64_t xn, const double* W, int64_t wm,
+                       int64_t wq, double* Out, int64_t oz, int64_t ohi, int64_t olo, int64_t on, int first_batched, void* ws,
+                       int64_t ws_bytes, void* stream);
 
 /* ---- K1: MPO.MPS absorption of one site.  Replaces MPS.apply_mpo (mps.py:353-359) -> _mps_HA (:753-763).
  * A: (Dl, pold, Dr) C-order.  W: (ba, po, bb, pi) C-order, legs (left, out, right, in).

@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libtnpeps.so')
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['api.hip', 'gemm_f64.hip', 'rank_update.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip', 'sampler.hip', 'overlap.hip']
+SOURCES = ['api.hip', 'gemm_f64.hip', 'rank_update.hip', 'factor_products.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip', 'sampler.hip', 'overlap.hip']
 
 _i64, _f64, _int, _ptr = C.c_int64, C.c_double, C.c_int, C.c_void_p
 
@@ -21,6 +21,10 @@ SIGNATURES = {
     'tn_gemm': (_int, [_i64, _i64, _i64, _f64, _ptr, _i64, _i64, _ptr, _i64, _i64, _f64, _ptr, _i64, _i64,
                        _i64, _i64, _i64, _i64, _ptr, _i64, _ptr]),
     'tn_gemm_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'tn_factor_products_eligible': (_int, [_i64] * 6 + [_int]),
+    'tn_factor_products_ws_bytes': (_i64, [_i64] * 5 + [_int]),
+    'tn_factor_products': (_int, [_i64] * 7 + [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _i64,
+                                  _int, _ptr, _i64, _ptr]),
     'tn_absorb': (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _i64, _i64, _i64, _i64, _ptr]),
     'tn_qr': (_int, [_ptr, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _i64, _int, _f64, C.POINTER(_i64), _ptr, _i64,
               _ptr]),
@@ -204,7 +208,7 @@ SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes
                'tn_mpo_from_factor_ops', 'tn_env3_stack', 'tn_env3_stack_ws_bytes', 'tn_stack_cell_law', 'tn_stack_cell_law_ws_bytes',
                'tn_last_error')
 _lib = None
-ABI_VERSION = 17         # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
+ABI_VERSION = 18        # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
 
 
 def lib():

@@ -23,7 +23,7 @@ using namespace tn;
 
 extern "C" {
 
-int tn_version(void) { return 17; }
+int tn_version(void) { return 18; }
 
 #ifndef TN_SRC_HASH
 #define TN_SRC_HASH "unknown"
@@ -93,6 +93,47 @@ int tn_gemm(int64_t M, int64_t N, int64_t K, double alpha, const double* A, int6
     return gemm(ST, M, N, K, alpha, A, rsa, csa, B, rsb, csb, beta, C, rsc, csc, batch, bsa, bsb, bsc, (double*)ws, ws_bytes);
 }
 int64_t tn_gemm_ws_bytes(int64_t M, int64_t N, int64_t K, int64_t batch) { return gemm_ws_bytes(M, N, K, batch); }
+
+int tn_factor_products_eligible(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int64_t M, int first_batched) {
+    return factor_products_fits(Z, I, J, K1, N, M) && (first_batched || gemm_ws_bytes(Z * I, J * N, K1, 1) == 0) ? 1 : 0;
+}
+// the two launches' workspace: S for every z, then the split-K scratch of an unbatched first product
+static int64_t factor_products_layout(char* base, int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int first_batched, double** S,
+                                      double** gw, int64_t* gw_bytes) {
+    WsCarve c{base};
+    *gw_bytes = first_batched ? 0 : gemm_ws_bytes(Z * I, J * N, K1, 1);
+    *S = c.take<double>(Z * I * J * N * 8);
+    *gw = c.take<double>(*gw_bytes);
+    return c.total();
+}
+int64_t tn_factor_products_ws_bytes(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int first_batched) {
+    double* S; double* gw; int64_t gb;
+    return factor_products_layout(nullptr, Z, I, J, K1, N, first_batched, &S, &gw, &gb);
+}
+int tn_factor_products(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int64_t Mhi, int64_t Mlo, const double* P, int64_t pz,
+                       int64_t pi, int64_t pk, const double* X, int64_t xk, int64_t xj, int64_t xn, const double* W, int64_t wm,
+                       int64_t wq, double* Out, int64_t oz, int64_t ohi, int64_t olo, int64_t on, int first_batched, void* ws,
+                       int64_t ws_bytes, void* stream) {
+    TN_CHECK_ARG(Z >= 1 && I >= 1 && J >= 1 && K1 >= 1 && N >= 1 && Mhi >= 1 && Mlo >= 1, "non-positive dimension");
+    TN_CHECK_ARG(P && X && W && Out, "null operand");
+    TN_CHECK_ARG((Z == 1 || pz == I * pi) && (first_batched || J == 1 || xj == N * xn), "the first product needs pz = I pi, and unbatched xj = N xn");
+    if (factor_products_on() && tn_factor_products_eligible(Z, I, J, K1, N, Mhi * Mlo, first_batched)) {
+        FactorProducts f;
+        f.Z = Z; f.I = I; f.J = J; f.K1 = K1; f.N = N; f.Mhi = Mhi; f.Mlo = Mlo;
+        f.P = P; f.pz = pz; f.pi = pi; f.pk = pk; f.X = X; f.xk = xk; f.xj = xj; f.xn = xn; f.W = W; f.wm = wm; f.wq = wq;
+        f.Out = Out; f.oz = oz; f.ohi = ohi; f.olo = olo; f.on = on;
+        return factor_products(ST, f);
+    }
+    double* S; double* gw; int64_t gb;
+    const int64_t need = factor_products_layout((char*)ws, Z, I, J, K1, N, first_batched, &S, &gw, &gb);
+    TN_CHECK_ARG(ws && ws_bytes >= need, "workspace too small (tn_factor_products_ws_bytes)");
+    int rc;
+    if (first_batched) rc = gemm(ST, Z * I, N, K1, 1.0, P, pi, pk, X, xk, xn, 0.0, S, J * N, 1, J, 0, xj, N, nullptr, 0);
+    else rc = gemm(ST, Z * I, J * N, K1, 1.0, P, pi, pk, X, xk, xn, 0.0, S, J * N, 1, 1, 0, 0, 0, gw, gb);
+    for (int64_t h = 0; h < Mhi && rc == 0; ++h)
+        rc = gemm(ST, Mlo, N, I * J, 1.0, W + h * Mlo * wm, wm, wq, S, N, 1, 0.0, Out + h * ohi, olo, on, Z, 0, I * J * N, oz, nullptr, 0);
+    return rc;
+}
 
 int tn_absorb(const double* A, const double* W, double* out, int64_t Dl, int64_t pold, int64_t Dr, int64_t ba, int64_t po,
               int64_t bb, int64_t pi, int hconj, int64_t batch, int64_t bsA, int64_t bsW, int64_t bsOut, void* stream) {

@@ -672,6 +672,12 @@ public:
     }
 
     // ---- weighted rank-revealing first pass (MPS.canonise_right_weighted) ----
+    // A pair of products through the factors goes to factor_products (one launch, same bits) where the shape fits the kernel and the
+    // launch plan would not split K of the first product, an unbatched M1 x N1 x K1 one (M1 = 0: a batched one, which never splits).
+    // TN_FACTOR_FUSED=0 (read per call) keeps the two launches everywhere.
+    static bool factor_pair_fused(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int64_t M, int64_t M1, int64_t N1) {
+        return factor_products_on() && factor_products_fits(Z, I, J, K1, N, M) && (M1 == 0 || gemm_ws_bytes(M1, N1, K1, 1) == 0);
+    }
     int gram_step_structured(M2& G, int64_t n) {
         const int64_t* fd = &facdims[7 * n];
         const int64_t Dl = fd[0], ps = fd[1], Dr = fd[2], ba = fd[3], po = fd[4], bb = fd[5], pi = fd[6];
@@ -687,18 +693,33 @@ public:
         CH(new_block(na * ba * Dl, gpb, Gp, "Gram (permuted)"));
         if (hconj) CH(permute4(st, G.p, ba * na, na, 1, ba, Dl, ba, ba, Dl, Gp));          // G[(alpha ba + l) na + alpha' ba + l']
         else CH(permute4(st, G.p, na, Dl * na, Dl, 1, Dl, ba, ba, Dl, Gp));                // G[(l Dl + alpha) na + l' Dl + alpha']
-        Ref t1b; double* T1 = nullptr;
-        CH(new_block(na * ba * ps * Dr, t1b, T1, "Gram step T1"));
-        CH(mm(na * ba, ps * Dr, Dl, Gp, Dl, 1, Af, ps * Dr, 1, T1, ps * Dr, 1));
-        gpb.reset();
-        // Wx[(t, r'), (l', s')] = Wl[l', s', r', t]
         Ref wxb; double* Wx = nullptr;
-        CH(new_block(pt * bb * ba * ps, wxb, Wx, "Wx"));
-        CH(permute4(st, W, wtd, wr, wl, wsd, pt, bb, ba, ps, Wx));
         Ref t2b; double* T2 = nullptr;
-        CH(new_block(na * pt * bb * Dr, t2b, T2, "Gram step T2"));
-        CH(bmm(na, pt * bb, Dr, ba * ps, Wx, ba * ps, 1, 0, T1, Dr, 1, ba * ps * Dr, T2, Dr, 1, pt * bb * Dr));
-        t1b.reset();
+        if (factor_pair_fused(na, ba, ps, Dl, Dr, pt * bb, na * ba, ps * Dr)) {
+            // T2 = Wx (Gp A) in one launch, T1 never written (factor_products.hip): z = (alpha, l), i = l', k = alpha', j = s', n = beta';
+            // Wx q-major, Wx[(l', s'), (t, r')], so that the kernel reads whole segments of it
+            CH(new_block(pt * bb * ba * ps, wxb, Wx, "Wx"));
+            CH(permute4(st, W, wl, wsd, wtd, wr, ba, ps, pt, bb, Wx));
+            CH(new_block(na * pt * bb * Dr, t2b, T2, "Gram step T2"));
+            FactorProducts f;
+            f.Z = na; f.I = ba; f.J = ps; f.K1 = Dl; f.N = Dr; f.Mhi = 1; f.Mlo = pt * bb;
+            f.P = Gp; f.pz = ba * Dl; f.pi = Dl; f.pk = 1;
+            f.X = Af; f.xk = ps * Dr; f.xj = Dr; f.xn = 1;
+            f.W = Wx; f.wm = 1; f.wq = pt * bb;
+            f.Out = T2; f.oz = pt * bb * Dr; f.ohi = 0; f.olo = Dr; f.on = 1;
+            CH(factor_products(st, f));
+            gpb.reset();
+        } else {
+            Ref t1b; double* T1 = nullptr;
+            CH(new_block(na * ba * ps * Dr, t1b, T1, "Gram step T1"));
+            CH(mm(na * ba, ps * Dr, Dl, Gp, Dl, 1, Af, ps * Dr, 1, T1, ps * Dr, 1));
+            gpb.reset();
+            // Wx[(t, r'), (l', s')] = Wl[l', s', r', t]
+            CH(new_block(pt * bb * ba * ps, wxb, Wx, "Wx"));
+            CH(permute4(st, W, wtd, wr, wl, wsd, pt, bb, ba, ps, Wx));
+            CH(new_block(na * pt * bb * Dr, t2b, T2, "Gram step T2"));
+            CH(bmm(na, pt * bb, Dr, ba * ps, Wx, ba * ps, 1, 0, T1, Dr, 1, ba * ps * Dr, T2, Dr, 1, pt * bb * Dr));
+        }
         // Wy[(s, r), (l, t)] = Wl[l, s, r, t]
         Ref wyb; double* Wy = nullptr;
         CH(new_block(ps * bb * ba * pt, wyb, Wy, "Wy"));
@@ -750,6 +771,21 @@ public:
         const int64_t Dl = fd[0], ps = fd[1], Dr = fd[2], ba = fd[3], po = fd[4], bb = fd[5], pi = fd[6], r = Cm.c;
         const int64_t pt = hconj ? pi : po;                                     // hconj: s = po, t = pi; else s = pi, t = po
         if (Cm.r != Dr * bb || (hconj ? po : pi) != ps) { set_error("tn_compress_mps: centre matrix does not fit the factors of site %lld", (long long)n); return -1; }
+        if (factor_pair_fused(Dl, ps, bb, Dr, r, ba * pt, hconj ? Dl * ps : 0, bb * r)) {
+            // both products in one launch, T never written (factor_products.hip): z = alpha, i = s, k = beta, j = rb, n = r'; Wq q-major,
+            // Wq[(s, rb), (l, t)]; without Hconj the rows (l, t) of item alpha go straight to (l, alpha, t, r')
+            Ref wb; double* Wq = nullptr;
+            CH(new_block(ba * pt * ps * bb, wb, Wq, "attach through the factors: W"));
+            if (hconj) CH(permute4(st, facW[n], bb * pi, pi, po * bb * pi, 1, ps, bb, ba, pt, Wq));
+            else CH(permute4(st, facW[n], 1, pi, po * bb * pi, bb * pi, ps, bb, ba, pt, Wq));
+            FactorProducts f;
+            f.Z = Dl; f.I = ps; f.J = bb; f.K1 = Dr; f.N = r; f.Mhi = ba; f.Mlo = pt;
+            f.P = facA[n]; f.pz = ps * Dr; f.pi = Dr; f.pk = 1;
+            f.X = Cm.p; f.xk = hconj ? bb * r : r; f.xj = hconj ? r : Dr * r; f.xn = 1;
+            f.W = Wq; f.wm = 1; f.wq = ba * pt;
+            f.Out = Am; f.oz = hconj ? ba * pt * r : pt * r; f.ohi = hconj ? pt * r : Dl * pt * r; f.olo = r; f.on = 1;
+            return factor_products(st, f);
+        }
         Ref tb; double* T = nullptr;
         CH(new_block(Dl * ps * bb * r, tb, T, "attach through the factors: T"));
         if (hconj) CH(mm(Dl * ps, bb * r, Dr, facA[n], Dr, 1, Cm.p, bb * r, 1, T, bb * r, 1));

@@ -174,6 +174,20 @@ static inline int rank_update(hipStream_t st, int64_t m, int64_t n, int b, Mat W
     return rank_update(st, m, n, b, W.p, W.rs, W.cs, X.p, X.rs, X.cs, C.p, C.rs, C.cs, active);
 }
 
+// ---- the two products of a contraction through the MPS (x) MPO factors in one launch (factor_products.hip) ---------------------
+//     S_z[(i, j), n] = sum_k P[z, i, k] X[k, j, n],    Out_z[m_hi Mlo + m_lo, n] = sum_q W[m, q] S_z[q, n],  q = i J + j
+// element strides throughout.  Bit for bit what gemm (first product, K not split) followed by a batched gemm computes.
+struct FactorProducts {
+    int64_t Z, I, J, K1, N, Mhi, Mlo;
+    const double* P; int64_t pz, pi, pk;
+    const double* X; int64_t xk, xj, xn;
+    const double* W; int64_t wm, wq;                // row m = m_hi Mlo + m_lo, column q
+    double* Out; int64_t oz, ohi, olo, on;
+};
+bool factor_products_fits(int64_t Z, int64_t I, int64_t J, int64_t K1, int64_t N, int64_t M);      // the kernel's static limits
+inline bool factor_products_on() { return env_flag_on("TN_FACTOR_FUSED"); }                          // read per call: the tests switch it
+int factor_products(hipStream_t st, const FactorProducts& f);
+
 // ---- small dense kernels (small.hip) ------------------------------------------------------------
 constexpr int NBMAX = 64;      // largest panel / Jacobi pair width handled by the single-workgroup kernels
 
