@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 18 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 19 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -584,6 +584,39 @@ int tn_pair_moments(const uint64_t* rows, int64_t M, int64_t G, int64_t wpg, int
 int64_t tn_spin_moments_ws_bytes(int64_t M, int64_t nbits, uint32_t wmax);
 int tn_spin_moments(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, uint32_t wmax, uint64_t* out, int64_t ldo,
                     void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- K10: cell sweeps over given configurations (no counterpart in the reference: tnac4o.relax_samples) ---------------------------
+ * tn_cell_sweep: `sweeps` sweeps of block updates of whole cells over M configurations, IN PLACE in states (DEVICE, M x Nx*Ny int16,
+ * lattice order of this rotation).  cells (HOST array, cells[ny * Nx + nx]): only the ENERGY part of a tn_beam_cell is read -- down,
+ * right, Es, E1, E4, left_map, up_map, q, e1cols, e4cols; F, dmap, rmap, A and the MPS dimensions may be NULL / 0.  The call needs NO
+ * boundary MPS and runs no contraction.  Conditional energy of cell c in state s given the states sl, su, sr, sb of its neighbours
+ * (R, Bc: the right / lower cell; L = left_map ? left_map[sl] : sl, U likewise from up_map and su):
+ *     e(s) = (((1.0 Es[s] + E1[s e1cols + L]) + E4[s e4cols + U]) + R.E1[sr R.e1cols + (R.left_map ? R.left_map[s] : s)])
+ *                                                                 + Bc.E4[sb Bc.e4cols + (Bc.up_map ? Bc.up_map[s] : s)]
+ * with these additions in this order, a term absent (not zero-added) at a lattice edge: the bits of the same expression in numpy.
+ * One sweep = the cells of colour 0 (ny + nx even), then those of colour 1, every cell of a colour updated from the states as they stand
+ * before that colour (one launch per colour).  sweeps = 0 updates nothing and only writes the outputs.
+ * mode 0, heat bath at inverse temperature beta: w_s = exp(-beta (e(s) - min e)); the running sum c_s runs over s in an order that
+ * depends on q alone, W = c_{q-1}; with t = u W the new state is the first s with c_s >= t and w_s > 0, otherwise the last s with
+ * w_s > 0 (tn_sample_pn's rule).  uniforms (DEVICE): sweeps * Nx*Ny rows of ldu >= M doubles in [0, 1); the number of (sweep j, cell k
+ * in walk order, sample m) is uniforms[(j Nx Ny + k) ldu + m].  mode 1, quench: the new state is the smallest s attaining min e(s) if
+ * that minimum is strictly below e(current), otherwise the cell stays; uniforms must be NULL.
+ * Results (DEVICE): energy_out (M) = the energy of the final configuration, added cell by cell in walk order with the additions of
+ * tn_gibbs_score's energy_out (the same bits); moves_out (M int32, may be NULL) = the number of cell updates that changed the state;
+ * last_moves_out (M int32, may be NULL) = the same for the final sweep only (quench: 0 = a local minimum of the cell moves).
+ * A sample's result depends on its own row of states and its own column of uniforms only -- not on M, on the grid, or on how the
+ * samples are cut into calls.  A state outside [0, q) of its cell is never used as an index: as a neighbour (and in energy_out) it is
+ * read as 0, as the current state of a quench its energy counts as +inf.
+ * ws: tn_cell_sweep_ws_bytes (0 for a shape the call refuses): the table of the cells and one flag per (cell, sample).
+ * Asynchronous on `stream`, no host synchronisation; no barriers across workgroups and no atomics.  TN_CELL_SWEEP_LDS=<bytes> (read per
+ * call; default 32768, at most 153600, 0: never) is the size up to which a cell's tables are staged in LDS instead of being read
+ * from global memory: the same bits for every value.  Limits: q <= 32767, M < 2^31.
+ * Errors: -1 argument (mode; beta <= 0 or not finite in mode 0; uniforms NULL in mode 0 or not NULL in mode 1; ldu < M; sweeps < 0; a
+ * null pointer; a bad cell), -3 workspace too small; both before any launch, nothing is written. */
+int64_t tn_cell_sweep_ws_bytes(int64_t Nx, int64_t Ny, int64_t M);
+int tn_cell_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int16_t* states, int mode, double beta, int64_t sweeps,
+                  const double* uniforms, int64_t ldu, double* energy_out, int32_t* moves_out, int32_t* last_moves_out, void* ws,
+                  int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1097,6 +1097,48 @@ class tnac4o:
         self.scored_negative = min(globalmin, 0)
         return log2q
 
+    def relax_samples(self, sweeps=1, mode='heat_bath', beta=None, states=None, uniforms=None, chunk=None, max_sweeps=64):
+        """Move configurations by sweeps of block updates of whole cells (tn_cell_sweep, tnac4o_amd/relax.py): every cell in turn --
+        checkerboard colour ny + nx even first, then odd -- is given a new state from its conditional law given its four neighbours,
+        a table of q numbers read off the cell energies.  Runs NO contraction and needs no boundary MPS; works in the rotation that
+        is set, Ising and RMF.
+        mode='heat_bath': the new state is drawn from the conditional Boltzmann law at `beta` (None = the solver's).  A sweep leaves
+        the Boltzmann law invariant, so sweeps started from the samples of sample_boltzmann at a cheap Dmax can only bring their law
+        closer to it.  uniforms: None = np.random.rand(sweeps, Ny*Nx, M), or a (sweeps, Ny*Nx, M) float64 array / device tensor in
+        [0, 1): sweep, cell in walk order of the current rotation, sample; anything else is a ValueError.
+        mode='quench': every cell goes to the smallest state of minimal conditional energy when that lowers the energy strictly, and
+        stays otherwise (zero-temperature descent; the energy never rises).  sweeps=None repeats sweeps until no cell of any
+        configuration moves in the last one, at most max_sweeps; uniforms must be None.
+        states: an integer numpy array (M, Nx*Ny) in model cell order, in the encoding of `states` (spin read-outs or annealer
+        output: states_from_binary); None = the stored `states`.  A wrong shape or dtype, or an entry outside the states of its cell,
+        is a ValueError raised before any device work.  chunk: configurations per call, as sample_boltzmann's; configuration k's
+        result does not depend on it.
+        Stores states (M, Nx*Ny) in model cell order and energy (M,) (returned), relax_energy_before (M,), relax_moves (M,) = cell
+        updates that changed the configuration, relax_converged (M,) bool = nothing moved in the last sweep (meaningful for a quench:
+        a minimum under the cell moves), relax_sweeps = sweeps run.  probability, sample_log2Z, log2Z_lower and log2Z_estimate are
+        set to None: the configurations are no longer draws of q -- calculate_log_probability() gives log2 q of the new states.
+        rhoT, degeneracy and every thermal and scored attribute are left alone."""
+        from . import relax, sampler
+        lib_mode, nsw, b = relax.check_relax_arguments(mode, sweeps, self.beta if beta is None else beta, uniforms, max_sweeps)
+        st = sampler.check_states(self.states if states is None else states, self._cell_sizes()[self.order])
+        M = st.shape[0]
+        if lib_mode == 0:
+            uniforms = relax.check_sweep_uniforms(uniforms, nsw, self.Nx * self.Ny, M)
+        if chunk is not None:
+            sampler.chunk_slices(M, chunk)
+        self.logger.info('Relaxing %d configurations (%s) with beta = %.2f', M, mode, b)
+        rot = np.empty_like(st)
+        rot[:, self.order] = st                                  # the inverse of _store_result's states[:, order]
+        new, energy, before, moves, last, swept = relax.relax_native(self, rot, lib_mode, b, nsw, uniforms=uniforms, chunk=chunk,
+                                                                     max_sweeps=max_sweeps)
+        self.states = new[:, self.order]
+        self.energy = energy
+        self.relax_energy_before, self.relax_moves = before, moves
+        self.relax_converged = (last == 0) & (swept > 0)
+        self.relax_sweeps = int(swept)
+        self.probability = self.sample_log2Z = self.log2Z_lower = self.log2Z_estimate = None
+        return energy
+
     # ------------------------------------------------------------------------------------ thermal marginals (GPU)
     def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
         """Boltzmann marginal of every cell and magnetisation of every spin at the solver's beta, from both boundary MPS.
