@@ -143,14 +143,21 @@ int tn_qr_batched(double* A, int64_t rs, int64_t cs, int64_t m, int64_t n, doubl
  * With up to 256 live vectors all Jacobi rounds run in ONE launch with the vectors resident in LDS (svdl_kernel: in-kernel barriers,
  * within the co-residency budget of the panel step; TN_SVD_FUSED=0 keeps three launches per round): same results bit for bit.  A launch
  * in which a barrier gave up reports it, the rounds are redone as separate launches inside the same call and the stream stays off the
- * single-launch forms (message on stderr); nothing non-finite is returned. */
+ * single-launch forms (message on stderr); nothing non-finite is returned.
+ * Range: the whole double range is served on every path.  The one-launch kernel (both dimensions <= 64) always scales its input by a
+ * power of two; the block path does so when the largest squared row norm leaves 2^-320 .. 2^500 (entries of about 1e-48 .. 1e75) and
+ * otherwise computes exactly what it computed before.  U, Vt, keep and discarded of 2^e C are those of C, S is 2^e S(C), while
+ * nothing leaves the range.  -2 "svd: non-finite input" is returned only when an entry is NaN or Inf; nothing is written then.
+ * An all-zero C: return 0, keep = 0, discarded = 0.0, nothing written. */
 int tn_svd_trunc(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, int64_t Dmax, double tol, double* U,
                  int64_t urs, int64_t ucs, double* S, double* Vt, int64_t vrs, int64_t vcs, int64_t* keep_host,
                  double* discarded_host, int* sweeps_host, int* info_host, void* ws, int64_t ws_bytes, void* stream);
 /* ---- K5: singular values only, sorted descending, min(k,n) values written to HOST memory.
  * Replaces mps.svd_S (mps.py:62-73) as used by MPS.update_S (:550-560).
  * With both dimensions <= 64 (one launch) the input is scaled by a power of two inside the kernel: the full double range is served,
- * and S(2^e C) = 2^e S(C) bit for bit while nothing leaves the range.  A NaN or Inf entry: -2, "svd: non-finite input". */
+ * and S(2^e C) = 2^e S(C) bit for bit while nothing leaves the range.  A longer side above 64 (the block path of tn_svd_trunc, same
+ * window: scaled by a power of two when the largest squared row norm leaves 2^-320 .. 2^500, untouched otherwise) serves the whole
+ * range as well.  An all-zero C gives zeros.  A NaN or Inf entry, and nothing else: -2, "svd: non-finite input". */
 int tn_svdvals(const double* C, int64_t crs, int64_t ccs, int64_t k, int64_t n, double* S_host, int* sweeps_host,
                int* info_host, void* ws, int64_t ws_bytes, void* stream);
 int64_t tn_svd_ws_bytes(int64_t k, int64_t n, int vectors);

@@ -774,12 +774,11 @@ def test_small_truncated_svd_single_launch(ops):
         k, n = Cm.shape
         U, S, Vt, keep, disc, info = ops.svd_trunc(Cm, Dmax, 1e-16)
         Sh = S.cpu().numpy()
-        if name != 'scaled':            # (entries of 1e120: the block path's Gram matrices overflow; the single launch scales its input)
-            U0, S0, Vt0, keep0, disc0, info0 = _with_env('TN_SVD_SMALL', '0', lambda: ops.svd_trunc(Cm, Dmax, 1e-16))
-            assert keep == keep0, (name, keep, keep0)
-            S0h = S0.cpu().numpy()
-            assert np.abs(Sh - S0h).max() <= 1e-13 * S0h[0], name
-            assert abs(disc - disc0) <= 1e-12 * max(disc0, 1e-300) + 1e-15, (name, disc, disc0)
+        U0, S0, Vt0, keep0, disc0, info0 = _with_env('TN_SVD_SMALL', '0', lambda: ops.svd_trunc(Cm, Dmax, 1e-16))
+        assert keep == keep0, (name, keep, keep0)
+        S0h = S0.cpu().numpy()
+        assert np.abs(Sh - S0h).max() <= 1e-13 * S0h[0], name
+        assert abs(disc - disc0) <= 1e-12 * max(disc0, 1e-300) + 1e-15, (name, disc, disc0)
         Uh, Vh = U.cpu().numpy(), Vt.cpu().numpy()
         assert np.abs(Uh.T @ Uh - np.eye(keep)).max() < 1e-13 and np.abs(Vh @ Vh.T - np.eye(keep)).max() < 1e-13, name
         full = np.linalg.svd(Ch.numpy(), compute_uv=False)

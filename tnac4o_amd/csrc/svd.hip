@@ -26,13 +26,19 @@ namespace tn {
 
 constexpr int SVD_W = 32;
 
-__global__ __launch_bounds__(256) void vec_norm2_kernel(const double* __restrict__ X, int64_t vs, int64_t es, int64_t L,
-                                                        double* __restrict__ out) {
+// out[v] = sum_c (scl x_vc)^2 (scl: a power of two, 1.0 leaves the entries as they are); amax (may be null): amax[v] = max_c |x_vc|
+// of the unscaled entries, +Inf when one of them is NaN or Inf -- what tells an overflowed or vanished sum from a non-finite entry.
+__global__ __launch_bounds__(256) void vec_norm2_kernel(const double* __restrict__ X, int64_t vs, int64_t es, int64_t L, double scl,
+                                                        double* __restrict__ out, double* __restrict__ amax) {
     __shared__ double red[256];
     const int v = blockIdx.x, tid = threadIdx.x;
     const double* x = X + (int64_t)v * vs;
-    double s = 0.0;
-    for (int64_t c = tid; c < L; c += 256) { const double t = x[c * es]; s += t * t; }
+    double s = 0.0, m = 0.0;
+    for (int64_t c = tid; c < L; c += 256) {
+        const double x0 = x[c * es], t = x0 * scl, a = fabs(x0);
+        s += t * t;
+        m = fmax(m, a <= 1.7976931348623157e308 ? a : __longlong_as_double(0x7ff0000000000000LL));
+    }
     red[tid] = s;
     __syncthreads();
     for (int k = 128; k > 0; k >>= 1) {
@@ -40,21 +46,33 @@ __global__ __launch_bounds__(256) void vec_norm2_kernel(const double* __restrict
         __syncthreads();
     }
     if (tid == 0) out[v] = red[0];
+    if (amax) {                                                  // (uniform)
+        __syncthreads();
+        red[tid] = m;
+        __syncthreads();
+        for (int k = 128; k > 0; k >>= 1) {
+            if (tid < k) red[tid] = fmax(red[tid], red[tid + k]);
+            __syncthreads();
+        }
+        if (tid == 0) amax[v] = red[0];
+    }
 }
 
-// X[i] <- M[live[i]] (zero rows beyond nvl); P[i] <- one-hot(live[i]) when P != nullptr
+// X[i] <- scl M[live[i]] (zero rows beyond nvl; scl: a power of two, 1.0 for an input in range); P[i] <- one-hot(live[i]) when P != nullptr
 __global__ __launch_bounds__(256) void svd_init_kernel(const double* __restrict__ M, int64_t vs, int64_t es, int64_t L,
                                                        int64_t nv, const int* __restrict__ live, int nvl,
-                                                       double* __restrict__ X, double* __restrict__ P, int64_t pitch) {
+                                                       double* __restrict__ X, double* __restrict__ P, int64_t pitch, double scl) {
     const int i = blockIdx.x, tid = threadIdx.x;
     const bool on = i < nvl;
     const int src = on ? live[i] : 0;
-    for (int64_t c = tid; c < L; c += 256) X[(int64_t)i * pitch + c] = on ? M[(int64_t)src * vs + c * es] : 0.0;
+    for (int64_t c = tid; c < L; c += 256) X[(int64_t)i * pitch + c] = on ? M[(int64_t)src * vs + c * es] * scl : 0.0;
     if (P)
         for (int64_t c = tid; c < nv; c += 256) P[(int64_t)i * pitch + c] = (on && c == src) ? 1.0 : 0.0;
 }
 
 // One block per kept vector j (source row order[j]):  left[:, j] = sgn * P[row, :],  right[j, :] = sgn * X[row, :] / S_j
+// (S_j: the value of the vectors as they stand in X, i.e. of the input times the power of two jacobi_core scaled it by; Sout receives
+// S_j dscale, the value of the input itself -- dscale = 1.0 for an input in range)
 // with the reference's sign gauge: flip when in both vectors the most negative entry outweighs the most positive.
 // Up to 64 kept vectors (every truncation to chi <= 64): their values and rows travel by value in the kernel arguments (`byval`),
 // no host-to-device copy; more: `order` / `Ssorted` in device memory.
@@ -63,7 +81,7 @@ __global__ __launch_bounds__(256) void svd_gather_kernel(const double* __restric
                                                          int64_t nv, int64_t pitch, const int* __restrict__ order,
                                                          const double* __restrict__ Ssorted, double* __restrict__ Sout,
                                                          double* __restrict__ left, int64_t lrs, int64_t lcs,
-                                                         double* __restrict__ right, int64_t rrs, int64_t rcs, GatherList gl, int byval) {
+                                                         double* __restrict__ right, int64_t rrs, int64_t rcs, GatherList gl, int byval, double dscale) {
     __shared__ double rmin[256], rmax[256];
     __shared__ double sgn;
     const int j = blockIdx.x, tid = threadIdx.x;
@@ -98,7 +116,7 @@ __global__ __launch_bounds__(256) void svd_gather_kernel(const double* __restric
     }
     __syncthreads();
     const double s = sgn, sv = byval ? gl.S[j] : Ssorted[j];
-    if (tid == 0) Sout[j] = sv;
+    if (tid == 0) Sout[j] = sv * dscale;                       // the value of the caller's matrix; X holds the scaled vectors, so sv divides them
     const double inv = sv > 0.0 ? s / sv : 0.0;
     for (int64_t c = tid; c < L; c += 256) right[(int64_t)j * rrs + c * rcs] = x[c] * inv;
     for (int64_t c = tid; c < nv; c += 256) left[c * lrs + (int64_t)j * lcs] = p[c] * s;
@@ -504,6 +522,8 @@ int64_t svd_ws_bytes(int64_t k, int64_t n, int vectors) {
 
 // Core: orthogonalise the rows of M (nv x L, strides vs/es).  On return hostS holds the singular values sorted
 // descending (length nvl), *nvl_out the number of live vectors, order[] (device) the matching row permutation.
+// The values and the vectors left in X are those of *dscale_out^-1 M (a power of two, 1.0 unless M is out of range, see below):
+// the caller multiplies the values it hands out by *dscale_out; ratios of values -- the truncation rule -- need nothing.
 // rel_tol: the relative threshold below which singular values are of no interest to the caller (the truncation rule keeps
 // S > S0 max(eps, tol), mps.py:805-806).  Vectors a factor 4 below it (relative to the largest input row) are still rotated
 // whenever a group needs rotating, but they do not hold up convergence: the rows of a triangular factor beyond its
@@ -513,18 +533,41 @@ int64_t svd_ws_bytes(int64_t k, int64_t n, int vectors) {
 // and the discarded weight is the Frobenius norm of the remaining rows, which rotations do not change.
 static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, int64_t nv, int64_t L, bool vectors,
                        SvdWs& w, std::vector<double>& hostS, std::vector<int>& hostOrder, int* sweeps_out, int* info,
-                       double rel_tol) {
+                       double rel_tol, double* dscale_out) {
     int rc;
-    TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(vec_norm2_kernel, dim3((unsigned)nv), dim3(256), 0, st, M, vs, es, L, w.norms));
+    // squared norms of the rows into norms[0, nv), their largest absolute entries into norms[nv, 2 nv) (norms | Ssorted hold 2 nvp
+    // doubles and are free until the rounds end): one launch, one read-back
+    TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(vec_norm2_kernel, dim3((unsigned)nv), dim3(256), 0, st, M, vs, es, L, 1.0, w.norms, w.norms + nv));
     TN_CHECK_LAUNCH("vec_norm2_kernel");
-    std::vector<double> hn(nv);
+    std::vector<double> hn(2 * nv);
     // read-backs go through a page-locked staging buffer (see read_back): queued right behind the producing kernel
-    if ((rc = read_back(st, hn.data(), w.norms, (size_t)nv * 8, PIN_SVD_READ, "norms"))) return rc;
-    double nmax = 0.0;
-    for (int64_t i = 0; i < nv; ++i) {
-        if (!(hn[i] == hn[i]) || hn[i] > 1.7e308) { set_error("svd: non-finite input"); return -2; }
-        nmax = std::max(nmax, hn[i]);
+    if ((rc = read_back(st, hn.data(), w.norms, (size_t)nv * 16, PIN_SVD_READ, "norms"))) return rc;
+    double nmax = 0.0, amax = 0.0;
+    for (int64_t i = 0; i < nv; ++i) amax = std::max(amax, hn[nv + i]);
+    if (!(amax <= 1.7976931348623157e308)) { set_error("svd: non-finite input"); return -2; }     // an entry is NaN or Inf
+    for (int64_t i = 0; i < nv; ++i) nmax = hn[i] > nmax ? hn[i] : nmax;                            // (an overflowed sum: +Inf)
+    // Range.  The rounds form products of two Gram entries (g_pq^2, g_pp g_qq, (g_qq - g_pp)^2 + 4 g_pq^2 in eig_small and in the
+    // convergence measure), each at most nmax = the largest squared norm: 5 nmax^2 must stay finite, nmax < 2^510.  Downwards the
+    // rotation test g_pq^2 > (2^-50)^2 g_pp g_qq must still tell something for two rows at the deflation threshold, g_pp = g_qq =
+    // 2^-112 nmax: 2^-324 nmax^2 must be a normal number with its 53 bits, nmax >= 2^-322.  Inside 2^-320 <= nmax <= 2^500 (entries
+    // of roughly 1e-48 .. 1e75) nothing is scaled and every bit is what it was before the range was served.  Outside -- or when the
+    // sums overflowed or vanished altogether -- the entries are multiplied by the power of two that takes the largest of them into
+    // [1, 2), the norms are taken again from the scaled entries, svd_init_kernel scales the vectors on their way into X, and the
+    // values are multiplied back where they leave (*dscale_out).  Powers of two only: the mantissas are those of an input in range.
+    double scl = 1.0, dscale = 1.0;
+    if (amax > 0.0 && !(nmax >= 0x1p-320 && nmax <= 0x1p500)) {
+        int ex = 0;
+        std::frexp(amax, &ex);                                   // amax = f 2^ex, f in [0.5, 1)
+        ex = std::max(ex - 1, -1021);                            // (subnormal entries: the largest power of two with a finite reciprocal)
+        scl = std::ldexp(1.0, -ex);
+        dscale = std::ldexp(1.0, ex);
+        TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(vec_norm2_kernel, dim3((unsigned)nv), dim3(256), 0, st, M, vs, es, L, scl, w.norms, (double*)nullptr));
+        TN_CHECK_LAUNCH("vec_norm2_kernel");
+        if ((rc = read_back(st, hn.data(), w.norms, (size_t)nv * 8, PIN_SVD_READ, "norms"))) return rc;
+        nmax = 0.0;
+        for (int64_t i = 0; i < nv; ++i) nmax = std::max(nmax, hn[i]);
     }
+    if (dscale_out) *dscale_out = dscale;
     std::vector<int> live;
     const double thr = nmax * (1.9259299443872359e-34);      // (2^-56)^2 on squared norms
     for (int64_t i = 0; i < nv; ++i)
@@ -562,7 +605,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
     if ((rc = upload(st, w.live, hinit.data(), hinit.size() * 4, PIN_SVD_UPLOAD, "init"))) return rc;
     const int64_t pitch = L + (vectors ? nv : 0);
     TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(svd_init_kernel, dim3((unsigned)nvp), dim3(256), 0, st, M, vs, es, L, nv, w.live, nvl, w.X,
-                       vectors ? w.P : nullptr, pitch));
+                       vectors ? w.P : nullptr, pitch, scl));
     TN_CHECK_LAUNCH("svd_init_kernel");
 
     const int nchunk = gram_nchunk(L);
@@ -606,7 +649,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
                         "uses from now on\n", (void*)st, (int)hb[nvp + 2]);
                 fused_forms_disable(st);
                 TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(svd_init_kernel, dim3((unsigned)nvp), dim3(256), 0, st, M, vs, es, L, nv, w.live, nvl, w.X,
-                                   vectors ? w.P : nullptr, pitch));
+                                   vectors ? w.P : nullptr, pitch, scl));
                 TN_CHECK_LAUNCH("svd_init_kernel");
             } else {
                 sweeps = (int)hb[nvp];
@@ -656,7 +699,7 @@ static int jacobi_core(hipStream_t st, const double* M, int64_t vs, int64_t es, 
     if (info) *info = converged ? 0 : 1;
     prof_note(PROF_SVD_ROUNDS, (double)sweeps * nr, (double)sweeps * nr * ng, 0.0);
     if (!fused_done) {
-        TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(vec_norm2_kernel, dim3((unsigned)nvp), dim3(256), 0, st, w.X, pitch, 1, L, w.norms));
+        TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(vec_norm2_kernel, dim3((unsigned)nvp), dim3(256), 0, st, w.X, pitch, 1, L, 1.0, w.norms, (double*)nullptr));
         TN_CHECK_LAUNCH("vec_norm2_kernel");
         if ((rc = read_back(st, hs.data(), w.norms, (size_t)nvp * 8, PIN_SVD_READ, "S"))) return rc;
     }
@@ -759,7 +802,8 @@ static int svd_trunc_impl(hipStream_t st, const double* C, int64_t crs, int64_t 
     std::vector<int> hO;
     const double eps = 2.220446049250313e-16;
     const double t = tol > eps ? tol : eps;
-    int rc = jacobi_core(st, C, vs, es, nv, L, true, w, hS, hO, sweeps_out, info, t);
+    double dscale = 1.0;
+    int rc = jacobi_core(st, C, vs, es, nv, L, true, w, hS, hO, sweeps_out, info, t, &dscale);
     if (rc) return rc;
     const int nvl = (int)hS.size();
     int64_t keep = 0;
@@ -768,7 +812,7 @@ static int svd_trunc_impl(hipStream_t st, const double* C, int64_t crs, int64_t 
     double d2 = 0.0;
     for (int i = nvl - 1; i >= keep; --i) d2 += hS[i] * hS[i];
     if (keep_out) *keep_out = keep;
-    if (discarded_out) *discarded_out = std::sqrt(d2) / hS[0];
+    if (discarded_out) *discarded_out = hS[0] > 0.0 ? std::sqrt(d2) / hS[0] : 0.0;     // all-zero input: keep = 0, nothing discarded (as the small kernel)
     if (keep == 0) return 0;
     GatherList gl = {};
     const int byval = keep <= 64 ? 1 : 0;
@@ -787,10 +831,10 @@ static int svd_trunc_impl(hipStream_t st, const double* C, int64_t crs, int64_t 
     // rows: left = U (k x keep), right = Vt.  columns (C^T was factored): left = Vt^T, right = U^T.
     if (rows)
         TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(svd_gather_kernel, dim3((unsigned)keep), dim3(256), 0, st, w.X, L, w.P, nv, L + nv, dO, dS, S,
-                           U, urs, ucs, Vt, vrs, vcs, gl, byval));
+                           U, urs, ucs, Vt, vrs, vcs, gl, byval, dscale));
     else
         TN_PROF_LAUNCH(st, PROF_SVD_AUX, hipLaunchKernelGGL(svd_gather_kernel, dim3((unsigned)keep), dim3(256), 0, st, w.X, L, w.P, nv, L + nv, dO, dS, S,
-                           Vt, vcs, vrs, U, ucs, urs, gl, byval));
+                           Vt, vcs, vrs, U, ucs, urs, gl, byval, dscale));
     TN_CHECK_LAUNCH("svd_gather_kernel");
     return 0;
 }
@@ -845,9 +889,10 @@ int svd_vals(hipStream_t st, const double* C, int64_t crs, int64_t ccs, int64_t 
     svd_layout(nv, L, false, (char*)ws, &w);
     std::vector<double> hS;
     std::vector<int> hO;
-    int rc = jacobi_core(st, C, vs, es, nv, L, false, w, hS, hO, sweeps_out, info, 2.220446049250313e-16);
+    double dscale = 1.0;
+    int rc = jacobi_core(st, C, vs, es, nv, L, false, w, hS, hO, sweeps_out, info, 2.220446049250313e-16, &dscale);
     if (rc) return rc;
-    for (int64_t i = 0; i < nv; ++i) hostS[i] = i < (int64_t)hS.size() ? hS[i] : 0.0;
+    for (int64_t i = 0; i < nv; ++i) hostS[i] = i < (int64_t)hS.size() ? hS[i] * dscale : 0.0;
     return 0;
 }
 
