@@ -625,6 +625,32 @@ int tn_cell_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, 
                   const double* uniforms, int64_t ldu, double* energy_out, int32_t* moves_out, int32_t* last_moves_out, void* ws,
                   int64_t ws_bytes, void* stream);
 
+/* ---- K11: isoenergetic cluster moves on pairs of configurations (no counterpart in the reference: tnac4o.exchange_clusters) --------
+ * tn_cluster_exchange: one round of moves over P disjoint pairs of rows, IN PLACE.  rows (DEVICE) = M rows of nbits bits in
+ * tn_pair_hist's layout (lanes16 = 0) at a stride of ldr words: the words ceil(nbits / 64) .. ldr-1 of a row are never read or written,
+ * the bits beyond nbits in the last word are masked out of everything and written back unchanged.  The graph (DEVICE) is a CSR over
+ * the bits: rowptr (nbits + 1 int32), cols (nnz int32); the arcs of bit i are cols[max(rowptr[i], 0) .. min(rowptr[i+1], nnz) - 1]
+ * (an empty range when that is none), a neighbour outside [0, nbits) is skipped: nothing read from these arrays is used as an index
+ * unchecked.  pairs (DEVICE, P x 2 int32 row indices), uniforms (DEVICE, P doubles in [0, 1)).
+ * The move of pair p = (a, b): D = row_a XOR row_b (masked), cnt = popcount(D).  cnt = 0 (a == b included): nothing moves.  Otherwise
+ * r = min(floor(uniforms[p] * cnt), cnt - 1) -- one IEEE multiplication and a floor, the only floating point of the call --, the seed
+ * is the r-th set bit of D in ascending bit index, C = the bits reachable from the seed along listed arcs through bits of D (for a CSR
+ * that lists every coupling in both directions: the seed's connected component of the subgraph induced on D; for any other CSR:
+ * directed reachability), and row_a ^= C, row_b ^= C.  A uniform that is not in [0, 1) (NaN included) still gives an r in [0, cnt).
+ * Results (DEVICE, P int32 each, always fully written): size_out[p] = |C| (0 when nothing moved), diff_out[p] = cnt; both are -1 for a
+ * pair with an index outside [0, M), which touches nothing.
+ * C is a set function of the inputs: the result is bit-identical for every grid, every schedule and every way of cutting the pairs
+ * into calls.  Duty of the caller: every row appears in at most one pair (not checked: it would take a read of the device);
+ * otherwise those rows are undefined, but nothing is accessed out of range.  The growth of C is bounded by construction: at most nbits
+ * passes, every pass but the last adds at least one bit; no input makes it spin.
+ * Asynchronous on `stream`; no global atomics, no barrier across workgroups, no host synchronisation, no workspace.  nbits <= 4096: one
+ * wave per pair; above: one workgroup per pair.
+ * Limits: 0 <= M < 2^31; 1 <= nbits <= 65534; ldr >= ceil(nbits / 64); 0 <= nnz < 2^31; 0 <= P < 2^31.
+ * Errors: -1 argument (the message names the limit; a null operand -- cols may be NULL when nnz = 0), before any launch, nothing is
+ * written.  P = 0 is a valid no-op (0, whatever the pointers). */
+int tn_cluster_exchange(uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const int32_t* rowptr, const int32_t* cols, int64_t nnz,
+                        const int32_t* pairs, int64_t P, const double* uniforms, int32_t* size_out, int32_t* diff_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

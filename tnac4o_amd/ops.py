@@ -1086,3 +1086,41 @@ def spin_moments(rows, nbits, weights=None, wmax=None):
     p_rows, out, ws, wsb = _stat_buffers('tn_spin_moments_ws_bytes', rows, M, (n2, n2), nbits, wmax)
     check(lib().tn_spin_moments(p_rows, M, nbits, max(ld, nwords), d_w, wmax, out.data_ptr(), n2, ws, wsb, _stream()))
     return out
+
+
+def _i32_operand(t, name, numel=None):
+    """A contiguous device tensor of 32-bit integers (of numel entries, if given): its pointer -- a workspace pointer when it is empty."""
+    if not t.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % t.device)
+    if t.element_size() != 4 or t.is_floating_point() or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise TypeError('%s: a contiguous device tensor of %s32-bit integers' % (name, '' if numel is None else '%d ' % numel))
+    return t.data_ptr() if t.numel() else workspace(16, 1).data_ptr()
+
+
+def cluster_exchange(rows, nbits, rowptr, cols, pairs, uniforms):
+    """One round of isoenergetic cluster moves over disjoint pairs of packed rows, IN PLACE (tn_cluster_exchange): rows (M, ld) int64 /
+    uint64 device tensor whose first ceil(nbits / 64) words hold a row of nbits bits, layout of tnac4o_amd/overlap.py; rowptr
+    (nbits + 1,), cols (nnz,) int32 device tensors, the CSR of the graph over the bits; pairs (P, 2) int32 device tensor of row indices,
+    every row in at most one pair; uniforms (P,) float64 device tensor in [0, 1).  Returns (size, diff), (P,) int32 device tensors: the
+    size of the cluster that was flipped in both rows of a pair and the number of bits in which the two rows differ (both -1 for a pair
+    with an index outside [0, M))."""
+    M, ld = _packed_rows(rows)
+    nbits = int(nbits)
+    nwords = -(-max(nbits, 0) // 64)
+    if rows.shape[1] < nwords:
+        raise ValueError('rows hold %d words, %d bits take %d' % (rows.shape[1], nbits, nwords))
+    p_rowptr = _i32_operand(rowptr, 'rowptr', max(nbits, 0) + 1)
+    p_cols = _i32_operand(cols, 'cols')
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise TypeError('pairs: a (P, 2) tensor')
+    P = int(pairs.shape[0])
+    p_pairs = _i32_operand(pairs, 'pairs')
+    _need_gpu(uniforms)
+    if not uniforms.is_contiguous() or uniforms.numel() != P:
+        raise TypeError('uniforms: a contiguous device tensor of P float64')
+    size = torch.empty(P, dtype=torch.int32, device=rows.device)
+    diff = torch.empty(P, dtype=torch.int32, device=rows.device)
+    check(lib().tn_cluster_exchange(rows.data_ptr() if M else p_pairs, M, nbits, max(ld, nwords), p_rowptr, p_cols, int(cols.numel()), p_pairs, P,
+                                    uniforms.data_ptr() if P else p_pairs, size.data_ptr() if P else p_pairs, diff.data_ptr() if P else p_pairs,
+                                    _stream()))
+    return size, diff

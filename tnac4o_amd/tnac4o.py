@@ -1139,6 +1139,33 @@ class tnac4o:
         self.probability = self.sample_log2Z = self.log2Z_lower = self.log2Z_estimate = None
         return energy
 
+    def exchange_clusters(self, rounds=1, pairs=None, uniforms=None):
+        """Move the stored configurations by isoenergetic cluster moves on pairs of them (Houdayer's move in its form for arbitrary
+        graphs; tn_cluster_exchange, tnac4o_amd/exchange.py): for a pair of replicas a, b one of the spins in which they differ is
+        picked at random, and the connected cluster of differing spins that contains it -- connected along the couplings of J -- is
+        flipped in both.  Ising only (RMF: ValueError); needs at least two stored states; runs no contraction, needs no boundary
+        MPS and does not depend on the rotation (the bits are in model order).
+        The move is rejection-free and its own inverse with the same selection probability, so it leaves the law of a pair
+        invariant WHEN THE STORED STATES ARE SAMPLES AT ONE COMMON TEMPERATURE (sample_boltzmann, relax_samples in heat-bath mode);
+        alternated with relax_samples it is the usual ergodic combination.  It conserves E_a + E_b, fields included, and the
+        partners' overlap q_ab (the set of differing spins stays as it is).  A cluster that equals ALL the differing spins merely
+        swaps the two replicas: that is common at high temperature on these graphs, where the differing spins percolate.  Between
+        two quenched states the move is an energy-conserving recombination: relax_samples(mode='quench', sweeps=None) after it can
+        leave minima the cell quench alone cannot.
+        rounds: rounds of moves; in a round every state is in at most one pair.  pairs: None = for each round
+        np.random.permutation(M)[:2 P].reshape(P, 2) with P = M // 2 from numpy's global generator, or an integer numpy array
+        (rounds, P, 2) of indices into `states`, none twice within a round.  uniforms: None = np.random.rand(rounds, P), or a
+        (rounds, P) float64 array / device tensor in [0, 1): pair p of a round with cnt differing spins takes the
+        min(floor(u cnt), cnt - 1)-th of them in model order as its seed.  Every pairing is drawn before any uniform; anything else
+        is a ValueError raised before any device work.
+        Stores states (M, Nx*Ny) in model cell order, energy (M,) in the bits relax_samples and scored_energy produce,
+        exchange_energy_before (M,), exchange_pairs (rounds, P, 2), exchange_cluster_sizes (rounds, P) (returned; 0 = the partners
+        were equal) and exchange_differing (rounds, P) = the spins in which the partners differ.  probability, sample_log2Z,
+        log2Z_lower and log2Z_estimate are set to None, as relax_samples does.  rhoT, degeneracy and every thermal and scored attribute
+        are left alone.  More than 65534 active spins: NotImplementedError; there is no host fallback."""
+        from . import exchange
+        return exchange.exchange_clusters(self, rounds, pairs, uniforms)
+
     # ------------------------------------------------------------------------------------ thermal marginals (GPU)
     def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
         """Boltzmann marginal of every cell and magnetisation of every spin at the solver's beta, from both boundary MPS.
