@@ -651,6 +651,54 @@ int tn_cell_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, 
 int tn_cluster_exchange(uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const int32_t* rowptr, const int32_t* cols, int64_t nnz,
                         const int32_t* pairs, int64_t P, const double* uniforms, int32_t* size_out, int32_t* diff_out, void* stream);
 
+/* ---- K12: parallel tempering with isoenergetic cluster moves (no counterpart in the reference: tnac4o.temper_samples) ---------------
+ * tn_temper: `rounds` rounds of heat-bath sweeps, cluster moves and temperature swaps over a population of M = R T configurations, IN
+ * PLACE in states (DEVICE, M x Nx*Ny int16, tn_cell_sweep's layout; cells: the same HOST table).  Row m belongs to chain c = m / T.
+ * betas (HOST, T doubles): strictly increasing, positive, finite.  The temperature assignment (DEVICE, in / out): tidx (M int32) = the
+ * temperature index of every row, slot (R x T int32) = the row of chain c that sits at temperature t; slot[c][tidx[m]] == m on entry is
+ * the caller's duty (a fresh run: tidx[m] = m % T, slot[c][t] = c T + t).  A swap exchanges temperature LABELS (two entries of slot,
+ * two of tidx), never rows.  Round r of the call has the global index round0 + r:
+ *  1. `sweeps` heat-bath sweeps of tn_cell_sweep's move (mode 0) with row m at betas[tidx[m]] (a tidx outside [0, T) is read as 0):
+ *     the same conditional energy with the same additions in the same order, the same draw rule and chunked running sum, the same
+ *     handling of a state outside its cell, the same TN_CELL_SWEEP_LDS staging -- one source of the move, instantiated with a
+ *     per-row beta.  The number of (round r, sweep j, cell k in walk order, row m) is usweep[((r sweeps + j) Nx Ny + k) ldu + m].
+ *  2. Cluster moves, only when nbits > 0: for every temperature t >= cluster_from (Tc = T - cluster_from of them) and every chain pair
+ *     p = (ca, cb) of cpairs (DEVICE, rounds x Pc x 2 int32 chain indices, disjoint within a round: the caller's duty), the move of
+ *     tn_cluster_exchange on the row pair (slot[ca][t], slot[cb][t]) with the uniform ucl[(r Tc + (t - cluster_from)) Pc + p]; a pair
+ *     with a chain index outside [0, R) or a slot entry outside [0, M) moves nothing and reports -1, -1.  Before the moves all rows are
+ *     converted to packed spin bits in the workspace, afterwards back: bitcell (DEVICE, nbits x 2 int32) = (cell k in walk order, bit
+ *     j of its state) of every row position, cellbits (DEVICE, Nx*Ny x nbmax int32) = the row position of bit j of cell k's state,
+ *     -1 beyond the cell's spins; a row bit is 1 - state bit (binary_states / states_from_binary).  One thread gathers each (row, word)
+ *     and each (row, cell): no word is written by two threads; an entry of either table outside its range is skipped, never used
+ *     as an index.  A state outside its cell is converted as 0, and a cell is written back only where the bits give another state
+ *     than it was read as.  rowptr, cols, nnz: the CSR of tn_cluster_exchange.
+ *  3. E[m] = the energy of every row by tn_cell_sweep's energy pass (the bits of its energy_out).
+ *  4. Temperature swaps, par = (round0 + r) & 1: for every chain c and every t with t % 2 == par and t + 1 < T, a = slot[c][t],
+ *     b = slot[c][t+1], D = (betas[t+1] - betas[t]) * (E[b] - E[a]) -- two subtractions and one multiplication in fp64, not contracted
+ *     --; accepted iff D >= 0 or uswap[(r R + c) (T - 1) + t] < exp(D); a NaN energy never accepts.  swap_accepted[t] and
+ *     swap_attempted[t] (DEVICE, T - 1 int32 each) are ADDED to, not cleared: they accumulate over calls.
+ * Results (DEVICE): energy_out (M) = the energies of the final states (rounds = 0 writes nothing else).  Optional, NULL allowed:
+ * energy_trace (rounds x M doubles) and tidx_trace (rounds x M int32), E and tidx after step 4 of every round; size_out and diff_out
+ * (rounds x Tc x Pc int32), tn_cluster_exchange's outputs of every move in the order of ucl.
+ * Degenerate forms, all valid: T = 1 (no swap; uswap and the counters may be NULL); nbits = 0 (no cluster move; the bit tables, the
+ * graph, cpairs and ucl may be NULL); Pc = 0 or cluster_from = T; sweeps = 0 (usweep may be NULL); rounds = 0.
+ * Determinism: the result is a function of the inputs alone.  It does not depend on the grid, and it does not depend on how the
+ * rounds are cut into calls: calls with round0 advanced, the slices of usweep, cpairs, ucl and uswap that belong to their rounds, and
+ * tidx, slot and the counters carried over give the same bits as one call.  With nbits = 0 the chains are independent: the result
+ * of a chain does not depend on R or on which other chains share the call.
+ * ws: tn_temper_ws_bytes(Nx, Ny, M, T, nbits, Pc) (0 for a shape the call refuses): the table of the cells, the betas, the packed rows,
+ * the row pairs of a round.  Asynchronous on `stream`; no host synchronisation, no barrier across workgroups, no global atomics (the
+ * counters are reduced in the one workgroup that serves a temperature).
+ * Limits: those of tn_cell_sweep; M a multiple of T; 0 <= nbits <= 65534; 1 <= nbmax <= 15; 0 <= cluster_from <= T; 0 <= 2 Pc <= R.
+ * Errors: -1 argument (the message names the limit), -3 workspace too small; both before any launch, nothing is written. */
+int64_t tn_temper_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t T, int64_t nbits, int64_t Pc);
+int tn_temper(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t T, const double* betas, int16_t* states, int32_t* tidx,
+              int32_t* slot, int64_t round0, int64_t rounds, int64_t sweeps, const double* usweep, int64_t ldu, int64_t nbits, int64_t nbmax,
+              const int32_t* cellbits, const int32_t* bitcell, const int32_t* rowptr, const int32_t* cols, int64_t nnz, int64_t cluster_from,
+              const int32_t* cpairs, int64_t Pc, const double* ucl, const double* uswap, double* energy_out, int32_t* swap_accepted,
+              int32_t* swap_attempted, double* energy_trace, int32_t* tidx_trace, int32_t* size_out, int32_t* diff_out, void* ws, int64_t ws_bytes,
+              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@
 // pair, up to four words per thread, the same loop with __syncthreads_or.  The CSR stays in global memory: it is shared by all
 // pairs and lives in L2.  Nothing read from rowptr, cols or pairs is used as an index unchecked.
 #include "common.h"
+#include "sweep.h"
 
 namespace tn {
 
@@ -229,6 +230,27 @@ __global__ void __launch_bounds__(256) exchange_block_kernel(uint64_t* __restric
 
 }  // namespace
 
+int64_t cluster_exchange_max_nbits() { return EX_MAX_NBITS; }
+
+// the launch of a round (sweep.h): tn_cluster_exchange below and tn_temper, which has checked the same limits
+int cluster_exchange_launch(hipStream_t st, uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const int32_t* rowptr, const int32_t* cols,
+                            int64_t nnz, const int32_t* pairs, int64_t P, const double* uniforms, int32_t* size_out, int32_t* diff_out) {
+    const int64_t nwords = cdiv(nbits, 64);
+    const int used = (int)(nbits - (nwords - 1) * 64);
+    const uint64_t last_mask = used == 64 ? ~(uint64_t)0 : (((uint64_t)1 << used) - 1);
+    if (nbits <= EX_WAVE_BITS) {
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(exchange_wave_kernel, dim3((unsigned)cdiv(P, EX_WAVES)), dim3(64 * EX_WAVES), 0, st, rows, M,
+                                                         (int)nbits, (int)nwords, ldr, last_mask, rowptr, cols, (int)nnz, pairs, P, uniforms, size_out,
+                                                         diff_out));
+        TN_CHECK_LAUNCH("exchange_wave_kernel");
+    } else {
+        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(exchange_block_kernel, dim3((unsigned)P), dim3(256), 0, st, rows, M, (int)nbits, (int)nwords, ldr,
+                                                         last_mask, rowptr, cols, (int)nnz, pairs, P, uniforms, size_out, diff_out));
+        TN_CHECK_LAUNCH("exchange_block_kernel");
+    }
+    return 0;
+}
+
 }  // namespace tn
 
 using namespace tn;
@@ -250,20 +272,7 @@ int tn_cluster_exchange(uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, c
     TN_CHECK_ARG(ldr >= nwords, "ldr shorter than a row of ceil(nbits / 64) words");
     if (P == 0) return 0;
     TN_CHECK_ARG(rows && rowptr && pairs && uniforms && size_out && diff_out && (cols || nnz == 0), "null operand");
-    hipStream_t st = (hipStream_t)stream;
-    const int used = (int)(nbits - (nwords - 1) * 64);
-    const uint64_t last_mask = used == 64 ? ~(uint64_t)0 : (((uint64_t)1 << used) - 1);
-    if (nbits <= EX_WAVE_BITS) {
-        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(exchange_wave_kernel, dim3((unsigned)cdiv(P, EX_WAVES)), dim3(64 * EX_WAVES), 0, st, rows, M,
-                                                         (int)nbits, (int)nwords, ldr, last_mask, rowptr, cols, (int)nnz, pairs, P, uniforms, size_out,
-                                                         diff_out));
-        TN_CHECK_LAUNCH("exchange_wave_kernel");
-    } else {
-        TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(exchange_block_kernel, dim3((unsigned)P), dim3(256), 0, st, rows, M, (int)nbits, (int)nwords, ldr,
-                                                         last_mask, rowptr, cols, (int)nnz, pairs, P, uniforms, size_out, diff_out));
-        TN_CHECK_LAUNCH("exchange_block_kernel");
-    }
-    return 0;
+    return cluster_exchange_launch((hipStream_t)stream, rows, M, nbits, ldr, rowptr, cols, nnz, pairs, P, uniforms, size_out, diff_out);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 // A state outside [0, q) of its cell is never used as an index: as a neighbour it is read as 0, as the current state of a quench its
 // energy counts as +inf.
 #include "walk.h"
+#include "sweep.h"
 
 #pragma clang fp contract(off)
 
@@ -33,14 +34,6 @@ constexpr int64_t SWEEP_LDS_DEFAULT = 32 * 1024;    // ... and what they may tak
 constexpr int SWEEP_TILE = 256;                      // samples per workgroup = its threads (a result never depends on it)
 constexpr int SWEEP_PUT = 40;                        // table entries one launch of put_cells_kernel carries in its arguments
 
-struct SweepCell {                     // what a sweep reads of a cell (device pointers)
-    const double* Es;
-    const double* E1;
-    const double* E4;
-    const int64_t* left_map;
-    const int64_t* up_map;
-    int32_t q, e1cols, e4cols, staged;  // staged: the tables go to LDS
-};
 struct SweepCellPack { SweepCell c[SWEEP_PUT]; };
 
 // The table of the call travels in kernel arguments (copied when the launch is enqueued): no staging buffer has to outlive the call.
@@ -57,6 +50,7 @@ struct SweepArgs {
     int64_t Nx, Ny, M, ldu, ntiles;
     int colour, mode;
     double beta;
+    SweepBetas rb;                      // the per-row-beta instances only (tn_temper): beta of sample m = rb.betas[rb.tidx[m]]
 };
 
 __device__ __forceinline__ int in_cell(int s, int q) { return (s >= 0 && s < q) ? s : 0; }
@@ -68,9 +62,9 @@ struct SweepPrep {
     double u[SWEEP_TILE];
 };
 
-template <int W, int NJ, bool LDS>
+template <int W, int NJ, bool LDS, bool RB>
 __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const SweepCell& c, const SweepCell* R, const SweepCell* B, int64_t k, bool has_left,
-                                           bool has_up, const double* tEs, const double* tE1, const double* tE4, const SweepPrep& p, int64_t m0, int64_t m1) {
+                                           bool has_up, const double* tEs, const double* tE1, const double* tE4, const SweepPrep& p, const double* pbeta, int64_t m0, int64_t m1) {
     constexpr int G = 64 / W, NR = NJ > 0 ? NJ : 1;
     const int tid = threadIdx.x, lane = tid & 63, l = lane % W, g = (tid >> 6) * G + lane / W;
     const int q = c.q, nchunk = (q + W - 1) / W;
@@ -157,7 +151,9 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const SweepCell& 
             const double u = p.u[i];
             double wv[NR], cv[NR];
             double carry = 0.0;
-            auto weight = [&](int s, double e) { return s < q ? exp(-a.beta * (e - be)) : 0.0; };
+            double beta = a.beta;
+            if constexpr (RB) beta = pbeta[i];
+            auto weight = [&](int s, double e) { return s < q ? exp(-beta * (e - be)) : 0.0; };
             auto scan = [&](double v) {                          // inclusive over the group, lane order
 #pragma unroll
                 for (int o = 1; o < W; o <<= 1) {
@@ -227,7 +223,8 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const SweepCell& 
 // cells do not pay for the registers of the large ones; a workgroup whose cell belongs to another class returns at once.
 __host__ __device__ inline int sweep_class(int64_t q) { return q <= 8 ? 0 : q <= 32 ? 1 : q <= 256 ? 2 : 3; }
 
-template <int CLS>
+// RB: every sample at its own beta (staged next to what SweepPrep holds); the body of the move is the one above
+template <int CLS, bool RB>
 __global__ __launch_bounds__(256) void cell_sweep_kernel(SweepArgs a) {
     extern __shared__ double lds[];
     const int64_t slot = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
@@ -245,6 +242,15 @@ __global__ __launch_bounds__(256) void cell_sweep_kernel(SweepArgs a) {
     const double* tE1 = c.E1;
     const double* tE4 = c.E4;
     __shared__ SweepPrep prep;
+    const double* pbeta = nullptr;
+    if constexpr (RB) {
+        __shared__ double sbeta[SWEEP_TILE];
+        if ((int64_t)threadIdx.x < m1 - m0) {
+            const int64_t t = a.rb.tidx[m0 + threadIdx.x];
+            sbeta[threadIdx.x] = a.rb.betas[t >= 0 && t < a.rb.T ? t : 0];
+        }
+        pbeta = sbeta;
+    }
     if ((int64_t)threadIdx.x < m1 - m0) {
         const int i = threadIdx.x;
         const int64_t m = m0 + i;
@@ -272,8 +278,8 @@ __global__ __launch_bounds__(256) void cell_sweep_kernel(SweepArgs a) {
     __syncthreads();
 #define SWEEP_RUN(W, NJ)                                                                             \
     do {                                                                                             \
-        if (c.staged) sweep_tile<W, NJ, true>(a, c, R, B, k, has_left, has_up, tEs, tE1, tE4, prep, m0, m1);  \
-        else sweep_tile<W, NJ, false>(a, c, R, B, k, has_left, has_up, tEs, tE1, tE4, prep, m0, m1);          \
+        if (c.staged) sweep_tile<W, NJ, true, RB>(a, c, R, B, k, has_left, has_up, tEs, tE1, tE4, prep, pbeta, m0, m1);  \
+        else sweep_tile<W, NJ, false, RB>(a, c, R, B, k, has_left, has_up, tEs, tE1, tE4, prep, pbeta, m0, m1);        \
     } while (0)
     if constexpr (CLS == 0) SWEEP_RUN(8, 1);
     else if constexpr (CLS == 1) SWEEP_RUN(32, 1);
@@ -282,10 +288,10 @@ __global__ __launch_bounds__(256) void cell_sweep_kernel(SweepArgs a) {
 #undef SWEEP_RUN
 }
 
-template <int CLS>
+template <int CLS, bool RB>
 int launch_sweep(hipStream_t st, const SweepArgs& a, int64_t nblocks, int64_t lds) {
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)cell_sweep_kernel<CLS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(cell_sweep_kernel<CLS>, dim3((unsigned)nblocks), dim3(256), (size_t)lds, st, a));
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)cell_sweep_kernel<CLS, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL((cell_sweep_kernel<CLS, RB>), dim3((unsigned)nblocks), dim3(256), (size_t)lds, st, a));
     TN_CHECK_LAUNCH("cell_sweep_kernel");
     return 0;
 }
@@ -344,6 +350,92 @@ int64_t sweep_lds_limit() { return std::min(std::max<int64_t>(env_i64("TN_CELL_S
 
 }  // namespace
 
+// ---- what tn_temper shares (sweep.h) ---------------------------------------------------------------------------------------------
+#define SWEEP_CHECK(cond, msg)                      \
+    do {                                            \
+        if (!(cond)) {                              \
+            set_error("%s: %s", who, msg);          \
+            return -1;                              \
+        }                                           \
+    } while (0)
+
+int64_t sweep_cells_bytes(int64_t Nx, int64_t Ny) { return Nx * Ny * (int64_t)sizeof(SweepCell); }
+
+int sweep_plan(const char* who, int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, SweepPlan& plan) {
+    const int64_t ncell = Nx * Ny;
+    const int64_t lds_limit = sweep_lds_limit();
+    plan.Nx = Nx; plan.Ny = Ny; plan.M = M;
+    plan.tab.assign((size_t)ncell, SweepCell{});
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < 4; ++k) { plan.lds_bytes[c][k] = 0; plan.present[c][k] = false; }   // per colour and class of cells
+    for (int64_t k = 0; k < ncell; ++k) {
+        const tn_beam_cell& c = cells[k];
+        const int64_t ny = k / Nx, nx = k % Nx;
+        SWEEP_CHECK(c.q >= 1 && c.q <= 32767 && c.Es, "cells: q outside 1 .. 32767, or Es null");
+        SWEEP_CHECK(nx == 0 || (c.E1 && c.e1cols >= 1 && c.e1cols < ((int64_t)1 << 31)), "cells: E1 null or e1cols out of range right of column 0");
+        SWEEP_CHECK(ny == 0 || (c.E4 && c.e4cols >= 1 && c.e4cols < ((int64_t)1 << 31)), "cells: E4 null or e4cols out of range below row 0");
+        SweepCell& t = plan.tab[(size_t)k];
+        t.Es = c.Es; t.E1 = nx > 0 ? c.E1 : nullptr; t.E4 = ny > 0 ? c.E4 : nullptr;
+        t.left_map = nx > 0 ? c.left_map : nullptr; t.up_map = ny > 0 ? c.up_map : nullptr;
+        t.q = (int32_t)c.q; t.e1cols = nx > 0 ? (int32_t)c.e1cols : 1; t.e4cols = ny > 0 ? (int32_t)c.e4cols : 1;
+        const int64_t ldq = c.q | 1;
+        const int64_t bytes = (c.q + (nx > 0 ? c.e1cols * ldq : 0) + (ny > 0 ? c.e4cols * ldq : 0)) * 8;
+        t.staged = bytes <= lds_limit ? 1 : 0;
+        const int colour = (int)((ny + nx) & 1), cls = sweep_class(c.q);
+        plan.present[colour][cls] = true;
+        if (t.staged) plan.lds_bytes[colour][cls] = std::max(plan.lds_bytes[colour][cls], bytes);
+    }
+    plan.ntiles = cdiv(M, SWEEP_TILE);
+    const int64_t slots = Ny * ((Nx + 1) / 2);
+    plan.nblocks = 0;
+    SWEEP_CHECK(!__builtin_mul_overflow(slots, plan.ntiles, &plan.nblocks) && plan.nblocks < ((int64_t)1 << 31),
+                "cells x tiles of samples exceed 2^31 workgroups: fewer samples per call");
+    return 0;
+}
+#undef SWEEP_CHECK
+
+int sweep_put_cells(hipStream_t st, const SweepPlan& plan, SweepCell* dev) {
+    const int64_t ncell = plan.Nx * plan.Ny;
+    for (int64_t k0 = 0; k0 < ncell; k0 += SWEEP_PUT) {
+        SweepCellPack pack;
+        const int n = (int)std::min<int64_t>(SWEEP_PUT, ncell - k0);
+        memset((void*)&pack, 0, sizeof(pack));
+        for (int i = 0; i < n; ++i) pack.c[i] = plan.tab[(size_t)(k0 + i)];
+        hipLaunchKernelGGL(put_cells_kernel, dim3(1), dim3(64), 0, st, pack, n, dev + k0);
+        TN_CHECK_LAUNCH("put_cells_kernel");
+    }
+    return 0;
+}
+
+int sweep_once(hipStream_t st, const SweepPlan& plan, const SweepCell* dev, int16_t* states, int mode, double beta, const SweepBetas& rb,
+               const double* uniforms, int64_t ldu, uint8_t* chg) {
+    for (int colour = 0; colour < 2; ++colour) {
+        SweepArgs a;
+        a.cells = dev; a.states = states; a.uniforms = uniforms; a.chg = chg;
+        a.Nx = plan.Nx; a.Ny = plan.Ny; a.M = plan.M; a.ldu = ldu; a.ntiles = plan.ntiles; a.colour = colour; a.mode = mode; a.beta = beta;
+        a.rb = rb;
+        const int64_t* lds = plan.lds_bytes[colour];
+        if (rb.betas) {
+            if (plan.present[colour][0]) BS((launch_sweep<0, true>(st, a, plan.nblocks, lds[0])));
+            if (plan.present[colour][1]) BS((launch_sweep<1, true>(st, a, plan.nblocks, lds[1])));
+            if (plan.present[colour][2]) BS((launch_sweep<2, true>(st, a, plan.nblocks, lds[2])));
+            if (plan.present[colour][3]) BS((launch_sweep<3, true>(st, a, plan.nblocks, lds[3])));
+        } else {
+            if (plan.present[colour][0]) BS((launch_sweep<0, false>(st, a, plan.nblocks, lds[0])));
+            if (plan.present[colour][1]) BS((launch_sweep<1, false>(st, a, plan.nblocks, lds[1])));
+            if (plan.present[colour][2]) BS((launch_sweep<2, false>(st, a, plan.nblocks, lds[2])));
+            if (plan.present[colour][3]) BS((launch_sweep<3, false>(st, a, plan.nblocks, lds[3])));
+        }
+    }
+    return 0;
+}
+
+int sweep_energy(hipStream_t st, const SweepPlan& plan, const SweepCell* dev, const int16_t* states, double* energy) {
+    hipLaunchKernelGGL(sweep_energy_kernel, dim3((unsigned)cdiv(plan.M, 256)), dim3(256), 0, st, dev, states, plan.Nx, plan.Ny, plan.M, energy);
+    TN_CHECK_LAUNCH("sweep_energy_kernel");
+    return 0;
+}
+
 }  // namespace tn
 
 using namespace tn;
@@ -375,30 +467,8 @@ int tn_cell_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, 
     const int64_t need = tn_cell_sweep_ws_bytes(Nx, Ny, M);
     TN_CHECK_ARG(need > 0, "Nx x Ny x M: too large");
     const int64_t ncell = Nx * Ny;
-    const int64_t lds_limit = sweep_lds_limit();
-    std::vector<SweepCell> tab((size_t)ncell);
-    int64_t lds_bytes[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // per colour and class of cells
-    bool present[2][4] = {{false, false, false, false}, {false, false, false, false}};
-    for (int64_t k = 0; k < ncell; ++k) {
-        const tn_beam_cell& c = cells[k];
-        const int64_t ny = k / Nx, nx = k % Nx;
-        TN_CHECK_ARG(c.q >= 1 && c.q <= 32767 && c.Es, "cells: q outside 1 .. 32767, or Es null");
-        TN_CHECK_ARG(nx == 0 || (c.E1 && c.e1cols >= 1 && c.e1cols < ((int64_t)1 << 31)), "cells: E1 null or e1cols out of range right of column 0");
-        TN_CHECK_ARG(ny == 0 || (c.E4 && c.e4cols >= 1 && c.e4cols < ((int64_t)1 << 31)), "cells: E4 null or e4cols out of range below row 0");
-        SweepCell& t = tab[(size_t)k];
-        t.Es = c.Es; t.E1 = nx > 0 ? c.E1 : nullptr; t.E4 = ny > 0 ? c.E4 : nullptr;
-        t.left_map = nx > 0 ? c.left_map : nullptr; t.up_map = ny > 0 ? c.up_map : nullptr;
-        t.q = (int32_t)c.q; t.e1cols = nx > 0 ? (int32_t)c.e1cols : 1; t.e4cols = ny > 0 ? (int32_t)c.e4cols : 1;
-        const int64_t ldq = c.q | 1;
-        const int64_t bytes = (c.q + (nx > 0 ? c.e1cols * ldq : 0) + (ny > 0 ? c.e4cols * ldq : 0)) * 8;
-        t.staged = bytes <= lds_limit ? 1 : 0;
-        const int colour = (int)((ny + nx) & 1), cls = sweep_class(c.q);
-        present[colour][cls] = true;
-        if (t.staged) lds_bytes[colour][cls] = std::max(lds_bytes[colour][cls], bytes);
-    }
-    const int64_t ntiles = cdiv(M, SWEEP_TILE), slots = Ny * ((Nx + 1) / 2);
-    int64_t nblocks = 0;
-    TN_CHECK_ARG(!__builtin_mul_overflow(slots, ntiles, &nblocks) && nblocks < ((int64_t)1 << 31), "cells x tiles of samples exceed 2^31 workgroups: fewer samples per call");
+    SweepPlan plan;
+    BS(sweep_plan(__func__, Nx, Ny, cells, M, plan));
     TN_CHECK_ARG(ws, "ws: null");
     if (ws_bytes < need) {
         set_error("tn_cell_sweep: workspace too small (%lld bytes, tn_cell_sweep_ws_bytes asks for %lld)", (long long)ws_bytes, (long long)need);
@@ -406,26 +476,12 @@ int tn_cell_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, 
     }
     hipStream_t st = (hipStream_t)stream;
     const SweepWs w = sweep_layout(ws, Nx, Ny, M);
-    for (int64_t k0 = 0; k0 < ncell; k0 += SWEEP_PUT) {
-        SweepCellPack pack;
-        const int n = (int)std::min<int64_t>(SWEEP_PUT, ncell - k0);
-        memset((void*)&pack, 0, sizeof(pack));
-        for (int i = 0; i < n; ++i) pack.c[i] = tab[(size_t)(k0 + i)];
-        hipLaunchKernelGGL(put_cells_kernel, dim3(1), dim3(64), 0, st, pack, n, w.cells + k0);
-        TN_CHECK_LAUNCH("put_cells_kernel");
-    }
+    BS(sweep_put_cells(st, plan, w.cells));
     const bool count = moves_out || last_moves_out;
     const unsigned mblk = (unsigned)cdiv(M, 256);
+    const SweepBetas one{nullptr, nullptr, 0};
     for (int64_t j = 0; j < sweeps; ++j) {
-        for (int colour = 0; colour < 2; ++colour) {
-            SweepArgs a;
-            a.cells = w.cells; a.states = states; a.uniforms = mode == 0 ? uniforms + j * ncell * ldu : nullptr; a.chg = count ? w.chg : nullptr;
-            a.Nx = Nx; a.Ny = Ny; a.M = M; a.ldu = ldu; a.ntiles = ntiles; a.colour = colour; a.mode = mode; a.beta = beta;
-            if (present[colour][0]) BS(launch_sweep<0>(st, a, nblocks, lds_bytes[colour][0]));
-            if (present[colour][1]) BS(launch_sweep<1>(st, a, nblocks, lds_bytes[colour][1]));
-            if (present[colour][2]) BS(launch_sweep<2>(st, a, nblocks, lds_bytes[colour][2]));
-            if (present[colour][3]) BS(launch_sweep<3>(st, a, nblocks, lds_bytes[colour][3]));
-        }
+        BS(sweep_once(st, plan, w.cells, states, mode, beta, one, mode == 0 ? uniforms + j * ncell * ldu : nullptr, ldu, count ? w.chg : nullptr));
         if (count) {
             hipLaunchKernelGGL(sweep_moves_kernel, dim3(mblk), dim3(256), 0, st, w.chg, ncell, M, j == 0 ? 1 : 0, moves_out, last_moves_out);
             TN_CHECK_LAUNCH("sweep_moves_kernel");
@@ -435,9 +491,7 @@ int tn_cell_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, 
         if (moves_out) BSH(hipMemsetAsync(moves_out, 0, (size_t)M * 4, st), "tn_cell_sweep: clear");
         if (last_moves_out) BSH(hipMemsetAsync(last_moves_out, 0, (size_t)M * 4, st), "tn_cell_sweep: clear");
     }
-    hipLaunchKernelGGL(sweep_energy_kernel, dim3(mblk), dim3(256), 0, st, w.cells, states, Nx, Ny, M, energy_out);
-    TN_CHECK_LAUNCH("sweep_energy_kernel");
-    return 0;
+    return sweep_energy(st, plan, w.cells, states, energy_out);
 }
 
 }  // extern "C"

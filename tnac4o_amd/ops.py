@@ -1124,3 +1124,74 @@ def cluster_exchange(rows, nbits, rowptr, cols, pairs, uniforms):
                                     uniforms.data_ptr() if P else p_pairs, size.data_ptr() if P else p_pairs, diff.data_ptr() if P else p_pairs,
                                     _stream()))
     return size, diff
+
+
+def temper(cells, Nx, Ny, betas, states, tidx, slot, round0, rounds, sweeps, usweep=None, bits=None, cluster_from=0, cpairs=None, ucl=None,
+           uswap=None, accepted=None, attempted=None, record=False):
+    """`rounds` rounds of parallel tempering with cluster moves, IN PLACE in states, tidx, slot and the two counters (tn_temper;
+    include/tnpeps.h, K12).  cells: the ctypes tn_beam_cell array of the lattice (relax.EnergyCells(...).cells); betas: T host floats,
+    strictly increasing; states (M, Nx*Ny) int16, tidx (M,), slot (R, T), accepted / attempted (T - 1,) int32 device tensors (the
+    counters may be None when T = 1); usweep (rounds, sweeps, Nx*Ny, ld >= M) float64 device tensor, None with sweeps = 0; bits: None
+    (no cluster moves) or (nbits, cellbits (Nx*Ny, nbmax), bitcell (nbits, 2), rowptr (nbits + 1,), cols (nnz,)) with int32 device
+    tensors; cpairs (rounds, Pc, 2) int32, ucl (rounds, T - cluster_from, Pc) and uswap (rounds, R, T - 1) float64 device tensors.
+    Returns dict(energy (M,) float64) and, with record, energy_trace (rounds, M), tidx_trace (rounds, M), sizes and differing
+    (rounds, T - cluster_from, Pc) int32 (None without bits): device tensors."""
+    if not states.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % states.device)
+    if states.dim() != 2 or states.dtype != torch.int16 or not states.is_contiguous() or states.shape[1] != Nx * Ny:
+        raise TypeError('states: a contiguous (M, Nx*Ny) int16 device tensor')
+    M, T = int(states.shape[0]), len(betas)
+    if T < 1 or M % T:
+        raise ValueError('M = %d is no multiple of the %d temperatures' % (M, T))
+    R, rounds, sweeps = M // T, int(rounds), int(sweeps)
+    dev = states.device
+    p_tidx, p_slot = _i32_operand(tidx, 'tidx', M), _i32_operand(slot, 'slot', M)
+    c_betas = (C.c_double * T)(*[float(b) for b in betas])
+    p_u, ldu = None, 0
+    if sweeps > 0 and rounds > 0:
+        _need_gpu(usweep)
+        if usweep.dtype != torch.float64 or not usweep.is_contiguous() or usweep.dim() != 4 or tuple(usweep.shape[:3]) != (rounds, sweeps, Nx * Ny):
+            raise TypeError('usweep: a contiguous (rounds, sweeps, Nx*Ny, ld) float64 device tensor')
+        p_u, ldu = usweep.data_ptr(), int(usweep.shape[3])
+    nbits = nbmax = nnz = Pc = 0
+    p_cb = p_bc = p_rp = p_cols = p_cp = p_ucl = None
+    Tc = T - int(cluster_from)
+    if bits is not None:
+        nbits, cellbits, bitcell, rowptr, cols = bits
+        nbits, nbmax, nnz = int(nbits), int(cellbits.shape[1]), int(cols.numel())
+        p_cb, p_bc = _i32_operand(cellbits, 'cellbits', Nx * Ny * nbmax), _i32_operand(bitcell, 'bitcell', 2 * nbits)
+        p_rp, p_cols = _i32_operand(rowptr, 'rowptr', nbits + 1), _i32_operand(cols, 'cols')
+        if cpairs is not None:
+            if cpairs.dim() != 3 or cpairs.shape[0] != rounds or cpairs.shape[2] != 2:
+                raise TypeError('cpairs: a (rounds, Pc, 2) tensor')
+            Pc = int(cpairs.shape[1])
+            p_cp = _i32_operand(cpairs, 'cpairs')
+            _need_gpu(ucl)
+            if ucl.dtype != torch.float64 or not ucl.is_contiguous() or tuple(ucl.shape) != (rounds, Tc, Pc):
+                raise TypeError('ucl: a contiguous (rounds, T - cluster_from, Pc) float64 device tensor')
+            p_ucl = ucl.data_ptr() if ucl.numel() else p_cp
+    p_us = p_acc = p_att = None
+    if T > 1:
+        p_acc, p_att = _i32_operand(accepted, 'accepted', T - 1), _i32_operand(attempted, 'attempted', T - 1)
+        _need_gpu(uswap)
+        if uswap.dtype != torch.float64 or not uswap.is_contiguous() or tuple(uswap.shape) != (rounds, R, T - 1):
+            raise TypeError('uswap: a contiguous (rounds, R, T - 1) float64 device tensor')
+        p_us = uswap.data_ptr() if uswap.numel() else p_tidx
+    out = dict(energy=torch.empty(M, dtype=torch.float64, device=dev), energy_trace=None, tidx_trace=None, sizes=None, differing=None)
+    p_et = p_tt = p_sz = p_df = None
+    if record:
+        out['energy_trace'] = torch.empty((rounds, M), dtype=torch.float64, device=dev)
+        out['tidx_trace'] = torch.empty((rounds, M), dtype=torch.int32, device=dev)
+        if rounds:
+            p_et, p_tt = out['energy_trace'].data_ptr(), out['tidx_trace'].data_ptr()
+        if bits is not None:
+            out['sizes'] = torch.empty((rounds, Tc, Pc), dtype=torch.int32, device=dev)
+            out['differing'] = torch.empty((rounds, Tc, Pc), dtype=torch.int32, device=dev)
+            if out['sizes'].numel():
+                p_sz, p_df = out['sizes'].data_ptr(), out['differing'].data_ptr()
+    wsb = int(lib().tn_temper_ws_bytes(Nx, Ny, M, T, nbits, Pc))
+    ws = workspace(max(wsb, 16), 1)
+    check(lib().tn_temper(Nx, Ny, C.cast(cells, C.c_void_p), M, T, C.cast(c_betas, C.c_void_p), states.data_ptr(), p_tidx, p_slot, int(round0), rounds,
+                          sweeps, p_u, ldu, nbits, nbmax, p_cb, p_bc, p_rp, p_cols, nnz, int(cluster_from), p_cp, Pc, p_ucl, p_us,
+                          out['energy'].data_ptr(), p_acc, p_att, p_et, p_tt, p_sz, p_df, ws.data_ptr(), wsb, _stream()))
+    return out

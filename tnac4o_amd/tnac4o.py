@@ -1166,6 +1166,38 @@ class tnac4o:
         from . import exchange
         return exchange.exchange_clusters(self, rounds, pairs, uniforms)
 
+    def temper_samples(self, betas, rounds=10, sweeps=1, cluster_moves=True, cluster_beta_min=None, pairs=None, uniforms=None, record=False,
+                       keep=None, rounds_per_call=None):
+        """Parallel tempering with isoenergetic cluster moves (PT+ICM: Zhu, Ochoa, Katzgraber) over the stored configurations, whole
+        rounds on the device in one library call (tn_temper, tnac4o_amd/temper.py).  Runs NO contraction and needs no
+        boundary MPS; the solver's own beta plays no part.
+        Input: the stored `states`, M = R T of them with T = len(betas); betas strictly increasing, positive, finite.  Row m belongs to
+        chain m // T and STARTS at temperature index m % T.  A round is: `sweeps` heat-bath sweeps of relax_samples' move with every row
+        at the beta it holds; with cluster_moves, exchange_clusters' move between the rows of two chains at the same temperature,
+        for every temperature with betas >= cluster_beta_min (None: all) and every chain pair of the round; then swaps of the
+        temperature labels of neighbouring temperatures inside a chain (even pairs in even rounds, odd pairs in odd rounds),
+        accepted with min(1, exp((beta_{t+1} - beta_t)(E_{t+1} - E_t))).  cluster_moves=True needs an Ising model (RMF: ValueError),
+        R >= 2 and at most 65534 active spins; with cluster_moves=False pairs and cluster_beta_min must be None.
+        Randomness.  pairs: None = a random perfect matching of the R chains per round (exchange.check_pairs over R), or an integer
+        numpy array (rounds, Pc, 2) of chain indices, none twice within a round.  uniforms: None, or a dict with the three keys
+        'sweep' (rounds, sweeps, Ny*Nx, M) -- round, sweep, cell in walk order of the CURRENT rotation, row --, 'cluster'
+        (rounds, Tc, Pc) with Tc the number of temperatures that make cluster moves, and 'swap' (rounds, R, T - 1): float64 numpy
+        arrays or device tensors in [0, 1).  With None they come from numpy's global generator: all pairings first, then block by
+        block of rounds_per_call rounds in the order sweep, cluster, swap -- the generator's stream then depends on rounds_per_call,
+        the law does not, and with given uniforms neither does the result.  rounds_per_call: rounds per library call (None: planned
+        from the free device memory; the sweep's uniform numbers, rounds sweeps Nx Ny M 8 bytes, are the large item).  Everything is
+        validated before any device work (ValueError).
+        Stores states (M, Nx*Ny) in model cell order and energy (M,) (returned) in the bits relax_samples gives, temper_betas (T,),
+        temper_index (M,) = the temperature index every row ends at, temper_beta (M,) = its beta, temper_swap_accepted and
+        temper_swap_attempted (T - 1,) over all rounds.  With record=True also temper_energy_trace (rounds, T, R) = the energy at
+        every temperature of every chain after each round, and temper_cluster_sizes, temper_cluster_differing (rounds, Tc, Pc).
+        probability, sample_log2Z, log2Z_lower and log2Z_estimate are set to None, as relax_samples does.
+        keep: None leaves a MIXED population in states / energy -- rows at all T temperatures, told apart by temper_index, which the
+        calculate_overlap_* calls would pool; keep=t leaves only the R rows that end at temperature index t (chains ascending) in
+        states and energy, so that those calls see one temperature (temper_index and temper_beta still describe all M rows)."""
+        from . import temper
+        return temper.temper_samples(self, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, record, keep, rounds_per_call)
+
     # ------------------------------------------------------------------------------------ thermal marginals (GPU)
     def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
         """Boltzmann marginal of every cell and magnetisation of every spin at the solver's beta, from both boundary MPS.
