@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 19 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 22 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -698,6 +698,52 @@ int tn_temper(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int6
               const int32_t* cpairs, int64_t Pc, const double* ucl, const double* uswap, double* energy_out, int32_t* swap_accepted,
               int32_t* swap_attempted, double* energy_trace, int32_t* tidx_trace, int32_t* size_out, int32_t* diff_out, void* ws, int64_t ws_bytes,
               void* stream);
+
+/* ---- K13: population annealing (no counterpart in the reference: tnac4o.anneal_population) -----------------------------------------
+ * tn_anneal: a population of M configurations is taken along the schedule betas (HOST, K doubles), IN PLACE in states (DEVICE,
+ * M x Nx*Ny int16, tn_cell_sweep's layout; cells: the same HOST table) and family (DEVICE, M int32, in / out: a label that travels with
+ * its row; a fresh run: family[m] = m).  betas[0] >= 0 is the inverse temperature whose law the incoming rows sample -- no sweep is made
+ * at it --; betas[1 ..] are strictly increasing above it and finite.  On entry E[m] = the energy of every row by tn_cell_sweep's energy
+ * pass (the bits of its energy_out).  Step s = 1 .. K-1, db = betas[s] - betas[s-1] (one subtraction on the host):
+ *  1. Emin = the smallest E[m] that is no NaN (NaN when every one is)                                          -> emin_out[s-1].
+ *  2. w_m = exp(-(db * (E[m] - Emin))): one subtraction, one multiplication, one exp in fp64, not contracted; a w_m that is NaN counts
+ *     as 0.
+ *  3. Running sums in a fixed SEQUENTIAL order that depends on M alone.  Rows are cut into tiles of 256, a tile into four groups of 64:
+ *     inside a group g_i = g_{i-1} + w_i, row after row (g_{-1} = 0); inside a tile the group bases b_0 = 0, b_{k+1} = b_k + (the last
+ *     g of group k) and l_m = b_k + g_i (group 0: l_m = g_i); across tiles t_0 = 0, t_{k+1} = t_k + (the last l of tile k), tile after
+ *     tile, and C_m = t_k + l_m.  W = t after the last tile                                                   -> wsum_out[s-1].
+ *     The sum of w_m^2 is added in the same order (group after group inside a tile)                            -> w2sum_out[s-1].
+ *     Every partial sum is a sequential sum of non-negative numbers on top of the one before it, so C is non-decreasing in m.
+ *  4. Systematic resampling with u = ures[s-1] (DEVICE, K-1 doubles in [0, 1)): O_{-1} = 0, O_{M-1} = M and for m < M-1
+ *     O_m = min(M, max(O_{m-1}, floor(((C_m / W) * (double)M) + u))): one division, one multiplication, one addition, one floor in fp64,
+ *     a negative or NaN value read as 0.  (C is non-decreasing and each of the four operations is monotone, so the maximum is attained
+ *     by its second operand.)  Row m gets n_m = O_m - O_{m-1} copies; survivors_out[s-1] = the number of rows with n_m >= 1.  W zero
+ *     or not finite (every weight zero or NaN; an infinite sum): the step is the identity, O_m = m + 1.
+ *  5. parent[j] = the m with O_{m-1} <= j < O_m, by binary search over O once per row; states'[j] = states[parent[j]],
+ *     family'[j] = family[parent[j]].  A row is copied in pieces of the widest power of two, at most 16 bytes, that divides 2 Nx Ny
+ *     and the addresses of both copies (an odd number of cells: element by element).  The second copy of the rows lives in ws; when
+ *     the call returns, states and family hold the result in stream order.  The search keeps inside [0, M) whatever O holds, and a
+ *     parent is checked again before it indexes a row.
+ *  6. `sweeps` heat-bath sweeps of tn_cell_sweep's move (mode 0) at betas[s]: the same kernels.  The number of (step s, sweep j, cell k
+ *     in walk order, row m) is usweep[(((s-1) sweeps + j) Nx Ny + k) ldu + m] (DEVICE, ldu >= M).
+ *  7. E[m] = the energy of every row by tn_cell_sweep's energy pass                                            -> energy_out (M).
+ * Optional, NULL allowed: energy_trace ((K-1) x M doubles), E after step 7 of every step; parent_trace ((K-1) x M int32), parent.
+ * The estimate the outputs carry: ln Z(betas[s]) / Z(betas[s-1]) ~ ln(W / M) - db Emin.
+ * Degenerate forms, all valid: K = 1 (energy_out only; ures and the four per-step outputs may be NULL); sweeps = 0 (usweep may be
+ * NULL); M = 1.
+ * Determinism: the result is a function of the inputs alone -- not of the grid, and not of how the schedule is cut into calls: a call on
+ * betas[a .. b] followed by one on betas[b .. c] with the slices of ures and usweep that belong to their steps, states and family
+ * carried over, gives the bits of one call on betas[a .. c].
+ * ws: tn_anneal_ws_bytes(Nx, Ny, M) (0 for a shape the call refuses): the table of the cells, the second copy of rows and families,
+ * l, O, parent and three numbers per tile.  Asynchronous on `stream`; no host synchronisation, no barrier across workgroups, no
+ * kernel that waits for another workgroup, no global atomics.
+ * Limits: those of tn_cell_sweep (q <= 32767, M < 2^31); 1 <= K <= 2^31.
+ * Errors: -1 argument (the message names the limit: betas[0] negative, betas not strictly increasing or not finite, ldu < M, a null
+ * pointer, a bad cell), -3 workspace too small; both before any launch, nothing is written. */
+int64_t tn_anneal_ws_bytes(int64_t Nx, int64_t Ny, int64_t M);
+int tn_anneal(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t K, const double* betas, int16_t* states, int32_t* family,
+              int64_t sweeps, const double* usweep, int64_t ldu, const double* ures, double* energy_out, double* emin_out, double* wsum_out,
+              double* w2sum_out, int32_t* survivors_out, double* energy_trace, int32_t* parent_trace, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

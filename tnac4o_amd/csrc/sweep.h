@@ -1,6 +1,7 @@
-// What tn_temper (temper.hip) shares with tn_cell_sweep (relax.hip) and tn_cluster_exchange (exchange.hip): the device table of the
-// cells, the plan of a sweep's launches, and launchers of the kernels that stay where they are.  Internal header.
+// What tn_temper (temper.hip) and tn_anneal (anneal.hip) share with tn_cell_sweep (relax.hip) and tn_cluster_exchange (exchange.hip):
+// the device table of the cells, the plan of a sweep's launches, and launchers of the kernels that stay where they are.  Internal header.
 #pragma once
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/tnpeps.h"
@@ -46,5 +47,13 @@ int sweep_energy(hipStream_t st, const SweepPlan& plan, const SweepCell* dev, co
 int64_t cluster_exchange_max_nbits();
 int cluster_exchange_launch(hipStream_t st, uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const int32_t* rowptr, const int32_t* cols,
                             int64_t nnz, const int32_t* pairs, int64_t P, const double* uniforms, int32_t* size_out, int32_t* diff_out);
+
+// the product of non-negative factors fits an index: no overflow and below 2^60
+inline bool mul_fits(std::initializer_list<int64_t> f) {
+    int64_t p = 1;
+    for (int64_t x : f)
+        if (x < 0 || __builtin_mul_overflow(p, x, &p)) return false;
+    return p < ((int64_t)1 << 60);
+}
 
 }  // namespace tn

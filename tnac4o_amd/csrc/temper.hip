@@ -156,13 +156,6 @@ TemperWs temper_layout(void* ws, int64_t Nx, int64_t Ny, int64_t M, int64_t T, i
     return s;
 }
 
-bool mul_fits(std::initializer_list<int64_t> f) {
-    int64_t p = 1;
-    for (int64_t x : f)
-        if (x < 0 || __builtin_mul_overflow(p, x, &p)) return false;
-    return p < ((int64_t)1 << 60);
-}
-
 }  // namespace
 
 }  // namespace tn

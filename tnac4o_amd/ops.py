@@ -1195,3 +1195,51 @@ def temper(cells, Nx, Ny, betas, states, tidx, slot, round0, rounds, sweeps, usw
                           sweeps, p_u, ldu, nbits, nbmax, p_cb, p_bc, p_rp, p_cols, nnz, int(cluster_from), p_cp, Pc, p_ucl, p_us,
                           out['energy'].data_ptr(), p_acc, p_att, p_et, p_tt, p_sz, p_df, ws.data_ptr(), wsb, _stream()))
     return out
+
+
+def anneal(cells, Nx, Ny, betas, states, family, sweeps, usweep=None, ures=None, record=False):
+    """The steps betas[0] -> betas[1] -> ... of population annealing, IN PLACE in states and family (tn_anneal; include/tnpeps.h, K13).
+    cells: the ctypes tn_beam_cell array of the lattice (relax.EnergyCells(...).cells); betas: K host floats, betas[0] >= 0 and strictly
+    increasing after it; states (M, Nx*Ny) int16 and family (M,) int32 device tensors; usweep (K - 1, sweeps, Nx*Ny, ld >= M) float64
+    device tensor, None with sweeps = 0 or K = 1; ures (K - 1,) float64 device tensor, None with K = 1.  Returns a dict of device
+    tensors: energy (M,), emin, wsum, w2sum (K - 1,) float64, survivors (K - 1,) int32, energy_trace (K - 1, M) float64, and with
+    record parent_trace (K - 1, M) int32 (None otherwise)."""
+    if not states.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % states.device)
+    if states.dim() != 2 or states.dtype != torch.int16 or not states.is_contiguous() or states.shape[1] != Nx * Ny:
+        raise TypeError('states: a contiguous (M, Nx*Ny) int16 device tensor')
+    M, K, sweeps = int(states.shape[0]), len(betas), int(sweeps)
+    if K < 1:
+        raise ValueError('betas: at least one')
+    steps = K - 1
+    dev = states.device
+    p_fam = _i32_operand(family, 'family', M)
+    c_betas = (C.c_double * K)(*[float(b) for b in betas])
+    p_u, ldu, p_r = None, 0, None
+    if steps > 0:
+        _need_gpu(ures)
+        if ures.dtype != torch.float64 or not ures.is_contiguous() or tuple(ures.shape) != (steps,):
+            raise TypeError('ures: a contiguous (K - 1,) float64 device tensor')
+        p_r = ures.data_ptr()
+        if sweeps > 0:
+            _need_gpu(usweep)
+            if usweep.dtype != torch.float64 or not usweep.is_contiguous() or usweep.dim() != 4 or tuple(usweep.shape[:3]) != (steps, sweeps, Nx * Ny):
+                raise TypeError('usweep: a contiguous (K - 1, sweeps, Nx*Ny, ld) float64 device tensor')
+            p_u, ldu = usweep.data_ptr(), int(usweep.shape[3])
+    out = dict(energy=torch.empty(M, dtype=torch.float64, device=dev), parent_trace=None)
+    for k in ('emin', 'wsum', 'w2sum'):
+        out[k] = torch.empty(steps, dtype=torch.float64, device=dev)
+    out['survivors'] = torch.empty(steps, dtype=torch.int32, device=dev)
+    out['energy_trace'] = torch.empty((steps, M), dtype=torch.float64, device=dev)
+    if record:
+        out['parent_trace'] = torch.empty((steps, M), dtype=torch.int32, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+
+    wsb = int(lib().tn_anneal_ws_bytes(Nx, Ny, M))
+    ws = workspace(max(wsb, 16), 1)
+    check(lib().tn_anneal(Nx, Ny, C.cast(cells, C.c_void_p), M, K, C.cast(c_betas, C.c_void_p), states.data_ptr(), p_fam, sweeps, p_u, ldu, p_r,
+                          out['energy'].data_ptr(), ptr(out['emin']), ptr(out['wsum']), ptr(out['w2sum']), ptr(out['survivors']),
+                          ptr(out['energy_trace']), ptr(out['parent_trace']), ws.data_ptr(), wsb, _stream()))
+    return out

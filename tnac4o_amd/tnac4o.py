@@ -1198,6 +1198,48 @@ class tnac4o:
         from . import temper
         return temper.temper_samples(self, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, record, keep, rounds_per_call)
 
+    def anneal_population(self, betas, sweeps=1, M=None, uniforms=None, record=False, log2Z0=None, steps_per_call=None):
+        """Population annealing (Hukushima, Iba; Machta; Wang, Machta, Katzgraber): a population of M configurations is taken along the
+        schedule `betas`, whole steps on the device in one library call (tn_anneal, tnac4o_amd/anneal.py), and log2 Z is
+        estimated at every beta of the schedule.  Runs NO contraction and needs no boundary MPS; the solver's own beta plays no part;
+        Ising and RMF.
+        betas: K >= 1 finite numbers, betas[0] >= 0, strictly increasing.  betas[0] is the inverse temperature whose law the incoming
+        population samples; no sweep is made at it.  M=None anneals the stored `states`, taken as samples at betas[0].  With M given,
+        betas[0] must be 0 and the population is drawn uniformly on the host, state = min(floor(u q_k), q_k - 1) with q_k the states
+        of cell k.  A step from beta' to beta weights row m with exp(-(beta - beta')(E_m - Emin)), resamples the population to exactly
+        M rows by systematic resampling with one uniform number (row m gets floor or ceil of M w_m / W copies), and makes `sweeps`
+        heat-bath sweeps of relax_samples' move at beta.
+        Randomness.  uniforms: None, or a dict with the keys 'resample' (K - 1,) and 'sweep' (K - 1, sweeps, Ny*Nx, M) -- step, sweep,
+        cell in walk order of the CURRENT rotation, row -- and, when M is given, 'init' (M, Ny*Nx), cells in that walk order too:
+        float64 numpy arrays or device tensors in [0, 1).  With None they come from numpy's global generator: init first, then block
+        by block of steps_per_call steps in the order resample, sweep -- the generator's stream then depends on steps_per_call, the
+        law does not, and with given uniforms neither does the result.  steps_per_call: steps per library call (None: planned from
+        half the free device memory; the sweep's uniform numbers are the large item).  Everything is validated before any device
+        work (ValueError).
+        Stores states (M, Nx*Ny) in model cell order and energy (M,) (returned) in the bits relax_samples gives, and
+        anneal_betas (K,);
+        anneal_log2Z (K,) = log2Z0 plus the running sum of log2(W_s / M) - (betas[s] - betas[s-1]) Emin_s / ln 2.  log2 Z here means
+          log2 sum_x exp(-beta E(x)) over ALL configurations x of the cell states, E in the convention of `energy`.  The cell states of
+          an Ising model enumerate exactly its active spins (sum_k log2 q_k = their number), so this is the quantity
+          calculate_free_energy and sample_log2Z give, with no constant between them.  log2Z0 = None: with betas[0] = 0 it is
+          sum_k log2 q_k, the exact value; with betas[0] > 0 it is 0, and anneal_log2Z then holds the RATIOS log2 Z(beta) / Z(betas[0])
+          (give log2Z0 = the log2 Z of the incoming law, e.g. calculate_free_energy's, for absolute values).  A step whose weights
+          all vanish contributes -inf;
+        anneal_free_energy (K,) = -ln Z / beta where beta > 0, NaN at beta = 0;
+        anneal_energy_mean, anneal_heat_capacity (K,) = the mean of E and beta^2 var E (population variance) over the population at
+          every beta, after its sweeps (at betas[0]: of the incoming population);
+        anneal_ess (K - 1,) = W^2 / sum w^2, the effective sample size of every reweighting; anneal_survivors (K - 1,) = the rows
+          that kept at least one copy;
+        anneal_family (M,) = for every final row the index of the row of the incoming population it descends from;
+        anneal_rho_t = M sum_f (n_f / M)^2 and anneal_family_entropy = -sum_f (n_f / M) ln(n_f / M) over the families (Wang, Machta,
+          Katzgraber: rho_t << M is the condition for trusting the run);
+        with record=True anneal_energy_trace (K - 1, M) = the energies after every step and anneal_parent_trace (K - 1, M) = the row
+          every row was copied from in that step's resampling.
+        probability, sample_log2Z, log2Z_lower and log2Z_estimate are set to None, as temper_samples does.  rhoT, degeneracy and every
+        thermal and scored attribute are left alone."""
+        from . import anneal
+        return anneal.anneal_population(self, betas, sweeps, M, uniforms, record, log2Z0, steps_per_call)
+
     # ------------------------------------------------------------------------------------ thermal marginals (GPU)
     def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
         """Boltzmann marginal of every cell and magnetisation of every spin at the solver's beta, from both boundary MPS.
