@@ -973,8 +973,10 @@ def test_qr_single_launch_panels_bit_identical_to_chain(ops):
             Q0, R0, k0 = _with_env('TN_QR_SMALL', '0', lambda: _with_env('TN_PANEL_FUSED', '0', run))
             assert k0 == k1 and torch.equal(Q0, Q1) and torch.equal(R0, R1), (tuple(T.shape), tol, k0, k1)
             if float(T.abs().max()) > 0:
-                rel = ((Q1 @ R1 - T).norm(dim=0) / T.norm(dim=0).clamp_min(1e-300)).max().item()
-                assert rel < 1e-13 or tol > 0, (tuple(T.shape), rel)
+                # column by column; after an exit every column may miss by tol x the largest column norm (the header's contract)
+                cn = T.norm(dim=0)
+                res = (Q1 @ R1 - T).norm(dim=0)
+                assert bool((res <= 1e-13 * cn + tol * cn.max()).all()), (tuple(T.shape), tol, (res / cn.clamp_min(1e-300)).max().item())
 
 
 def test_qr_single_launch_panels_under_uneven_load(ops):
