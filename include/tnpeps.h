@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 22 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 23 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -744,6 +744,24 @@ int64_t tn_anneal_ws_bytes(int64_t Nx, int64_t Ny, int64_t M);
 int tn_anneal(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t K, const double* betas, int16_t* states, int32_t* family,
               int64_t sweeps, const double* usweep, int64_t ldu, const double* ures, double* energy_out, double* emin_out, double* wsum_out,
               double* w2sum_out, int32_t* survivors_out, double* energy_trace, int32_t* parent_trace, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- K14: uniform numbers from a counter-based generator (no counterpart in the reference: the seed= of the Monte Carlo calls) ------
+ * tn_uniforms: out[r ld + c] = U(seed, stream0 + r, first + c) for r < rows, c < cols (DEVICE, doubles, ld >= cols; the elements
+ * c >= cols of a row are never touched).  U is a pure function of three unsigned 64-bit numbers:
+ *   Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85;
+ *   one of the ten rounds maps (c0, c1, c2, c3), (k0, k1) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), then the key is
+ *   bumped by its increments.
+ *   U(seed, stream, i): b = i >> 1, x = philox(counter (b lo32, b hi32, stream lo32, stream hi32), key (seed lo32, seed hi32)), h = i & 1,
+ *   v = x[2h] + 2^32 x[2h+1], U = (v >> 11) 2^-53: both steps exact in fp64, U in [0, 1 - 2^-53].
+ * One Philox block is two numbers, 16 bytes: a block that lies inside the row at an address that is a multiple of 16 is stored with one
+ * 16-byte store, every other number (a row that starts at an odd `first`, an odd cols, an odd ld or base) with an 8-byte store; the
+ * bits do not depend on which.  The result is a function of the arguments alone, not of the grid; a fill of [first, first + n) equals
+ * the fills of [first, first + a) and [first + a, first + n).
+ * rows = 0 or cols = 0 is a valid no-op.  Asynchronous on `stream`: one launch, no workspace, no atomics, no barrier across workgroups,
+ * no host synchronisation.
+ * Errors: -1 before any launch, the message names the limit: rows or cols negative, ld < cols, rows ld >= 2^62, first + cols above 2^64,
+ * stream0 + rows above 2^64, and (rows, cols > 0) out null or not aligned to 8 bytes. */
+int tn_uniforms(uint64_t seed, uint64_t stream0, uint64_t first, int64_t rows, int64_t cols, double* out, int64_t ld, void* stream);
 
 #ifdef __cplusplus
 }

@@ -64,11 +64,14 @@ def draw_population(u, qs):
     return np.minimum(np.floor(np.asarray(u, dtype=np.float64) * qs[None, :]).astype(np.int64), qs[None, :] - 1)
 
 
-def check_arguments(solver, betas, sweeps, M, uniforms, log2Z0, steps_per_call):
+def check_arguments(solver, betas, sweeps, M, uniforms, log2Z0, steps_per_call, seed=None):
     """Everything anneal_population can refuse before any device work.  Returns a dict: betas, K, M, fresh (the population is drawn),
-    states ((M, Nx*Ny) int64 in model order, None when fresh), sweeps, shapes, uniforms (None or the dict), log2Z0, steps_per_call."""
+    states ((M, Nx*Ny) int64 in model order, None when fresh), sweeps, shapes, uniforms (None or the dict), log2Z0, steps_per_call,
+    seed (None or an int: rng.check_seed, not together with uniforms)."""
+    from .rng import check_seed_alone
     b = check_schedule(betas)
     K = int(b.size)
+    seed = check_seed_alone(seed, uniforms)
     if isinstance(sweeps, bool) or int(sweeps) != sweeps or sweeps < 0:
         raise ValueError('sweeps must be a non-negative integer')
     if steps_per_call is not None and (isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1):
@@ -99,7 +102,25 @@ def check_arguments(solver, betas, sweeps, M, uniforms, log2Z0, steps_per_call):
             raise ValueError('log2Z0 must be None or a finite number')
     shapes = uniform_shapes(K, int(sweeps), solver.Nx * solver.Ny, M)
     return dict(betas=b, K=K, M=M, fresh=fresh, states=st, sweeps=int(sweeps), shapes=shapes, uniforms=check_anneal_uniforms(uniforms, shapes, fresh),
-                log2Z0=log2Z0, steps_per_call=None if steps_per_call is None else int(steps_per_call))
+                log2Z0=log2Z0, steps_per_call=None if steps_per_call is None else int(steps_per_call), seed=seed)
+
+
+def seeded_block(seed, shapes, lo, hi, dev):
+    """The uniform numbers of the steps lo .. hi - 1 filled on the device (one tn_uniforms per array): every number a function of the
+    seed and its logical position with the GLOBAL step, so the blocks of any cut join to the same arrays."""
+    from . import rng
+    tail = tuple(shapes['sweep'][1:])
+    return {'resample': rng.fill(seed, rng.ANNEAL_RESAMPLE, 0, (hi - lo,), first=lo, dev=dev),
+            'sweep': rng.fill(seed, rng.ANNEAL_SWEEP, lo * tail[0] * tail[1], (hi - lo,) + tail, dev=dev)}
+
+
+def seeded_population(seed, M, qs, dev):
+    """draw_population on the device from the seed's init numbers (rng.ANNEAL_INIT: row = member, index = cell): (M, ncell) int16."""
+    import torch
+    from . import rng
+    q = torch.as_tensor(np.asarray(qs, dtype=np.float64)).to(dev)
+    u = rng.fill(seed, rng.ANNEAL_INIT, 0, (M, int(q.numel())), dev=dev)
+    return torch.minimum(torch.floor(u * q[None, :]), q[None, :] - 1.0).to(torch.int16)
 
 
 def step_bytes(shapes, M, record):
@@ -139,7 +160,8 @@ def family_statistics(family):
 def anneal_native(solver, states_rot, a, record):
     """The device loop: states and families go up once, the schedule runs in blocks of steps_per_call steps of tn_anneal, each on
     betas[lo .. hi] with states and family carried over on the device, everything comes back once.  states_rot: (M, Ny*Nx) in the
-    lattice order of the current rotation; a: what check_arguments returned.  Returns a dict of numpy arrays: states, energy, family,
+    lattice order of the current rotation, or None with a['seed'] and a['fresh']: the population is then made on the device;
+    a: what check_arguments returned.  Returns a dict of numpy arrays: states, energy, family,
     energy0 (M,) = the energies on entry, emin, wsum, w2sum, survivors (K - 1,), energy_trace (K - 1, M) and with record parent_trace."""
     import torch
     from . import ops
@@ -149,7 +171,11 @@ def anneal_native(solver, states_rot, a, record):
     M, K, sweeps, betas = a['M'], a['K'], a['sweeps'], a['betas']
     steps = K - 1
     table = EnergyCells(solver, dev)
-    d_st = torch.as_tensor(np.ascontiguousarray(states_rot, dtype=np.int16)).to(dev)
+    seed = a.get('seed')
+    if states_rot is None:
+        d_st = seeded_population(seed, M, solver._cell_sizes(), dev)
+    else:
+        d_st = torch.as_tensor(np.ascontiguousarray(states_rot, dtype=np.int16)).to(dev)
     d_fam = torch.arange(M, dtype=torch.int32, device=dev)
     per = a['steps_per_call']
     if per is None:
@@ -166,9 +192,12 @@ def anneal_native(solver, states_rot, a, record):
     outs = []
     for lo in range(0, steps, per):
         hi = min(lo + per, steps)
-        u = given if given is not None else draw_block(a['shapes'], 0, hi - lo)
-        off = lo if given is not None else 0
-        d_u = {k: block(u[k], off, off + hi - lo) for k in STEP_KEYS}
+        if seed is not None:
+            d_u = seeded_block(seed, a['shapes'], lo, hi, dev)
+        else:
+            u = given if given is not None else draw_block(a['shapes'], 0, hi - lo)
+            off = lo if given is not None else 0
+            d_u = {k: block(u[k], off, off + hi - lo) for k in STEP_KEYS}
         out = ops.anneal(table.cells, Nx, Ny, betas[lo:hi + 1], d_st, d_fam, sweeps, usweep=d_u['sweep'] if sweeps else None, ures=d_u['resample'],
                          record=record)
         energy = out['energy']
@@ -190,10 +219,12 @@ def anneal_native(solver, states_rot, a, record):
     return res
 
 
-def anneal_population(solver, betas, sweeps=1, M=None, uniforms=None, record=False, log2Z0=None, steps_per_call=None):
+def anneal_population(solver, betas, sweeps=1, M=None, uniforms=None, record=False, log2Z0=None, steps_per_call=None, seed=None):
     """anneal_population of tnac4o (documented there)."""
-    a = check_arguments(solver, betas, sweeps, M, uniforms, log2Z0, steps_per_call)
-    if a['fresh']:
+    a = check_arguments(solver, betas, sweeps, M, uniforms, log2Z0, steps_per_call, seed)
+    if a['fresh'] and a['seed'] is not None:
+        rot = None
+    elif a['fresh']:
         u = a['uniforms']['init'] if a['uniforms'] is not None else np.random.rand(a['M'], solver.Nx * solver.Ny)
         rot = draw_population(u if isinstance(u, np.ndarray) else u.cpu().numpy(), solver._cell_sizes())
     else:

@@ -23,7 +23,7 @@ using namespace tn;
 
 extern "C" {
 
-int tn_version(void) { return 22; }
+int tn_version(void) { return 23; }
 
 #ifndef TN_SRC_HASH
 #define TN_SRC_HASH "unknown"

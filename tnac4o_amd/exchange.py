@@ -85,17 +85,23 @@ def check_round_uniforms(uniforms, rounds, P):
     return uniforms
 
 
-def check_arguments(solver, rounds, pairs, uniforms):
+def check_arguments(solver, rounds, pairs, uniforms, seed=None):
     """Everything exchange_clusters can refuse before any device work.  Returns (rounds, pairs (rounds, P, 2) int32, uniforms (rounds, P));
-    every pairing is drawn before any uniform."""
+    every pairing is drawn before any uniform.  With a seed (rng.check_seed; not together with uniforms) nothing is drawn from numpy's
+    generator: pairs=None gives the pairings of the seed's keys, and the uniforms returned are None -- they are filled on the device."""
+    from . import rng
     _ising(solver, 'exchange_clusters')
     if int(rounds) != rounds or rounds < 0:
         raise ValueError('rounds must be a non-negative integer')
+    seed = rng.check_seed_alone(seed, uniforms)
     st = np.asarray(solver.states)
     M = int(st.shape[0]) if st.ndim == 2 else 0
     if M < 2:
         raise ValueError('exchange_clusters needs at least two stored states (run sample_boltzmann, gibbs_sampling, a search or '
                          'decode_low_energy_states first)')
+    if seed is not None:
+        pairs = rng.draw_pairs(seed, rng.EXCHANGE_PAIRING, int(rounds), M) if pairs is None else check_pairs(pairs, rounds, M)
+        return int(rounds), pairs, None
     pairs = check_pairs(pairs, rounds, M)
     return int(rounds), pairs, check_round_uniforms(uniforms, rounds, pairs.shape[1])
 
@@ -107,26 +113,32 @@ def unpack_bits(rows, n):
     return np.unpackbits(by, axis=1, bitorder='little')[:, :n]
 
 
-def exchange_native(rows, nbits, rowptr, cols, pairs, uniforms):
+def exchange_native(rows, nbits, rowptr, cols, pairs, uniforms, seed=None):
     """The device loop: rows (M, nwords) uint64 go up once, every round is one tn_cluster_exchange on them, they come back once.
+    uniforms None and seed an integer: the (rounds, P) numbers are filled on the device (rng.EXCHANGE_SEED: row = round, index = pair).
     Returns (rows, cluster sizes (rounds, P) int64, differing bits (rounds, P) int64)."""
     import torch
-    from . import ops
+    from . import ops, rng
     dev = torch.device('cuda', torch.cuda.current_device())
     rounds, P = pairs.shape[0], pairs.shape[1]
     d_rows = torch.as_tensor(np.ascontiguousarray(rows).view(np.int64)).to(dev)
     d_rowptr, d_cols = torch.as_tensor(rowptr).to(dev), torch.as_tensor(cols).to(dev)
     d_pairs = torch.as_tensor(pairs).to(dev)
-    d_u = (torch.as_tensor(uniforms) if isinstance(uniforms, np.ndarray) else uniforms).to(dev).contiguous()
+    if seed is not None:
+        d_u = rng.fill(seed, rng.EXCHANGE_SEED, 0, (rounds, P), dev=dev)
+    else:
+        d_u = (torch.as_tensor(uniforms) if isinstance(uniforms, np.ndarray) else uniforms).to(dev).contiguous()
     out = [ops.cluster_exchange(d_rows, nbits, d_rowptr, d_cols, d_pairs[k], d_u[k]) for k in range(rounds)]
     sizes = np.array([s.cpu().numpy() for s, _ in out], dtype=np.int64).reshape(rounds, P)
     diff = np.array([d.cpu().numpy() for _, d in out], dtype=np.int64).reshape(rounds, P)
     return d_rows.cpu().numpy().view(np.uint64), sizes, diff
 
 
-def exchange_clusters(solver, rounds=1, pairs=None, uniforms=None):
+def exchange_clusters(solver, rounds=1, pairs=None, uniforms=None, seed=None):
     """exchange_clusters of tnac4o (documented there)."""
-    rounds, pairs, uniforms = check_arguments(solver, rounds, pairs, uniforms)
+    from .rng import check_seed
+    rounds, pairs, uniforms = check_arguments(solver, rounds, pairs, uniforms, seed)
+    seed = check_seed(seed)
     act = active_spins(solver)
     n = int(act.size)
     if n < 1:
@@ -136,7 +148,7 @@ def exchange_clusters(solver, rounds=1, pairs=None, uniforms=None):
     rowptr, cols = coupling_csr(solver)
     old = np.asarray(solver.states)
     M = old.shape[0]
-    rows, sizes, diff = exchange_native(pack_bits(spin_bits(solver)), n, rowptr, cols, pairs, uniforms)
+    rows, sizes, diff = exchange_native(pack_bits(spin_bits(solver)), n, rowptr, cols, pairs, uniforms, seed)
     bits = np.zeros((M, int(solver.L)), dtype=np.int8)
     bits[:, act] = unpack_bits(rows, n)
     new = solver.states_from_binary(bits)

@@ -1243,3 +1243,25 @@ def anneal(cells, Nx, Ny, betas, states, family, sweeps, usweep=None, ures=None,
                           out['energy'].data_ptr(), ptr(out['emin']), ptr(out['wsum']), ptr(out['w2sum']), ptr(out['survivors']),
                           ptr(out['energy_trace']), ptr(out['parent_trace']), ws.data_ptr(), wsb, _stream()))
     return out
+
+
+def uniforms(seed, stream0, first, rows, cols, out=None):
+    """out[r, c] = U(seed, stream0 + r, first + c), the library's counter-based uniform numbers in [0, 1) (tn_uniforms; include/tnpeps.h,
+    K14; tnac4o_amd/rng.py): seed, stream0, first integers in [0, 2^64).  out: None = a new (rows, cols) float64 tensor on the current
+    device, or a (rows, cols) float64 device tensor whose rows are contiguous (any row stride >= cols): the elements between two rows
+    are left alone.  Returns out."""
+    rows, cols = int(rows), int(cols)
+    seed, stream0, first = int(seed), int(stream0), int(first)
+    for name, v in (('seed', seed), ('stream0', stream0), ('first', first)):
+        if not 0 <= v < 2 ** 64:
+            raise ValueError('%s must lie in [0, 2^64)' % name)
+    if rows < 0 or cols < 0:
+        raise ValueError('rows and cols must not be negative')
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.float64, device=torch.device('cuda', torch.cuda.current_device()))
+    _need_gpu(out)
+    if out.dim() != 2 or tuple(out.shape) != (rows, cols) or (cols > 1 and out.stride(1) != 1) or (rows > 1 and out.stride(0) < cols):
+        raise TypeError('out: a (rows, cols) float64 device tensor with contiguous rows')
+    ld = int(out.stride(0)) if rows > 1 else cols
+    check(lib().tn_uniforms(seed, stream0, first, rows, cols, out.data_ptr() if out.numel() else None, ld, _stream()))
+    return out

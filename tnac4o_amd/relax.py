@@ -46,11 +46,14 @@ def check_sweep_uniforms(uniforms, sweeps, ncell, M):
     return uniforms
 
 
-def check_relax_arguments(mode, sweeps, beta, uniforms, max_sweeps):
+def check_relax_arguments(mode, sweeps, beta, uniforms, max_sweeps, seed=None):
     """The argument rules of tnac4o.relax_samples that need neither the states nor a device: (library mode, sweeps or None, beta).
-    ValueError otherwise."""
+    seed: under rng.check_seed, not together with uniforms and not with mode='quench'.  ValueError otherwise."""
+    from .rng import check_seed_alone
     if mode not in MODES:
         raise ValueError("mode must be 'heat_bath' or 'quench' (got %r)" % (mode,))
+    if check_seed_alone(seed, uniforms) is not None and mode == 'quench':
+        raise ValueError("seed must be None with mode='quench' (a quench draws nothing)")
     if sweeps is None:
         if mode != 'quench':
             raise ValueError("sweeps=None (until nothing moves) needs mode='quench'")
@@ -90,15 +93,17 @@ class EnergyCells:
             c.e4cols = tb.E4.shape[1] if tb.E4.dim() == 2 else 1
 
 
-def relax_native(solver, states_rot, mode, beta, sweeps, uniforms=None, chunk=None, max_sweeps=64):
+def relax_native(solver, states_rot, mode, beta, sweeps, uniforms=None, chunk=None, max_sweeps=64, seed=None):
     """tn_cell_sweep over the configurations states_rot (M, Ny*Nx) integers in the lattice order of the current rotation, every entry
     inside the states of its cell, in row slices of at most `chunk` configurations.  mode: 0 heat bath / 1 quench; sweeps: their
     number, or None (quench): blocks of QUENCH_BLOCK sweeps until no cell of the slice moves in the last one, at most max_sweeps.
-    uniforms: what check_sweep_uniforms returned (heat bath), None (quench).  Per slice: one upload of its states and of its uniform
-    numbers, one read-back of everything it returns (the quench until nothing moves also reads one flag per block).
+    uniforms: what check_sweep_uniforms returned (heat bath), None (quench, or a heat bath with seed: an integer, the numbers of every
+    slice are then filled on the device -- rng.RELAX_SWEEP: row = sweep * Ny*Nx + cell, index = configuration).  Per slice: one upload of
+    its states and of its uniform numbers, one read-back of everything it returns (the quench until nothing moves also reads one flag
+    per block).
     Returns (states (M, Ny*Nx) int64 in the same order, energy, energy before, moves, last moves, sweeps run); stores nothing."""
     import torch
-    from . import ops
+    from . import ops, rng
     from ._lib import lib
     Nx, Ny = solver.Nx, solver.Ny
     ncell = Nx * Ny
@@ -154,7 +159,10 @@ def relax_native(solver, states_rot, mode, beta, sweeps, uniforms=None, chunk=No
         call(0, None, 0, p_before, None, None, mode=1)      # no sweep: the energies of the states as they arrive
         u = None
         if mode == 0:
-            if on_device:
+            if seed is not None:
+                u = rng.fill(seed, rng.RELAX_SWEEP, 0, (nsw * ncell, m), first=lo, dev=dev)
+                u_ptr, ldu = u.data_ptr(), m
+            elif on_device:
                 u_ptr, ldu = uniforms.data_ptr() + lo * 8, M
             else:
                 u = torch.as_tensor(np.ascontiguousarray(uniforms[:, :, lo:hi])).to(dev)

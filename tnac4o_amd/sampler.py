@@ -158,19 +158,21 @@ def _walk_table(solver, who, running_sum):
     return table, B
 
 
-def sample_native(solver, M, uniforms=None, chunk=None):
+def sample_native(solver, M, uniforms=None, chunk=None, seed=None):
     """The walk of tnac4o.sample_boltzmann over solver.rhoT (which must be set up), in column slices of `uniforms` of at most `chunk`
-    samples: one upload of the uniform numbers and one read-back of states / energies / log2 q per slice.  Stores the results on
-    the solver and returns the energies."""
+    samples: one upload of the uniform numbers and one read-back of states / energies / log2 q per slice.  seed (an integer, uniforms
+    None): the numbers of every slice are filled on the device instead (rng.WALK: row = cell, index = sample), nothing is drawn or
+    uploaded.  Stores the results on the solver and returns the energies."""
     import torch
-    from . import ops
+    from . import ops, rng
     from ._lib import lib
     Nx, Ny = solver.Nx, solver.Ny
     ncell = Nx * Ny
     M = int(M)
     if M < 1:
         raise ValueError('M must be positive')
-    uniforms = check_uniforms(uniforms, ncell, M)
+    if seed is None:
+        uniforms = check_uniforms(uniforms, ncell, M)
     if chunk is not None:
         chunk_slices(M, chunk)                            # (validates chunk before any device work)
     dev = solver.rhoT[0].A[0].device
@@ -195,12 +197,15 @@ def sample_native(solver, M, uniforms=None, chunk=None):
     energy = np.empty(M)
     log2q = np.empty(M)
     globalmin, max_groups = 1.0, 0
-    on_device = not isinstance(uniforms, np.ndarray)
+    on_device = seed is None and not isinstance(uniforms, np.ndarray)
     if on_device:
         uniforms = uniforms.to(dev).contiguous()
     for lo, hi in slices:
         m = hi - lo
-        if on_device:
+        if seed is not None:
+            u = rng.fill(seed, rng.WALK, 0, (ncell, m), first=lo, dev=dev)
+            u_ptr, ldu = u.data_ptr(), m
+        elif on_device:
             u_ptr, ldu, u = uniforms.data_ptr() + lo * 8, M, uniforms
         else:
             u = torch.as_tensor(np.ascontiguousarray(uniforms[:, lo:hi])).to(dev)

@@ -102,12 +102,15 @@ def draw_block(shapes, lo, hi):
     return {k: np.random.rand(*((hi - lo,) + tuple(shapes[k][1:]))) for k in UNIFORM_KEYS}
 
 
-def check_arguments(solver, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, keep, rounds_per_call):
+def check_arguments(solver, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, keep, rounds_per_call, seed=None):
     """Everything temper_samples can refuse before any device work.  Returns a dict: betas, T, R, M, states (M, Nx*Ny) int64 in model
     order, rounds, sweeps, cluster (bool), cluster_from, pairs (rounds, Pc, 2) int32, shapes, uniforms (None or the dict), keep,
-    rounds_per_call.  The pairings are drawn here (before any uniform) when pairs is None."""
+    rounds_per_call, seed (None or an int: rng.check_seed, not together with uniforms).  The pairings are drawn here (before any
+    uniform) when pairs is None: from numpy's global generator, or with a seed from its pairing keys."""
+    from . import rng
     b = check_betas(betas)
     T = int(b.size)
+    seed = rng.check_seed_alone(seed, uniforms)
     for name, v in (('rounds', rounds), ('sweeps', sweeps)):
         if isinstance(v, bool) or int(v) != v or v < 0:
             raise ValueError('%s must be a non-negative integer' % name)
@@ -140,7 +143,7 @@ def check_arguments(solver, betas, rounds, sweeps, cluster_moves, cluster_beta_m
             if not np.isfinite(cmin):
                 raise ValueError('cluster_beta_min must be None or a finite number')
             cluster_from = int(np.searchsorted(b, cmin, side='left'))
-        pairs = check_pairs(pairs, rounds, R)
+        pairs = rng.draw_pairs(seed, rng.TEMPER_PAIRING, rounds, R) if (seed is not None and pairs is None) else check_pairs(pairs, rounds, R)
     else:
         if pairs is not None:
             raise ValueError('pairs must be None with cluster_moves=False')
@@ -151,7 +154,19 @@ def check_arguments(solver, betas, rounds, sweeps, cluster_moves, cluster_beta_m
     shapes = uniform_shapes(rounds, sweeps, solver.Nx * solver.Ny, M, T, T - cluster_from, int(pairs.shape[1]))
     return dict(betas=b, T=T, R=R, M=M, states=st, rounds=rounds, sweeps=sweeps, cluster=cluster, cluster_from=cluster_from, pairs=pairs,
                 shapes=shapes, uniforms=check_temper_uniforms(uniforms, shapes), keep=None if keep is None else int(keep),
-                rounds_per_call=None if rounds_per_call is None else int(rounds_per_call))
+                rounds_per_call=None if rounds_per_call is None else int(rounds_per_call), seed=seed)
+
+
+def seeded_block(seed, shapes, lo, hi, dev):
+    """The uniform numbers of the rounds lo .. hi - 1 filled on the device (one tn_uniforms per array): every number a function of the
+    seed and its logical position with the GLOBAL round, so the blocks of any cut join to the same arrays."""
+    from . import rng
+    kinds = {'sweep': rng.TEMPER_SWEEP, 'cluster': rng.TEMPER_CLUSTER, 'swap': rng.TEMPER_SWAP}
+    out = {}
+    for k in UNIFORM_KEYS:
+        tail = tuple(shapes[k][1:])
+        out[k] = rng.fill(seed, kinds[k], lo * int(np.prod(tail[:-1], dtype=np.int64)), (hi - lo,) + tail, dev=dev)
+    return out
 
 
 def round_bytes(shapes, M, record):
@@ -212,9 +227,12 @@ def temper_native(solver, states_rot, a, record, tables=None):
     energy = None
     for lo in range(0, max(rounds, 1), per):
         hi = min(lo + per, rounds)
-        u = given if given is not None else draw_block(a['shapes'], 0, hi - lo)
-        off = lo if given is not None else 0
-        d_u = {k: block(u[k], off, off + hi - lo) for k in UNIFORM_KEYS}
+        if a.get('seed') is not None:
+            d_u = seeded_block(a['seed'], a['shapes'], lo, hi, dev)
+        else:
+            u = given if given is not None else draw_block(a['shapes'], 0, hi - lo)
+            off = lo if given is not None else 0
+            d_u = {k: block(u[k], off, off + hi - lo) for k in UNIFORM_KEYS}
         out = ops.temper(table.cells, Nx, Ny, a['betas'], d_st, d_tidx, d_slot, lo, hi - lo, sweeps, usweep=d_u['sweep'], bits=bits,
                          cluster_from=a['cluster_from'], cpairs=None if d_pairs is None else d_pairs[lo:hi].contiguous(), ucl=d_u['cluster'],
                          uswap=d_u['swap'], accepted=d_acc if T > 1 else None, attempted=d_att if T > 1 else None, record=record)
@@ -231,9 +249,9 @@ def temper_native(solver, states_rot, a, record, tables=None):
 
 
 def temper_samples(solver, betas, rounds=10, sweeps=1, cluster_moves=True, cluster_beta_min=None, pairs=None, uniforms=None, record=False,
-                   keep=None, rounds_per_call=None):
+                   keep=None, rounds_per_call=None, seed=None):
     """temper_samples of tnac4o (documented there)."""
-    a = check_arguments(solver, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, keep, rounds_per_call)
+    a = check_arguments(solver, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, keep, rounds_per_call, seed)
     tables = None
     if a['cluster']:
         tables = bit_tables(solver) + coupling_csr(solver)

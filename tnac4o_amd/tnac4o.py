@@ -1032,7 +1032,7 @@ class tnac4o:
         return self._store_result(Eng, states, np.zeros(1), 0, 0, globalmin)
 
     def sample_boltzmann(self, M=2 ** 16, Dmax=32, tolS=1e-15, tolV=1e-10, max_sweeps=20, graduate_truncation=True, uniforms=None,
-                         chunk=None):
+                         chunk=None, seed=None):
         """Draw M configurations from the Boltzmann distribution with the library's sampling walk (tn_gibbs_sample): the draws of
         gibbs_sampling -- a seeded run draws the same configurations -- without the host round trips per cell, and with the
         probability each configuration was drawn with.  Works in the rotation that is set, Ising and RMF.
@@ -1040,6 +1040,10 @@ class tnac4o:
         consumes), or a (Ny*Nx, M) float64 array / device tensor of numbers in [0, 1), row = cell in walk order of the current
         rotation, column = sample; anything else is a ValueError.  chunk: samples per call of the walk (default: the largest power
         of two <= M whose workspace fits half of the free device memory); sample k's result does not depend on it.
+        seed: None, or an integer in [0, 2^64) (not a bool; not together with uniforms: ValueError): the numbers come from the
+        library's counter-based generator (tnac4o_amd/rng.py), filled on the device slice by slice -- number (cell k,
+        sample m) is U(seed, stream of (walk, k), m), so sample m does not depend on M or chunk, and nothing is drawn on the host.
+        The same seed gives the same numbers in every call, as the same uniforms would: vary the seed.
         Stores energy (M,), states (M, Nx*Ny) in model cell order, degeneracy = 0, probability (M,) = log2 q(x) of every sample,
         discarded_probability = 0, negative_probability, and the estimates of the partition function that follow from q
         (tnac4o_amd/sampler.py): sample_log2Z (M,) = -beta energy / ln 2 - probability, the same number log2 Z for every sample when
@@ -1047,15 +1051,17 @@ class tnac4o:
         Z is the partition function over the ACTIVE spins: a spin without any term is not part of the network and would add
         exactly 1 to log2 Z.  Raises NotImplementedError naming the limit when a cell does not fit the walk; there is no host
         fallback.  Returns the sampled energies."""
-        from . import sampler
+        from . import rng, sampler
         if int(M) < 1:
             raise ValueError('M must be positive')
-        uniforms = sampler.check_uniforms(uniforms, self.Nx * self.Ny, int(M))       # (before any device work)
+        seed = rng.check_seed_alone(seed, uniforms)
+        if seed is None:
+            uniforms = sampler.check_uniforms(uniforms, self.Nx * self.Ny, int(M))   # (before any device work)
         if chunk is not None:
             sampler.chunk_slices(int(M), chunk)
         self.logger.info('Sampling (library walk) with beta = %.2f', self.beta)
         self._setup_rhoT(graduate_truncation=graduate_truncation, Dmax=Dmax, tolS=tolS, tolV=tolV, max_sweeps=max_sweeps)
-        return sampler.sample_native(self, int(M), uniforms=uniforms, chunk=chunk)
+        return sampler.sample_native(self, int(M), uniforms=uniforms, chunk=chunk, seed=seed)
 
     def _cell_sizes(self):
         """Number of states of every cell of the rotated lattice, row-major (host)."""
@@ -1097,7 +1103,7 @@ class tnac4o:
         self.scored_negative = min(globalmin, 0)
         return log2q
 
-    def relax_samples(self, sweeps=1, mode='heat_bath', beta=None, states=None, uniforms=None, chunk=None, max_sweeps=64):
+    def relax_samples(self, sweeps=1, mode='heat_bath', beta=None, states=None, uniforms=None, chunk=None, max_sweeps=64, seed=None):
         """Move configurations by sweeps of block updates of whole cells (tn_cell_sweep, tnac4o_amd/relax.py): every cell in turn --
         checkerboard colour ny + nx even first, then odd -- is given a new state from its conditional law given its four neighbours,
         a table of q numbers read off the cell energies.  Runs NO contraction and needs no boundary MPS; works in the rotation that
@@ -1105,7 +1111,11 @@ class tnac4o:
         mode='heat_bath': the new state is drawn from the conditional Boltzmann law at `beta` (None = the solver's).  A sweep leaves
         the Boltzmann law invariant, so sweeps started from the samples of sample_boltzmann at a cheap Dmax can only bring their law
         closer to it.  uniforms: None = np.random.rand(sweeps, Ny*Nx, M), or a (sweeps, Ny*Nx, M) float64 array / device tensor in
-        [0, 1): sweep, cell in walk order of the current rotation, sample; anything else is a ValueError.
+        [0, 1): sweep, cell in walk order of the current rotation, sample; anything else is a ValueError.  seed: None, or an integer in
+        [0, 2^64) as sample_boltzmann's (not with uniforms, not with mode='quench': ValueError): the numbers are filled on the device
+        slice by slice, number (sweep j, cell k, configuration m) is U(seed, stream of (relax sweep, j Ny*Nx + k), m) -- configuration
+        m's result depends neither on chunk nor on how many configurations follow it.  The same seed gives the same numbers in every
+        call: vary it.
         mode='quench': every cell goes to the smallest state of minimal conditional energy when that lowers the energy strictly, and
         stays otherwise (zero-temperature descent; the energy never rises).  sweeps=None repeats sweeps until no cell of any
         configuration moves in the last one, at most max_sweeps; uniforms must be None.
@@ -1118,11 +1128,12 @@ class tnac4o:
         a minimum under the cell moves), relax_sweeps = sweeps run.  probability, sample_log2Z, log2Z_lower and log2Z_estimate are
         set to None: the configurations are no longer draws of q -- calculate_log_probability() gives log2 q of the new states.
         rhoT, degeneracy and every thermal and scored attribute are left alone."""
-        from . import relax, sampler
-        lib_mode, nsw, b = relax.check_relax_arguments(mode, sweeps, self.beta if beta is None else beta, uniforms, max_sweeps)
+        from . import relax, rng, sampler
+        lib_mode, nsw, b = relax.check_relax_arguments(mode, sweeps, self.beta if beta is None else beta, uniforms, max_sweeps, seed)
+        seed = rng.check_seed(seed)
         st = sampler.check_states(self.states if states is None else states, self._cell_sizes()[self.order])
         M = st.shape[0]
-        if lib_mode == 0:
+        if lib_mode == 0 and seed is None:
             uniforms = relax.check_sweep_uniforms(uniforms, nsw, self.Nx * self.Ny, M)
         if chunk is not None:
             sampler.chunk_slices(M, chunk)
@@ -1130,7 +1141,7 @@ class tnac4o:
         rot = np.empty_like(st)
         rot[:, self.order] = st                                  # the inverse of _store_result's states[:, order]
         new, energy, before, moves, last, swept = relax.relax_native(self, rot, lib_mode, b, nsw, uniforms=uniforms, chunk=chunk,
-                                                                     max_sweeps=max_sweeps)
+                                                                     max_sweeps=max_sweeps, seed=seed)
         self.states = new[:, self.order]
         self.energy = energy
         self.relax_energy_before, self.relax_moves = before, moves
@@ -1139,7 +1150,7 @@ class tnac4o:
         self.probability = self.sample_log2Z = self.log2Z_lower = self.log2Z_estimate = None
         return energy
 
-    def exchange_clusters(self, rounds=1, pairs=None, uniforms=None):
+    def exchange_clusters(self, rounds=1, pairs=None, uniforms=None, seed=None):
         """Move the stored configurations by isoenergetic cluster moves on pairs of them (Houdayer's move in its form for arbitrary
         graphs; tn_cluster_exchange, tnac4o_amd/exchange.py): for a pair of replicas a, b one of the spins in which they differ is
         picked at random, and the connected cluster of differing spins that contains it -- connected along the couplings of J -- is
@@ -1157,17 +1168,21 @@ class tnac4o:
         (rounds, P, 2) of indices into `states`, none twice within a round.  uniforms: None = np.random.rand(rounds, P), or a
         (rounds, P) float64 array / device tensor in [0, 1): pair p of a round with cnt differing spins takes the
         min(floor(u cnt), cnt - 1)-th of them in model order as its seed.  Every pairing is drawn before any uniform; anything else
-        is a ValueError raised before any device work.
+        is a ValueError raised before any device work.  seed: None, or an integer in [0, 2^64) as sample_boltzmann's (not with
+        uniforms: ValueError): the seeds' numbers are filled on the device, number (round r, pair p) is U(seed, stream of (exchange
+        seed, r), p); with pairs=None the pairing of round r is the first 2 P entries of the stable ascending argsort of the keys
+        U(seed, stream of (exchange pairing, r), m), m < M, computed on the host; explicit pairs are allowed, only the uniforms then
+        come from the generator.  numpy's global generator is not touched.  The same seed gives the same numbers in every call: vary it.
         Stores states (M, Nx*Ny) in model cell order, energy (M,) in the bits relax_samples and scored_energy produce,
         exchange_energy_before (M,), exchange_pairs (rounds, P, 2), exchange_cluster_sizes (rounds, P) (returned; 0 = the partners
         were equal) and exchange_differing (rounds, P) = the spins in which the partners differ.  probability, sample_log2Z,
         log2Z_lower and log2Z_estimate are set to None, as relax_samples does.  rhoT, degeneracy and every thermal and scored attribute
         are left alone.  More than 65534 active spins: NotImplementedError; there is no host fallback."""
         from . import exchange
-        return exchange.exchange_clusters(self, rounds, pairs, uniforms)
+        return exchange.exchange_clusters(self, rounds, pairs, uniforms, seed)
 
     def temper_samples(self, betas, rounds=10, sweeps=1, cluster_moves=True, cluster_beta_min=None, pairs=None, uniforms=None, record=False,
-                       keep=None, rounds_per_call=None):
+                       keep=None, rounds_per_call=None, seed=None):
         """Parallel tempering with isoenergetic cluster moves (PT+ICM: Zhu, Ochoa, Katzgraber) over the stored configurations, whole
         rounds on the device in one library call (tn_temper, tnac4o_amd/temper.py).  Runs NO contraction and needs no
         boundary MPS; the solver's own beta plays no part.
@@ -1186,7 +1201,13 @@ class tnac4o:
         block of rounds_per_call rounds in the order sweep, cluster, swap -- the generator's stream then depends on rounds_per_call,
         the law does not, and with given uniforms neither does the result.  rounds_per_call: rounds per library call (None: planned
         from the free device memory; the sweep's uniform numbers, rounds sweeps Nx Ny M 8 bytes, are the large item).  Everything is
-        validated before any device work (ValueError).
+        validated before any device work (ValueError).  seed: None, or an integer in [0, 2^64) as sample_boltzmann's (not with
+        uniforms: ValueError): the three arrays are filled on the device block by block, every number a function of the seed and its
+        logical position with r the GLOBAL round -- sweep (r, j, k, m): U(seed, stream of (temper sweep, (r sweeps + j) Ny*Nx + k), m);
+        cluster (r, t', p): stream of (temper cluster, r Tc + t'), p; swap (r, c, t): stream of (temper swap, r R + c), t -- so the
+        result depends on rounds_per_call no more than with given uniforms; with pairs=None the chain pairing of round r comes from
+        the keys U(seed, stream of (temper pairing, r), c), c < R, by exchange_clusters' rule, on the host; explicit pairs are allowed.
+        numpy's global generator is not touched.  The same seed gives the same numbers in every call: vary it.
         Stores states (M, Nx*Ny) in model cell order and energy (M,) (returned) in the bits relax_samples gives, temper_betas (T,),
         temper_index (M,) = the temperature index every row ends at, temper_beta (M,) = its beta, temper_swap_accepted and
         temper_swap_attempted (T - 1,) over all rounds.  With record=True also temper_energy_trace (rounds, T, R) = the energy at
@@ -1196,9 +1217,10 @@ class tnac4o:
         calculate_overlap_* calls would pool; keep=t leaves only the R rows that end at temperature index t (chains ascending) in
         states and energy, so that those calls see one temperature (temper_index and temper_beta still describe all M rows)."""
         from . import temper
-        return temper.temper_samples(self, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, record, keep, rounds_per_call)
+        return temper.temper_samples(self, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, record, keep, rounds_per_call,
+                                     seed)
 
-    def anneal_population(self, betas, sweeps=1, M=None, uniforms=None, record=False, log2Z0=None, steps_per_call=None):
+    def anneal_population(self, betas, sweeps=1, M=None, uniforms=None, record=False, log2Z0=None, steps_per_call=None, seed=None):
         """Population annealing (Hukushima, Iba; Machta; Wang, Machta, Katzgraber): a population of M configurations is taken along the
         schedule `betas`, whole steps on the device in one library call (tn_anneal, tnac4o_amd/anneal.py), and log2 Z is
         estimated at every beta of the schedule.  Runs NO contraction and needs no boundary MPS; the solver's own beta plays no part;
@@ -1215,7 +1237,12 @@ class tnac4o:
         by block of steps_per_call steps in the order resample, sweep -- the generator's stream then depends on steps_per_call, the
         law does not, and with given uniforms neither does the result.  steps_per_call: steps per library call (None: planned from
         half the free device memory; the sweep's uniform numbers are the large item).  Everything is validated before any device
-        work (ValueError).
+        work (ValueError).  seed: None, or an integer in [0, 2^64) as sample_boltzmann's (not with uniforms: ValueError): every array
+        is filled on the device, every number a function of the seed and its logical position with s the GLOBAL step -- init (m, k):
+        U(seed, stream of (anneal init, m), k), and the fresh population is made on the device by the same rule; resample (s):
+        stream of (anneal resample, 0), s; sweep (s, j, k, m): stream of (anneal sweep, (s sweeps + j) Ny*Nx + k), m -- so the result
+        depends on steps_per_call no more than with given uniforms, and row m's numbers do not depend on M.  numpy's global generator
+        is not touched.  The same seed gives the same numbers in every call: vary it.
         Stores states (M, Nx*Ny) in model cell order and energy (M,) (returned) in the bits relax_samples gives, and
         anneal_betas (K,);
         anneal_log2Z (K,) = log2Z0 plus the running sum of log2(W_s / M) - (betas[s] - betas[s-1]) Emin_s / ln 2.  log2 Z here means
@@ -1238,7 +1265,7 @@ class tnac4o:
         probability, sample_log2Z, log2Z_lower and log2Z_estimate are set to None, as temper_samples does.  rhoT, degeneracy and every
         thermal and scored attribute are left alone."""
         from . import anneal
-        return anneal.anneal_population(self, betas, sweeps, M, uniforms, record, log2Z0, steps_per_call)
+        return anneal.anneal_population(self, betas, sweeps, M, uniforms, record, log2Z0, steps_per_call, seed)
 
     # ------------------------------------------------------------------------------------ thermal marginals (GPU)
     def calculate_marginals(self, Dmax=32, tolS=1e-16, tolV=1e-10, max_sweeps=20, graduate_truncation=True):
