@@ -763,6 +763,47 @@ int tn_anneal(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int6
  * stream0 + rows above 2^64, and (rows, cols > 0) out null or not aligned to 8 bytes. */
 int tn_uniforms(uint64_t seed, uint64_t stream0, uint64_t first, int64_t rows, int64_t cols, double* out, int64_t ld, void* stream);
 
+/* ---- K15: droplets of configurations relative to a reference (the search of the reference does this per branch, on the host; for
+ * stored states there is no counterpart: tnac4o.calculate_droplets) ------------------------------------------------------------------
+ * tn_droplets: rows (DEVICE) = M rows of nbits bits in tn_cluster_exchange's layout at a stride of ldr words, ref (DEVICE) = one such
+ * row of ceil(nbits / 64) words; neither is written.  Words behind a row and bits beyond nbits (of rows and of ref) are ignored.  The
+ * graph (DEVICE) is tn_cluster_exchange's CSR, rowptr (nbits + 1 int32), cols (nnz int32), with one coupling per arc, vals (nnz
+ * doubles), and the fields, field (nbits doubles, or NULL: none): the arcs of bit i are e = max(rowptr[i], 0) .. min(rowptr[i+1], nnz) - 1
+ * (an empty range when that is none), an arc to a neighbour outside [0, nbits) is skipped for growth and for energy: nothing read from
+ * these arrays or from rows is used as an index unchecked.
+ * For row m: D = row XOR ref (masked).  Its droplets are the sets C reachable along listed arcs through bits of D -- for a CSR that
+ * lists every coupling in both directions: the connected components of the subgraph induced on D; a one-way arc is followed as it is
+ * given, for growth and for energy --, grown one after the other, each from the lowest bit of D that no earlier droplet holds (its
+ * root): droplets are numbered 0, 1, ... by ascending root.  A bit that an earlier droplet holds is not taken again (one-way arcs can
+ * lead into one): the droplets are a partition of D for every CSR.  With g_i = 2 ref_i - 1 the excitation energy of C is
+ *   dE_C = 2 (sum over i in C of (-field[i] g_i + sum over the arcs e = (i -> j) of i with j not in D of -vals[e] g_i g_j)),
+ * which for a symmetric CSR of an Ising energy E = sum_{i<j} J_ij s_i s_j + sum_i h_i s_i is E(ref with C flipped) - E(ref): an arc that
+ * leaves C ends outside D, because a neighbour in D belongs to C.  The same walk of the arcs grows C and adds the terms.
+ * Results (DEVICE), per row m, always fully written: count_out[m] = the number of droplets (all of them, also beyond K), diff_out[m] =
+ * popcount(D), largest_out[m] = the largest size (0: none), de_total_out[m] = dE of droplet 0 + dE of droplet 1 + ..., added in this
+ * order from 0.0, over ALL droplets (int32, int32, int32, double).  Per row and slot k < K (root_out, size_out int32, de_out double,
+ * M x K each, NULL allowed when K = 0): the first min(count, K) droplets in root order; the slots behind them hold -1, 0, 0.0.
+ * size_hist (nbits + 1 int64): size_hist[s] is INCREASED by the number of droplets of size s over all rows of the call (all of them,
+ * also beyond K), with integer atomics; the caller zeroes it, calls over slices of the rows accumulate.  labels (M x nbits int32 at a
+ * stride of ldl, or NULL): labels[m ldl + i] = the number of the droplet of row m that holds bit i, -1 where the row equals the
+ * reference; entries i >= nbits of a row are never touched.
+ * Floating point: every term is a coupling or a field times +-1, so for exactly summable values (integers, say) every energy is exact.
+ * Otherwise: the frontier of a growth pass is a level of the breadth-first search from the root; a thread adds the terms of its words'
+ * bits in the order (level, bit ascending, field, arcs as listed), from 0.0; the threads' sums are added in a fixed tree.  The result
+ * is a function of the inputs alone: the same bits for every grid, every schedule and every way of cutting the rows into calls.  An
+ * energy that is zero is +0.0.
+ * Asynchronous on `stream`; no barrier across workgroups, no host synchronisation, no workspace; the only global atomics are the integer
+ * additions to size_hist.  nbits <= 4096: one wave per row, no workgroup barrier; above: one workgroup per row.  The growth is bounded
+ * by construction (at most nbits + 1 passes per droplet, at most popcount(D) droplets); no input makes it spin.
+ * Limits: 0 <= M < 2^31; 1 <= nbits <= 65534; ldr >= ceil(nbits / 64); 0 <= nnz < 2^31; 0 <= K < 2^31, M K < 2^60; with labels:
+ * ldl >= nbits, M ldl < 2^60.
+ * Errors: -1 argument (the message names the limit; a null operand -- cols and vals may be NULL when nnz = 0, the slot arrays when
+ * K = 0, field and labels always), before any launch, nothing is written.  M = 0 is a valid no-op (0, whatever the pointers). */
+int tn_droplets(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint64_t* ref, const int32_t* rowptr, const int32_t* cols,
+                const double* vals, int64_t nnz, const double* field, int64_t K, int32_t* count_out, int32_t* diff_out, int32_t* largest_out,
+                double* de_total_out, int32_t* root_out, int32_t* size_out, double* de_out, int64_t* size_hist, int32_t* labels, int64_t ldl,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,17 @@ def coupling_csr(solver):
     return rowptr.astype(np.int32), dst[order].astype(np.int32)
 
 
+def weighted_coupling_csr(solver):
+    """coupling_csr with the numbers of the energy E(s) = sum_{i<j} J_ij s_i s_j + sum_i J_ii s_i of auxx.energy_Jij on it: (rowptr, cols,
+    vals (nnz,) float64, field (n,) float64) -- vals[e] = the coupling J0[i, j], i < j, of the arc e, which both of its directions carry;
+    field[k] = J0[i, i] of the active spin i at position k.  (tn_droplets reads them: droplets_of_states.py.)"""
+    rowptr, cols = coupling_csr(solver)
+    act = active_spins(solver)
+    J0 = np.asarray(solver.J0, dtype=np.float64)
+    a, b = act[np.repeat(np.arange(act.size), np.diff(rowptr))], act[cols]
+    return rowptr, cols, np.ascontiguousarray(J0[np.minimum(a, b), np.maximum(a, b)]), np.ascontiguousarray(J0.diagonal()[act])
+
+
 def check_pairs(pairs, rounds, M):
     """The pairings of `rounds` rounds over M rows: None -> for each round np.random.permutation(M)[:2 P].reshape(P, 2), P = M // 2, from
     numpy's global generator; else an integer numpy array (rounds, P, 2) with every entry in [0, M) and no index twice within a round.

@@ -1265,3 +1265,54 @@ def uniforms(seed, stream0, first, rows, cols, out=None):
     ld = int(out.stride(0)) if rows > 1 else cols
     check(lib().tn_uniforms(seed, stream0, first, rows, cols, out.data_ptr() if out.numel() else None, ld, _stream()))
     return out
+
+
+def droplets(rows, nbits, ref, rowptr, cols, vals, field=None, K=64, size_hist=None, labels=False):
+    """The droplets of packed rows relative to a reference row (tn_droplets; include/tnpeps.h, K15): rows (M, ld) int64 / uint64 device
+    tensor whose first ceil(nbits / 64) words hold a row of nbits bits, ref a contiguous device tensor of at least that many 64-bit words,
+    layout of tnac4o_amd/overlap.py; rowptr (nbits + 1,), cols (nnz,) int32 and vals (nnz,) float64 device tensors, the CSR of the graph
+    over the bits with one coupling per arc; field None or (nbits,) float64.  K: droplets recorded per row.  size_hist: None = a new
+    zeroed (nbits + 1,) int64 device tensor, or such a tensor, which is ADDED to (calls over slices of the rows accumulate).  labels:
+    also the droplet number of every bit.  Returns a dict of device tensors: count, diff, largest (M,) int32, de_total (M,) float64,
+    root, size (M, K) int32, de (M, K) float64 (the slots behind a row's droplets hold -1, 0, 0.0), size_hist, and labels (M, nbits)
+    int32 (-1 where the row equals the reference) or None."""
+    M, ld = _packed_rows(rows)
+    nbits, K = int(nbits), int(K)
+    nwords = -(-max(nbits, 0) // 64)
+    if rows.shape[1] < nwords:
+        raise ValueError('rows hold %d words, %d bits take %d' % (rows.shape[1], nbits, nwords))
+    if K < 0:
+        raise ValueError('K must not be negative')
+    if not ref.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % ref.device)
+    if ref.element_size() != 8 or ref.is_floating_point() or not ref.is_contiguous() or ref.numel() < nwords:
+        raise TypeError('ref: a contiguous device tensor of at least %d 64-bit integer words' % nwords)
+    p_rowptr = _i32_operand(rowptr, 'rowptr', max(nbits, 0) + 1)
+    p_cols = _i32_operand(cols, 'cols')
+    nnz = int(cols.numel())
+    _need_gpu(vals)
+    if not vals.is_contiguous() or vals.numel() != nnz:
+        raise TypeError('vals: a contiguous device tensor of nnz float64, one per arc')
+    if field is not None:
+        _need_gpu(field)
+        if not field.is_contiguous() or field.numel() != nbits:
+            raise TypeError('field: None or a contiguous device tensor of nbits float64')
+    dev = rows.device
+    if size_hist is None:
+        size_hist = torch.zeros(max(nbits, 0) + 1, dtype=torch.int64, device=dev)
+    elif not size_hist.is_cuda or size_hist.dtype != torch.int64 or not size_hist.is_contiguous() or size_hist.numel() != nbits + 1:
+        raise TypeError('size_hist: None or a contiguous device tensor of nbits + 1 int64')
+    out = {k: torch.empty(M, dtype=torch.int32, device=dev) for k in ('count', 'diff', 'largest')}
+    out['de_total'] = torch.empty(M, dtype=torch.float64, device=dev)
+    out['root'], out['size'] = torch.empty((M, K), dtype=torch.int32, device=dev), torch.empty((M, K), dtype=torch.int32, device=dev)
+    out['de'] = torch.empty((M, K), dtype=torch.float64, device=dev)
+    out['size_hist'] = size_hist
+    out['labels'] = torch.empty((M, max(nbits, 0)), dtype=torch.int32, device=dev) if labels else None
+
+    def ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+
+    check(lib().tn_droplets(ptr(rows), M, nbits, max(ld, nwords), ref.data_ptr(), p_rowptr, p_cols, ptr(vals), nnz, ptr(field), K, ptr(out['count']),
+                            ptr(out['diff']), ptr(out['largest']), ptr(out['de_total']), ptr(out['root']), ptr(out['size']), ptr(out['de']),
+                            size_hist.data_ptr(), ptr(out['labels']), max(nbits, 0), _stream()))
+    return out

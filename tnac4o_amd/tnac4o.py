@@ -1181,6 +1181,31 @@ class tnac4o:
         from . import exchange
         return exchange.exchange_clusters(self, rounds, pairs, uniforms, seed)
 
+    def calculate_droplets(self, reference=None, max_droplets=64, labels=False, states=None, chunk=None):
+        """Decompose configurations into their droplets relative to a reference state (tn_droplets, tnac4o_amd/droplets_of_states.py;
+        DESIGN §23): the spins in which a state differs from the reference fall into connected clusters -- connected along the
+        couplings of J --, and each cluster is one excitation of the reference, with a size and an excitation energy
+        dE = E(reference with the cluster flipped) - E(reference) in the convention of auxx.energy_Jij.  The droplets of a state do not
+        touch one another, so their energies add up to E(state) - E(reference).  Ising only (RMF: ValueError); runs no contraction,
+        needs no boundary MPS and does not depend on the rotation (spins are in model order).
+        reference: None = the stored state of lowest `energy` (the first on ties); an integer = that stored state; an integer numpy
+        array of length L = bits as a row of binary_states() holds them (what the inactive spins hold is ignored).  states: None = the
+        stored states, or an integer array (M, Nx*Ny) of cell states in model cell order, as relax_samples takes them.  max_droplets =
+        K: the droplets recorded per state, the first K by ascending root (the smallest spin of a droplet); everything that is not
+        per droplet counts ALL droplets.  chunk: states per library call (None: what fits half of the free device memory).  Anything
+        else is a ValueError raised before any device work.
+        Stores droplet_count (M,) (returned), droplet_hamming (M,) = the differing spins, droplet_largest (M,), droplet_energy_total
+        (M,) = the sum of dE over all droplets of a state; droplet_roots, droplet_sizes, droplet_energies (M, K): roots are model spin
+        indices, the slots behind a state's droplets hold -1, 0, 0.0; droplet_size_counts (n + 1,) int64, entry s = the droplets of s
+        spins over all states, n = the active spins; droplet_truncated = the states with more than K droplets; droplet_reference (L,)
+        bits (0 at inactive spins) and droplet_reference_energy; droplet_labels (M, L) int32 with labels=True -- the number of the
+        droplet that holds a spin, -1 for a spin that equals the reference or is inactive --, else None.
+        `states`, `energy` and everything else the solver holds are left alone.  Couplings that are exactly summable (integers) give
+        exact energies; otherwise the order of the additions is fixed by the inputs alone: the result does not depend on chunk.
+        More than 65534 active spins: NotImplementedError; there is no host fallback."""
+        from . import droplets_of_states
+        return droplets_of_states.droplets_of_states(self, reference, max_droplets, labels, states, chunk)
+
     def temper_samples(self, betas, rounds=10, sweeps=1, cluster_moves=True, cluster_beta_min=None, pairs=None, uniforms=None, record=False,
                        keep=None, rounds_per_call=None, seed=None):
         """Parallel tempering with isoenergetic cluster moves (PT+ICM: Zhu, Ochoa, Katzgraber) over the stored configurations, whole
