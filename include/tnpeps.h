@@ -804,6 +804,35 @@ int tn_droplets(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, con
                 double* de_total_out, int32_t* root_out, int32_t* size_out, double* de_out, int64_t* size_hist, int32_t* labels, int64_t ldl,
                 void* stream);
 
+/* ---- K16: single-linkage clusters of configurations (no counterpart in the reference: tnac4o.calculate_state_linkage) ---------------
+ * Rows.  rows (DEVICE) = M rows in tn_pair_hist's layout at a stride of ldr words, in one of two forms.  lanes16 = 0: nbits bits per
+ * row, d(a, b) = popcount(a XOR b).  lanes16 = 1: nbits 16-bit lanes per row, d = the number of lanes that differ.  Whatever lies beyond
+ * nbits in the last word is masked.  Words nwords .. ldr-1 are never read (nwords = ceil(nbits / 64), lanes16: ceil(nbits / 4)).
+ * Fold.  With fold = 1 (bits only) the distance is d'(a, b) = min(d, nbits - d).  A state and its global spin flip are then the same
+ * point.
+ * Edge order.  Edges are ordered by the strict total order key(a, b) = (d(a, b), min(a, b), max(a, b)), compared lexicographically.
+ * Tree.  The tree is the unique minimum spanning tree of the complete graph on the M rows under that order.  Kruskal, Prim and Boruvka
+ * all return it, so the result does not depend on the algorithm, grid or run.  It has M - 1 edges, reported in ascending key order:
+ * edge e joins the rows edge_lo[e] < edge_hi[e] at distance edge_dist[e] (DEVICE, int32, M - 1 each; may be NULL when M < 2).
+ * Nearest other row.  For row a it is the b != a that minimises (d(a, b), b): nn_index[a] = b, nn_dist[a] = d(a, b) (DEVICE, int32, M
+ * each; both NULL or both given).  M = 1 writes nn_index = nn_dist = -1.  M <= 1 writes no edge.  M = 0 writes nothing but
+ * rounds_out = 0.
+ * rounds_out (DEVICE, one int32): the number of Boruvka rounds that did work, 1 <= rounds <= ceil(log2 M) for M >= 2, else 0; a
+ * diagnostic (it does not depend on the grid either).
+ * Asynchronous on `stream`, the host never synchronises: a fixed ceil(log2 M) rounds of ordinary launches are queued (a round at least
+ * halves the components); once a device counter says one component is left the kernels of a round return at once.  No barrier across
+ * workgroups and no spinning; integers only; the only atomics are 64-bit atomicMin on the best candidate of a row and on the best
+ * edge of a component (the key d:16 | lo:24 | hi:24), and the counter of the edges.  The pair pass of a round walks the upper triangle
+ * of the pair matrix in 64 x 64 blocks, as tn_pair_hist does, and offers every distance to both of its rows; TN_LINKAGE_WGS overrides
+ * its grid as TN_PAIR_HIST_WGS does (read per call, and by tn_state_linkage_ws_bytes as by the call).
+ * ws: 256-byte aligned, tn_state_linkage_ws_bytes (0 for a shape the call refuses and for M < 2, where ws may be NULL).
+ * Limits: 0 <= M <= 2^24; 1 <= nbits <= 65534; ldr >= nwords; fold only with lanes16 = 0.
+ * Errors: -1 argument (the message names the limit; a null operand; one of nn_index, nn_dist without the other), -3 workspace too small;
+ * both before any launch, nothing is written. */
+int64_t tn_state_linkage_ws_bytes(int64_t M, int64_t nbits, int lanes16);
+int tn_state_linkage(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, int lanes16, int fold, int32_t* nn_index, int32_t* nn_dist,
+                     int32_t* edge_lo, int32_t* edge_hi, int32_t* edge_dist, int32_t* rounds_out, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1316,3 +1316,31 @@ def droplets(rows, nbits, ref, rowptr, cols, vals, field=None, K=64, size_hist=N
                             ptr(out['diff']), ptr(out['largest']), ptr(out['de_total']), ptr(out['root']), ptr(out['size']), ptr(out['de']),
                             size_hist.data_ptr(), ptr(out['labels']), max(nbits, 0), _stream()))
     return out
+
+
+def state_linkage(rows, nbits, lanes16=False, fold=False, nearest=True):
+    """The single-linkage tree of packed rows (tn_state_linkage; include/tnpeps.h, K16): rows (M, ld) int64 / uint64 device tensor whose
+    first ceil(nbits / 64) words (lanes16: ceil(nbits / 4)) hold a row of nbits bits (lanes16: nbits 16-bit lanes), layout of
+    tnac4o_amd/overlap.py; fold: the distance min(d, nbits - d) (bits only).  Returns a dict of int32 device tensors: edge_lo, edge_hi,
+    edge_dist (max(M - 1, 0),), the edges of the minimum spanning tree under the order (d, lo, hi), ascending; nn_index, nn_dist (M,),
+    the nearest other row of every row (None with nearest=False); rounds (1,).  Nothing is synchronised."""
+    M, ld = _packed_rows(rows)
+    nbits = int(nbits)
+    nwords = -(-max(nbits, 0) // (4 if lanes16 else 64))
+    if rows.shape[1] < nwords:
+        raise ValueError('rows hold %d words, %d %s take %d' % (rows.shape[1], nbits, 'lanes' if lanes16 else 'bits', nwords))
+    l16, dev = int(bool(lanes16)), rows.device
+    wsb = int(lib().tn_state_linkage_ws_bytes(M, nbits, l16))
+    ws = workspace(max(wsb, 256), 1)
+    out = {k: torch.empty(max(M - 1, 0), dtype=torch.int32, device=dev) for k in ('edge_lo', 'edge_hi', 'edge_dist')}
+    out['nn_index'] = torch.empty(M, dtype=torch.int32, device=dev) if nearest else None
+    out['nn_dist'] = torch.empty(M, dtype=torch.int32, device=dev) if nearest else None
+    out['rounds'] = torch.empty(1, dtype=torch.int32, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+
+    check(lib().tn_state_linkage(rows.data_ptr() if M else ws.data_ptr(), M, nbits, max(ld, nwords), l16, int(bool(fold)),
+                                 out['nn_index'].data_ptr() if nearest and M else None, out['nn_dist'].data_ptr() if nearest and M else None,
+                                 ptr(out['edge_lo']), ptr(out['edge_hi']), ptr(out['edge_dist']), out['rounds'].data_ptr(), ws.data_ptr(), wsb, _stream()))
+    return out

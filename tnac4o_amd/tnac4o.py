@@ -1206,6 +1206,32 @@ class tnac4o:
         from . import droplets_of_states
         return droplets_of_states.droplets_of_states(self, reference, max_droplets, labels, states, chunk)
 
+    def calculate_state_linkage(self, threshold=None, kind=None, symmetric=None, states=None):
+        """Single-linkage hierarchical clustering of the configurations by Hamming distance (tn_state_linkage,
+        tnac4o_amd/linkage.py): which of the M states belong together, how many valleys there are, how big they are and
+        at what distance they merge.  The dendrogram is the minimum spanning tree of the complete graph on the states under the strict
+        total order key(a, b) = (d(a, b), min(a, b), max(a, b)); cut at height t it gives the connected components of "differ in at
+        most t".  The device finds the tree (all pairs, Boruvka rounds, exact integers: the result does not depend on the grid or the
+        run); runs no contraction.
+        kind: 'spin' d = the active spins that differ (Ising only; RMF: ValueError); 'cell' d = the cells in another state (any
+        mode); None = 'spin' for Ising, 'cell' for RMF.  symmetric: fold the distance, d' = min(d, N - d), so that a state and its
+        global spin flip are one point; 'spin' only; None = True exactly when the model has no fields (the diagonal of J0 is zero).
+        states: None = the stored states, or an integer array (M, Nx*Ny) of cell states in model cell order, as calculate_droplets
+        takes them.  threshold: None or an integer t >= 0.  Anything else, and no stored states, is a ValueError raised before any
+        device work.
+        Stores linkage_pairs (M-1, 2) int64 = the edges (lo < hi) in ascending key order, linkage_distance (M-1,) int64 = the merge
+        heights, ascending (returned); nearest_state, nearest_distance (M,) = for every state the b != a that minimises (d, b) (-1 for
+        a single state); linkage_cluster_counts (N+1,) int64, entry t = the clusters when all pairs at distance <= t are joined;
+        linkage_matrix (M-1, 4) float64 in the format of scipy's linkage (merge i creates cluster M + i, the smaller id first; for
+        scipy's dendrogram and fcluster); linkage_kind, linkage_symmetric, linkage_rounds (the rounds the device needed).  With a
+        threshold also state_cluster_labels (M,) (clusters numbered by their ascending smallest member), state_cluster_sizes,
+        state_cluster_first, and, when `energy` has one entry per state, state_cluster_representative (the member of lowest energy,
+        the first on ties) and state_cluster_energy_min, else None for both; without a threshold these five are None.
+        More than 65534 spins (cells) or more than 2^24 states: NotImplementedError naming the limit; there is no host fallback.
+        Changes nothing else."""
+        from . import linkage
+        return linkage.state_linkage(self, threshold, kind, symmetric, states)
+
     def temper_samples(self, betas, rounds=10, sweeps=1, cluster_moves=True, cluster_beta_min=None, pairs=None, uniforms=None, record=False,
                        keep=None, rounds_per_call=None, seed=None):
         """Parallel tempering with isoenergetic cluster moves (PT+ICM: Zhu, Ochoa, Katzgraber) over the stored configurations, whole
