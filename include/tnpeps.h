@@ -833,6 +833,52 @@ int64_t tn_state_linkage_ws_bytes(int64_t M, int64_t nbits, int lanes16);
 int tn_state_linkage(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, int lanes16, int fold, int32_t* nn_index, int32_t* nn_dist,
                      int32_t* edge_lo, int32_t* edge_hi, int32_t* edge_dist, int32_t* rounds_out, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- K17: exact heat bath and quench of whole lattice lines (no counterpart in the reference: tnac4o.relax_lines) -------------------
+ * tn_line_sweep: `sweeps` sweeps of updates of whole rows and columns over M configurations, IN PLACE in states (DEVICE, M x Nx*Ny
+ * int16, lattice order of this rotation).  cells, states, energy_out, the treatment of a state outside [0, q) as a neighbour and the
+ * independence of a sample's result from M, the grid and the cut into calls are tn_cell_sweep's (K10).
+ * The chain.  With the rows above and below given, row ny is a chain of cells x = 0 .. Nx-1 (B: the cell below; U from up_map and the
+ * state above as in K10):
+ *     side energy  a_x(s) = ((1.0 Es[s] + E4_x[s e4cols + U]) + B.E4[sb B.e4cols + (B.up_map ? B.up_map[s] : s)])
+ *     coupling     E1_x[s_x e1cols + r_{x-1}(s_{x-1})],  r_{x-1}(s') = left_map_x ? left_map_x[s'] : s'
+ * with these additions in this order, a term absent at a lattice edge.  A column is the same with (E1, left_map, nx) and (E4, up_map,
+ * ny) exchanged.  A row pass updates the rows of even ny, then those of odd ny (one launch per parity); a column pass the columns of
+ * even nx, then odd.  lines = 0: a sweep is one row pass (P = 1); 1: one column pass (P = 1); 2: a row pass, then a column pass (P = 2).
+ * mode 0, heat bath at beta: the whole line is drawn from its conditional Boltzmann law by forward filtering and backward sampling in
+ * the LINEAR domain: lambda_0(s) = w_0(s), lambda_x(s) = w_x(s) sum_r F_x[r] T_x[s, r] with w_x(s) = exp(-beta (a_x(s) - min_s a_x)),
+ * T_x[s, r] = exp(-beta (E1_x[s, r] - min E1_x)) and the column messages F_x[r] = (sum of lambda_{x-1}(s') over r_{x-1}(s') = r) /
+ * max_s lambda_{x-1}; cell Nx-1 is drawn from the weights lambda_{Nx-1}(s), then x = Nx-2 .. 0 from lambda_x(s) T_{x+1}[s_{x+1}, r_x(s)],
+ * every draw by K10's rule (running sum in ascending s, t = u W, the first s with c_s >= t and w_s > 0, else the last s with w_s > 0).
+ * uniforms (DEVICE): sweeps * P * Nx*Ny rows of ldu >= M doubles in [0, 1); the number of (sweep j, pass p, cell k, sample m) is
+ * uniforms[((j P + p) Nx Ny + k) ldu + m].  The sums of the messages and of the running sum are not the bits of a host summation: a
+ * draw closer to a boundary of the running sum than the rounding of these sums may differ from a reference.
+ * Range guard (mode 0, sweeps > 0): beta (max - min) <= 300 for every chain table of the directions in use (E1 for rows, E4 for
+ * columns).  Under it the largest lambda of a cell is at least 1e-131 after normalisation and nothing that underflows matters.  The
+ * guard needs the tables, which live on the device: in mode 0 the call reduces their ranges, reads them back and WAITS for the stream
+ * once, before any state is touched.  A call beyond the bound returns -1 with a message naming the range guard; it has then written
+ * the head of ws (the table of the cells and the ranges) and nothing else.
+ * mode 1, quench: the same recursion in (min, +): Lambda_0(s) = a_0(s), Lambda_x(s) = a_x(s) + min_r (mu_x[r] + E1_x[s, r]), mu_x[r] =
+ * min of Lambda_{x-1}(s') over r_{x-1}(s') = r, E* = min_s Lambda_{Nx-1}(s).  The energy of the line as it stands is c_0 = a_0(s_0),
+ * c_x = a_x(s_x) + (c_{x-1} + E1_x[s_x, r]), +inf when one of its cells holds a state outside its range.  The line moves only if
+ * E* < c_{Nx-1} strictly, and then to the minimiser that is smallest in the lexicographic order of (s_{Nx-1}, .., s_0): from the far end,
+ * the smallest state attaining min_s (Lambda_x(s) + E1_{x+1}[s_{x+1}, r_x(s)]).  No exponentials, no guard, the bits of the same
+ * expressions in numpy; uniforms must be NULL; asynchronous, no host synchronisation.
+ * Results (DEVICE): energy_out (M) as K10's (the same bits); moves_out / last_moves_out (M int32, may be NULL) = the number of CELLS
+ * whose state changed over the call / in its last sweep.  sweeps = 0 updates nothing and only writes the outputs.
+ * ws: tn_line_sweep_ws_bytes (0 for a shape the call refuses): the table of the cells, one flag per (cell, sample), the ranges, a
+ * 32 MiB arena of transfer tables and a 16 MiB scratch of the workgroups that cannot keep their messages in LDS -- only the flags
+ * depend on M.  T_x is computed once per call into the arena (transposed) for the tables that fit TN_LINE_SWEEP_TABLES bytes (read
+ * per call; default and at most 33554432, 0: none); every other table evaluates the same expression where it is read: the same bits.
+ * No barriers across workgroups and no atomics.  Limits: q <= 32767, M < 2^31, Nx Ny < 2^26, and q_max + the chain-table columns of
+ * one line <= 2^21 (the vectors of one sample).
+ * Errors: -1 argument (mode; lines; beta <= 0 or not finite in mode 0; uniforms NULL in mode 0 or not NULL in mode 1; ldu < M;
+ * sweeps < 0; M; a null pointer; a bad cell; the range guard), -3 workspace too small; all but the range guard before any launch,
+ * nothing is written. */
+int64_t tn_line_sweep_ws_bytes(int64_t Nx, int64_t Ny, int64_t M);
+int tn_line_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int16_t* states, int mode, int lines, double beta, int64_t sweeps,
+                  const double* uniforms, int64_t ldu, double* energy_out, int32_t* moves_out, int32_t* last_moves_out, void* ws,
+                  int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

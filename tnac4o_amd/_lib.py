@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libtnpeps.so')
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['api.hip', 'gemm_f64.hip', 'rank_update.hip', 'factor_products.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip', 'sampler.hip', 'overlap.hip', 'relax.hip', 'exchange.hip', 'temper.hip', 'anneal.hip', 'rng.hip', 'droplets.hip', 'linkage.hip']
+SOURCES = ['api.hip', 'gemm_f64.hip', 'rank_update.hip', 'factor_products.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip', 'sampler.hip', 'overlap.hip', 'relax.hip', 'exchange.hip', 'temper.hip', 'anneal.hip', 'rng.hip', 'droplets.hip', 'linkage.hip', 'lines.hip']
 
 _i64, _f64, _int, _ptr = C.c_int64, C.c_double, C.c_int, C.c_void_p
 
@@ -121,6 +121,8 @@ SIGNATURES = {
                     _ptr]),
     'tn_state_linkage_ws_bytes': (_i64, [_i64, _i64, _int]),
     'tn_state_linkage': (_int, [_ptr, _i64, _i64, _i64, _int, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr]),
+    'tn_line_sweep_ws_bytes': (_i64, [_i64, _i64, _i64]),
+    'tn_line_sweep': (_int, [_i64, _i64, _ptr, _i64, _ptr, _int, _int, _f64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr]),
     'tn_profile_enable': (None, [C.c_uint]),
     'tn_profile_reset': (None, []),
     'tn_profile_sample': (None, [C.c_uint]),

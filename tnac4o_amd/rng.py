@@ -31,6 +31,7 @@ TEMPER_PAIRING = 8       # temper_samples pairing keys (rounds, R)
 ANNEAL_INIT = 9          # anneal_population init (M, ncell)
 ANNEAL_RESAMPLE = 10     # anneal_population resample (K - 1,): row 0
 ANNEAL_SWEEP = 11        # anneal_population sweep (K - 1, sweeps, ncell, M)
+RELAX_LINE = 12          # relax_lines sweep (sweeps, passes, ncell, M)
 
 
 def check_seed(seed):

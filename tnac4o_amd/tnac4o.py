@@ -1150,6 +1150,52 @@ class tnac4o:
         self.probability = self.sample_log2Z = self.log2Z_lower = self.log2Z_estimate = None
         return energy
 
+    def relax_lines(self, sweeps=1, mode='heat_bath', lines='both', beta=None, states=None, uniforms=None, chunk=None, max_sweeps=64, seed=None):
+        """Move configurations by EXACT updates of whole lattice rows and columns (tn_line_sweep, tnac4o_amd/lines.py): with
+        the rows above and below given a row is a chain of cells, so its conditional law is sampled exactly by one forward pass of
+        messages and one backward pass of draws, and its conditional minimum found by the same recursion in (min, +); a column
+        likewise.  The move flips droplets that span a line, which no sequence of cell moves of relax_samples does at low
+        temperature.  Runs NO contraction and needs no boundary MPS; works in the rotation that is set, Ising and RMF.  Arguments,
+        storage and side effects are relax_samples'; the differences:
+        lines: 'rows' -- a sweep is one row pass: the rows of even ny, then those of odd ny --, 'columns' -- the columns of even nx,
+        then odd --, or 'both': a row pass, then a column pass (P = 2 passes per sweep, else P = 1).  Anything else: ValueError.
+        mode='heat_bath': every line is drawn from its conditional Boltzmann law at `beta`; a sweep leaves the Boltzmann law
+        invariant.  uniforms: None = np.random.rand(sweeps, P, Ny*Nx, M), or a (sweeps, P, Ny*Nx, M) float64 array / device tensor in
+        [0, 1): sweep, pass, cell in walk order of the current rotation, sample.  seed: the numbers are filled on the device, number
+        (sweep j, pass p, cell k, configuration m) is U(seed, stream of (relax line, (j P + p) Ny*Nx + k), m).  The heat bath works in
+        the linear domain and is safe while beta (max - min) <= 300 for every chain table (the cell's coupling table to its left
+        neighbour for rows, to its upper neighbour for columns): beyond that a ValueError naming the range guard is raised before any
+        device work.
+        mode='quench': a line goes to its conditional minimum -- ties to the minimiser that is smallest from the far end of the line
+        -- when that lowers the energy strictly, and stays otherwise; the energy never rises.  sweeps=None repeats sweeps until no
+        line of any configuration moves in the last one, at most max_sweeps: the result is a minimum against every change confined
+        to one row or one column (with lines='both'), in particular a fixed point of relax_samples' cell quench.
+        Stores states, energy (returned), relax_energy_before, relax_moves (M,) = the cells whose state changed, relax_converged,
+        relax_sweeps; probability, sample_log2Z, log2Z_lower and log2Z_estimate are set to None."""
+        from . import lines as ln, rng, sampler
+        lib_mode, lib_lines, nsw, b = ln.check_line_arguments(mode, lines, sweeps, self.beta if beta is None else beta, uniforms, max_sweeps, seed)
+        seed = rng.check_seed(seed)
+        st = sampler.check_states(self.states if states is None else states, self._cell_sizes()[self.order])
+        M = st.shape[0]
+        if lib_mode == 0:
+            if seed is None:
+                uniforms = ln.check_line_uniforms(uniforms, nsw, ln.passes(lines), self.Nx * self.Ny, M)
+            ln.check_range_guard(self, lines, b)
+        if chunk is not None:
+            sampler.chunk_slices(M, chunk)
+        self.logger.info('Relaxing %d configurations by lines (%s, %s) with beta = %.2f', M, mode, lines, b)
+        rot = np.empty_like(st)
+        rot[:, self.order] = st                                  # the inverse of _store_result's states[:, order]
+        new, energy, before, moves, last, swept = ln.lines_native(self, rot, lib_mode, lib_lines, b, nsw, uniforms=uniforms, chunk=chunk,
+                                                                  max_sweeps=max_sweeps, seed=seed)
+        self.states = new[:, self.order]
+        self.energy = energy
+        self.relax_energy_before, self.relax_moves = before, moves
+        self.relax_converged = (last == 0) & (swept > 0)
+        self.relax_sweeps = int(swept)
+        self.probability = self.sample_log2Z = self.log2Z_lower = self.log2Z_estimate = None
+        return energy
+
     def exchange_clusters(self, rounds=1, pairs=None, uniforms=None, seed=None):
         """Move the stored configurations by isoenergetic cluster moves on pairs of them (Houdayer's move in its form for arbitrary
         graphs; tn_cluster_exchange, tnac4o_amd/exchange.py): for a pair of replicas a, b one of the spins in which they differ is
