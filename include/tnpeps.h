@@ -217,7 +217,11 @@ int tn_mpo_from_factor_ops(const double* F, const int32_t* dmap, const int32_t* 
  *   F : (q, nl, nu)     non-zero factor of the PEPS tensor, T[s,l,d,r,u] = F[s,l,u] [d=dmap[s]] [r=rmap[s]]
  *   per branch kk: pref[kk], suf[kk], lidx[kk], uidx[kk] (int32).  Out: P (nb, q) normalised, minP (nb).
  *   parent_log2p (nb) / log2p_out (nb, q), both or neither: log2p_out[kk, s] = log2(P[kk, s]) + parent_log2p[kk], the expansion of
- *   the branch log-probabilities of tnac4o.py:450-453 in the same launch. */
+ *   the branch log-probabilities of tnac4o.py:450-453 in the same launch: -inf where P is 0 or the parent is -inf, never NaN.
+ * A NaN in one row d of one prefix's T1 stays in the branches of that prefix: their states with dmap[s] = d come back NaN (the other
+ * entries of those tables mean nothing) and their flag is -1; every other branch is unchanged bit for bit.
+ * Limit (argument error otherwise): (p Dr + Dr br + p br + q) * 8 <= 150 KiB of LDS.  tn_calc_pn, tn_sample_pn, tn_score_pn,
+ * tn_env_rr_batched and tn_env_rl_batched check their arguments before the launch: a refused call (-1) writes nothing. */
 int tn_calc_pn(const double* T1, const double* RR, const double* F, const int32_t* dmap, const int32_t* rmap,
                const int32_t* pref, const int32_t* suf, const int32_t* lidx, const int32_t* uidx, int64_t nb,
                int64_t q, int64_t nl, int64_t nu, int64_t p, int64_t Dr, int64_t br, double* P, double* minP,
@@ -254,7 +258,8 @@ int tn_score_pn(const double* T1, const double* RR, const double* F, const int32
  * group, in candidate order inside a group: E, log2p, deg, pos (their position in the candidate list), group g = members starts[g] ..
  * starts[g+1]-1 (ngroups + 1 offsets).  Per group: rep_pos_out = position of the FIRST member of minimal energy, deg_out = sum of the
  * degeneracies of the members within min_dEng of that minimum, log2p_out = the representative's log2p when it is alone in that set,
- * else the mean over the set added up in member order. */
+ * else the mean over the set added up in member order.  An empty group (starts[g] == starts[g+1]) reads no member and returns
+ * rep_pos_out = -1, deg_out = 0, log2p_out = -inf. */
 int tn_merge_groups(const double* E, const double* log2p, const int64_t* deg, const int64_t* pos, const int64_t* starts, int64_t ngroups,
                     double min_dEng, int64_t* rep_pos_out, int64_t* deg_out, double* log2p_out, void* stream);
 /* ---- K9: per-item power-of-two normalisation of a batch of environments (tnac4o.py:533, 1781):

@@ -91,6 +91,12 @@ __global__ __launch_bounds__(256) void merge_groups_kernel(const double* __restr
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= ng) return;
     const int64_t lo = starts[g], hi = starts[g + 1];
+    if (lo >= hi) {                                    // an empty group has no member to read: no representative, nothing merged
+        rep_pos[g] = -1;
+        degn[g] = 0;
+        lpn[g] = -std::numeric_limits<double>::infinity();
+        return;
+    }
     double emin = E[lo];
     int64_t first = lo;
     for (int64_t i = lo + 1; i < hi; ++i)
