@@ -1,7 +1,8 @@
 """Reference, inputs and expected exit columns for the direct tests of the un-pivoted rank-revealing exit of tn_qr / tn_qr_batched /
 tn_site_qr (reveal_check and qr_factor_impl in csrc/qr.hip), restated from the wording of include/tnpeps.h.  numpy only, no GPU.
 
-- householder_qr_ld(M): un-pivoted Householder QR in np.longdouble with diag(R) >= 0: Q (m x k), R (k x n), k = min(m, n).
+- householder_qr_ld(M): un-pivoted Householder QR in np.longdouble with diag(R) >= 0: Q (m x k), R (k x n), k = min(m, n).  Its two
+  halves, reflect_columns (some reflections, in place) and accumulate_q, also serve the panel steps of tests/qr_pivot_ref.py.
 - exit_reference(M, rank_tol, frob): the exit rule on the reference's R.  With P = ceil(k / 32) panels there is no exit unless P > 2;
   the checkpoints lie behind the panels p = 1, 3, ... with p + 1 < P, i.e. at j1 = 64, 128, ...; "left" is the largest squared column
   norm of R[j1:, j1:] (frob: the sum of them), the scale the same measure over the columns of the input; the factorisation stops at the
@@ -18,6 +19,8 @@ tn_site_qr (reveal_check and qr_factor_impl in csrc/qr.hip), restated from the w
 - MARGIN: every checkpoint ratio of every input and site lies outside [1 / MARGIN, MARGIN] (tests/test_qr_exit_host.py), so that a
   disagreement about the exit column can never be a rounding tie.
 reference(name) / site_reference(name, side) keep M (longdouble) and its R per process; q_reference(name) adds Q.
+- check_factors(ref, Q, R, keff, ...): what a (possibly truncated) factorisation from the GPU owes the reference, with the bounds of
+  tests/test_gpu_qr_exit.py and tests/test_gpu_qr_pivot.py.
 """
 import collections
 import functools
@@ -33,13 +36,13 @@ Site = collections.namedtuple('Site', 'core p inner kc rank_tol k k_frob noisy')
 
 
 # ------------------------------------------------------------------------------------------------------------------ the reference
-def householder_qr_ld(M, want_q=True):
-    """(Q, R) of the un-pivoted Householder QR of M in longdouble, diag(R) >= 0; Q is None with want_q=False."""
-    A = np.array(M, dtype=LD)
+def reflect_columns(A, steps):
+    """The first `steps` Householder reflections of the un-pivoted QR, applied in place to the longdouble array A: rows 0 .. steps-1 then
+    hold those rows of R (zeros below the diagonal in the first `steps` columns), A[steps:, steps:] the updated trailing block.  Returns
+    the reflectors [(v, beta) or None], H_j = I - beta v v^T acting on rows j.. ."""
     m, n = A.shape
-    k = min(m, n)
     refl = []
-    for j in range(k):
+    for j in range(steps):
         x = A[j:, j]
         x0 = x[0]
         sigma = x[1:] @ x[1:]
@@ -56,16 +59,29 @@ def householder_qr_ld(M, want_q=True):
         A[j, j] = alpha
         A[j + 1:, j] = 0
         refl.append((v, beta))
-    R = np.triu(A[:k])
-    if not want_q:
-        return None, R
+    return refl
+
+
+def accumulate_q(refl, m):
+    """The first len(refl) columns of H_0 H_1 ... H_{len(refl)-1} (m rows), reflector j acting on rows j.. ."""
+    k = len(refl)
     Q = np.zeros((m, k), dtype=LD)
     Q[np.arange(k), np.arange(k)] = 1
-    for j in range(k - 1, -1, -1):
-        if refl[j] is not None:
-            v, beta = refl[j]
-            Q[j:, j:] -= np.outer(beta * v, v @ Q[j:, j:])
-    return Q, R
+    for i in range(k - 1, -1, -1):
+        if refl[i] is not None:
+            v, beta = refl[i]
+            Q[i:, i:] -= np.outer(beta * v, v @ Q[i:, i:])
+    return Q
+
+
+def householder_qr_ld(M, want_q=True):
+    """(Q, R) of the un-pivoted Householder QR of M in longdouble, diag(R) >= 0; Q is None with want_q=False."""
+    A = np.array(M, dtype=LD)
+    m, n = A.shape
+    k = min(m, n)
+    refl = reflect_columns(A, k)
+    R = np.triu(A[:k])
+    return (accumulate_q(refl, m) if want_q else None), R
 
 
 def _measure(c2, frob):
@@ -182,11 +198,15 @@ def _orth(g, m, n):
     return np.linalg.qr(g.standard_normal((m, n)))[0]
 
 
-def centre_matrix(name, rows, cols):
-    """A random rows x cols matrix with singular values spread evenly over [0.8, 1.25]."""
-    g = _rng(99, sorted(SITES).index(name))
+def spread_matrix(g, rows, cols):
+    """A random rows x cols matrix from the generator g with singular values spread evenly over [0.8, 1.25]."""
     r = min(rows, cols)
     return (_orth(g, rows, r) * np.linspace(0.8, 1.25, r)[None, :]) @ _orth(g, cols, r).T
+
+
+def centre_matrix(name, rows, cols):
+    """The centre matrix of a site of SITES (see spread_matrix)."""
+    return spread_matrix(_rng(99, sorted(SITES).index(name)), rows, cols)
 
 
 def site_operands(name, side):
@@ -238,3 +258,32 @@ def lapack_deviation(name, keff):
     cn = np.sqrt(np.asarray(reference(name).col2, dtype=np.float64))
     dR = np.asarray(R[:keff] - Rl[:keff], dtype=np.float64)
     return float(np.abs(Q[:, :keff] - Ql[:, :keff]).max()), float((np.sqrt((dR * dR).sum(0)) / cn).max())
+
+
+# ------------------------------------------------------------------------------------------------------------------ what a factorisation owes its reference
+TOL = 5e-14
+
+
+def check_factors(ref, Q, R, keff, rank_tol, frob, trailing2, noisy, label):
+    """Everything a (possibly truncated) factorisation M ~ Q R owes the reference `ref` of M; returns ||M - Q R||_F (longdouble)."""
+    m, n = ref.M.shape
+    full = min(m, n)
+    print(label, 'keff', keff)
+    assert Q.shape == (m, keff) and R.shape == (keff, n), label
+    assert np.isfinite(Q).all() and np.isfinite(R).all(), label
+    orth = np.abs(Q.T @ Q - np.eye(keff)).max()
+    print(label, 'orthogonality', orth)
+    assert orth < TOL, label
+    assert np.abs(np.tril(R[:, :keff], -1)).max() == 0.0 and (np.diag(R) >= 0).all(), label
+    E = ref.M - Q.astype(LD) @ R.astype(LD)
+    res = np.sqrt((E * E).sum(0))
+    cn = np.sqrt(ref.col2)
+    scale = np.sqrt(ref.col2.sum()) if frob else cn.max()
+    bound = TOL * cn + (LD(rank_tol) * scale * (1 + LD(1e-6)) if keff < full else 0)
+    print(label, 'largest residual / bound', float((res / np.where(bound > 0, bound, 1)).max()))
+    assert (res <= bound).all(), label
+    fro2 = float((E * E).sum())
+    if keff < full and noisy:
+        print(label, 'dropped block: ||M - Q R||_F^2 / reference - 1', fro2 / trailing2 - 1)
+        assert abs(fro2 - trailing2) <= 1e-5 * trailing2, label
+    return float(np.sqrt(LD(fro2)))

@@ -17,8 +17,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 LD = np.longdouble
-TOL = 5e-14
 LAPACK_FACTOR = 8.0
+check_factors = qx.check_factors
 
 
 def dev(x):
@@ -59,31 +59,6 @@ def run_qr(ops, M, rank_tol, colmajor):
         T, Q, R = dev(M), nan(m, k), nan(k, n)
     _, _, keff = ops.qr_into(T, Q, R, rank_tol=rank_tol)
     return host(Q)[:, :keff], host(R)[:keff], keff
-
-
-def check_factors(ref, Q, R, keff, rank_tol, frob, trailing2, noisy, label):
-    """Everything a (possibly truncated) factorisation M ~ Q R owes the reference `ref` of M; returns ||M - Q R||_F (longdouble)."""
-    m, n = ref.M.shape
-    full = min(m, n)
-    print(label, 'keff', keff)
-    assert Q.shape == (m, keff) and R.shape == (keff, n), label
-    assert np.isfinite(Q).all() and np.isfinite(R).all(), label
-    orth = np.abs(Q.T @ Q - np.eye(keff)).max()
-    print(label, 'orthogonality', orth)
-    assert orth < TOL, label
-    assert np.abs(np.tril(R[:, :keff], -1)).max() == 0.0 and (np.diag(R) >= 0).all(), label
-    E = ref.M - Q.astype(LD) @ R.astype(LD)
-    res = np.sqrt((E * E).sum(0))
-    cn = np.sqrt(ref.col2)
-    scale = np.sqrt(ref.col2.sum()) if frob else cn.max()
-    bound = TOL * cn + (LD(rank_tol) * scale * (1 + LD(1e-6)) if keff < full else 0)
-    print(label, 'largest residual / bound', float((res / np.where(bound > 0, bound, 1)).max()))
-    assert (res <= bound).all(), label
-    fro2 = float((E * E).sum())
-    if keff < full and noisy:
-        print(label, 'dropped block: ||M - Q R||_F^2 / reference - 1', fro2 / trailing2 - 1)
-        assert abs(fro2 - trailing2) <= 1e-5 * trailing2, label
-    return float(np.sqrt(LD(fro2)))
 
 
 # ------------------------------------------------------------------------------------------------------------------ tn_qr
