@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-/* version of this C-ABI, currently 23 (bumped whenever a signature below changes; the binding checks it at load time) */
+/* version of this C-ABI, currently 26 (bumped whenever a signature below changes; the binding checks it at load time) */
 int tn_version(void);
 /* copies the hash of the sources the library was built from (set by the build recipe) into buf; returns its length */
 int tn_build_id(char* buf, int n);
@@ -883,6 +883,24 @@ int64_t tn_line_sweep_ws_bytes(int64_t Nx, int64_t Ny, int64_t M);
 int tn_line_sweep(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int16_t* states, int mode, int lines, double beta, int64_t sweeps,
                   const double* uniforms, int64_t ldu, double* energy_out, int32_t* moves_out, int32_t* last_moves_out, void* ws,
                   int64_t ws_bytes, void* stream);
+
+/* ---- K18: per-row sums of the pairwise distances of a set of packed rows (no counterpart in the reference: the jackknife errors of the
+ * overlap moments, tnac4o.calculate_overlap_errors) -------------------------------------------------------------------------------------
+ * tn_pair_rowsums: the pair matrix of tn_pair_hist (K9) reduced per ROW instead of per distance bin.  Rows, lanes16, the masking of the
+ * last word, ldr and weights (DEVICE, M uint32; NULL = all 1) are exactly those of tn_pair_hist.  out (DEVICE, 16-byte aligned, M x 6
+ * entries of two uint64: lo, hi), row-major.  For row a, with d = dist(a, b) and the sum running over every b != a in 0 .. M-1:
+ *     out[a][0] = sum w_b,   out[a][k] = sum w_b d^k for k = 1 .. 4,   out[a][5] = sum w_b |nbits - 2 d|,
+ * each entry the exact integer lo + 2^64 hi.  The row's own weight does not enter its sums; a row of weight 0 still gets its sums.  A
+ * row b != a with the same content has d = 0: it enters entries 0 and 5 only.  Every entry of every row is written: M = 1 gives six
+ * zeros, M = 0 writes nothing.  An integer function of the inputs: bit-identical for every grid, split and run (no atomics and no
+ * floating point: the full square of the pair matrix in 64 x 64 tiles, the sums of a row in registers, the 16 threads of a row added
+ * with carry, one slab per segment of the columns in ws, summed with carry).
+ * ws: 16-byte aligned, tn_pair_rowsums_ws_bytes (which reads TN_PAIR_ROWSUMS_WGS as the call does; 0 for a shape the call refuses).
+ * Asynchronous on `stream`.  Limits: 0 <= M < 2^31 and 1 <= nbits <= 65535: then w d^2 < 2^64 and w d^4 < 2^96, so a row's sum stays
+ * below 2^127.  Errors: -1 argument (the message names the limit), -3 workspace too small; both before any launch, nothing is written. */
+int64_t tn_pair_rowsums_ws_bytes(int64_t M, int64_t nbits, int lanes16);
+int tn_pair_rowsums(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, int lanes16, uint64_t* out, void* ws,
+                    int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

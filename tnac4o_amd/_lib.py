@@ -106,6 +106,8 @@ SIGNATURES = {
     'tn_pair_hist': (_int, [_ptr, _i64, _i64, _i64, _ptr, _int, _ptr, _ptr, _i64, _ptr]),
     'tn_pair_moments_ws_bytes': (_i64, [_i64, _i64, _i64, _int]),
     'tn_pair_moments': (_int, [_ptr, _i64, _i64, _i64, _i64, _ptr, C.c_uint32, _int, _ptr, _ptr, _i64, _ptr]),
+    'tn_pair_rowsums_ws_bytes': (_i64, [_i64, _i64, _int]),
+    'tn_pair_rowsums': (_int, [_ptr, _i64, _i64, _i64, _ptr, _int, _ptr, _ptr, _i64, _ptr]),
     'tn_spin_moments_ws_bytes': (_i64, [_i64, _i64, C.c_uint32]),
     'tn_spin_moments': (_int, [_ptr, _i64, _i64, _i64, _ptr, C.c_uint32, _ptr, _i64, _ptr, _i64, _ptr]),
     'tn_cell_sweep_ws_bytes': (_i64, [_i64, _i64, _i64]),
@@ -223,7 +225,7 @@ SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes
                'tn_mpo_from_factor_ops', 'tn_env3_stack', 'tn_env3_stack_ws_bytes', 'tn_stack_cell_law', 'tn_stack_cell_law_ws_bytes',
                'tn_last_error')
 _lib = None
-ABI_VERSION = 25       # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
+ABI_VERSION = 26       # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
 
 
 def lib():

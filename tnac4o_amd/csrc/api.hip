@@ -23,7 +23,7 @@ using namespace tn;
 
 extern "C" {
 
-int tn_version(void) { return 25; }
+int tn_version(void) { return 26; }
 
 #ifndef TN_SRC_HASH
 #define TN_SRC_HASH "unknown"

@@ -1,9 +1,10 @@
-// Exact integer statistics of M packed rows, the samples of tnac4o: three entries, each a persistent grid over the tiles of an upper
-// triangle whose workgroups write partial sums into slabs of the workspace, and a kernel that adds the slabs.  Integer sums
-// throughout: no result depends on the grid, on the tile order or on the run.
+// Exact integer statistics of M packed rows, the samples of tnac4o: four entries, each a persistent grid over the tiles of an upper
+// triangle (tn_pair_rowsums: of the full square) whose workgroups write partial sums into slabs of the workspace, and a kernel that
+// adds the slabs.  Integer sums throughout: no result depends on the grid, on the tile order or on the run.
 //   tn_pair_hist     hist[d] = sum_{a<b} w_a w_b [dist(a, b) = d]                  tnac4o.calculate_overlap_distribution
 //   tn_pair_moments  out[i][j] = sum_{a<b} w_a w_b d_i(a, b) d_j(a, b)             tnac4o.calculate_overlap_correlations
 //   tn_spin_moments  out[i][j] = sum_a w_a [x_a,i != x_a,j]                        tnac4o.calculate_sample_correlations
+//   tn_pair_rowsums  out[a][k] = sum_{b != a} w_b dist(a, b)^k, k = 0 .. 4, ...    tnac4o.calculate_overlap_errors
 // dist = popcount(a XOR b) over bit-packed spins, or the 16-bit lanes (cell states) that differ.  Each family is described where its
 // kernels start; what they share comes first.
 #include "common.h"
@@ -675,6 +676,141 @@ inline SpinMomentsPlan spin_moments_plan(int64_t M, int64_t nbits, uint32_t wmax
     return p;
 }
 
+// ---- tn_pair_rowsums: out[a][k] = sum_{b != a} w_b d(a, b)^k (k = 0 .. 4), out[a][5] = sum_{b != a} w_b |nbits - 2 d(a, b)| -----------------
+// The pair matrix reduced per ROW instead of per distance bin.  pair_rowsums_kernel walks the full SQUARE of the pair matrix: a unit of
+// work is a block of 64 rows a and one of the S segments of the nblk blocks of 64 rows b; the tile loop is pair_hist_kernel's (chunks
+// of PH_CW words of both blocks through LDS, a 4 x 4 register block of distances per thread), the diagonal pairs a = b and the rows
+// >= M drop out through a weight of 0.  After the K loop of a tile the 4096 distances pass through LDS once (uint16, with the weights
+// of the 64 rows b next to them) and are dealt out again, row-wise: thread t takes row a = t / 4 and the 16 rows b of quarter t % 4, so
+// that it holds the six 128-bit sums of ONE row, 24 registers that live across the tiles of the unit, and not of the four rows of its
+// register block (that form, with the high limbs cut to what the bounds allow, took 155 VGPRs, left 3 waves per SIMD and ran 2 to 3 %
+// slower).  Per pair:
+// w d^2 in 64 bits, d^3 and d^4 as (w d^2) d and (w d^2) d^2 by a 64 x 64 -> 128 multiply; the sums of w, w d and w |n - 2 d| over the
+// 16 pairs stay in 64 bits (below 2^36, 2^52, 2^52) and are folded once per tile.  At the end of a unit the 4 threads of a row --
+// 4 consecutive lanes -- are added up with carry by shuffles, and the first of them writes the six sums into slab s of the
+// workspace.  The grid is persistent: workgroup g takes the units g, g + G, ...  pair_rowsums_reduce_kernel adds the S slabs of an
+// entry with carry (slab_sum) and writes every entry of out.  Integer adds, no atomics, no floating point: the same integers for
+// every grid and split.
+constexpr int64_t PR_MAX_NBITS = 65535;
+constexpr int64_t PR_MAX_ROWS = (int64_t)1 << 31;                  // M stays below
+constexpr int64_t PR_DEFAULT_WGS = 4 * 256;                        // 4 workgroups on each of 256 compute units
+constexpr int PR_DPITCH = PH_TILE + 8;                             // uint16 entries between two rows a of the distance table (16-byte aligned)
+static_assert(PR_MAX_NBITS < (1 << 16), "a distance fits the uint16 of the table");
+static_assert((unsigned __int128)0xffffffffull * PR_MAX_NBITS * PR_MAX_NBITS < ((unsigned __int128)1 << 64), "w d^2 fits one limb");
+static_assert((unsigned __int128)16 * 0xffffffffull * PR_MAX_NBITS < ((unsigned __int128)1 << 64), "the 16 terms w d, w |n - 2 d| of a tile fit one limb");
+static_assert(PR_MAX_NBITS * PR_MAX_NBITS < ((int64_t)1 << 32) && PR_MAX_ROWS <= ((int64_t)1 << 31),
+              "w d^4 = (w d^2) d^2 < 2^96 and fewer than 2^31 terms: a row's sum stays below 2^127");
+
+struct PairRowsumsPlan {
+    int64_t nblk, S, nwg, ws_bytes;
+};
+// The one layout of the workspace, for the size query and the call: S slabs of M rows x 6 entries of 16 bytes.  The grid asked for is
+// TN_PAIR_ROWSUMS_WGS (read per call) or 4 workgroups per compute unit; the blocks b of a row block are cut into S segments so that
+// there are at least that many units, at most one segment per block, and the grid never exceeds the units.
+inline PairRowsumsPlan pair_rowsums_plan(int64_t M) {
+    PairRowsumsPlan p;
+    p.nblk = cdiv(M, PH_TILE);
+    const int64_t asked = env_i64("TN_PAIR_ROWSUMS_WGS", 0), want = std::min<int64_t>(asked > 0 ? asked : PR_DEFAULT_WGS, PH_MAX_WGS);
+    p.S = p.nblk > 0 ? std::min<int64_t>(cdiv(want, p.nblk), p.nblk) : 0;
+    p.nwg = std::min<int64_t>(want, p.nblk * p.S);
+    p.ws_bytes = std::max<int64_t>(16, p.S * M * 6 * 16);
+    return p;
+}
+inline bool pair_rowsums_shape_ok(int64_t M, int64_t nbits) { return M >= 0 && M < PR_MAX_ROWS && nbits >= 1 && nbits <= PR_MAX_NBITS; }
+
+template <bool LANES16>
+__global__ __launch_bounds__(256) void pair_rowsums_kernel(const uint64_t* __restrict__ rows, int64_t M, int64_t nwords, int64_t ldr, uint64_t last_mask,
+                                                           const uint32_t* __restrict__ weights, int nbits, int64_t nblk, int64_t S,
+                                                           ulonglong2* __restrict__ slabs) {
+    __shared__ uint64_t sA[PH_CW * PH_PITCH], sB[PH_CW * PH_PITCH];
+    __shared__ __attribute__((aligned(16))) uint16_t sD[PH_TILE * PR_DPITCH];
+    __shared__ uint32_t sW[PH_TILE];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int r = tid >> 2, q = tid & 3;                       // after the K loop: row a0 + r against the rows b0 + 16 q .. b0 + 16 q + 15
+    for (int64_t u = blockIdx.x; u < nblk * S; u += gridDim.x) {
+        const int64_t ba = u / S, s = u % S, a0 = ba * PH_TILE;
+        unsigned long long lo[6], hi[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) lo[k] = hi[k] = 0;
+        for (int64_t bb = s * nblk / S; bb < (s + 1) * nblk / S; ++bb) {
+            const int64_t b0 = bb * PH_TILE;
+            unsigned dist[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dist[i][j] = 0;
+            for (int64_t k0 = 0; k0 < nwords; k0 += PH_CW) {
+                __syncthreads();                               // the previous chunk has been read
+                stage_block(sA, rows, M, ldr, a0, k0, nwords, last_mask);
+                stage_block(sB, rows, M, ldr, b0, k0, nwords, last_mask);
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < PH_CW; ++k) {
+                    uint64_t a[4], b[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        a[i] = sA[k * PH_PITCH + ty * 4 + i];
+                        b[i] = sB[k * PH_PITCH + tx * 4 + i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) dist[i][j] += pair_dist<LANES16>(a[i], b[j]);
+                }
+            }
+            // The tile's distances, and the weights of its rows b (0 for a row past the end, so that its pairs drop out below), through
+            // LDS.  Every thread has passed the barriers of this tile's K loop since it read the table of the tile before.
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                *(uint64_t*)&sD[(ty * 4 + i) * PR_DPITCH + tx * 4] =
+                    (uint64_t)dist[i][0] | (uint64_t)dist[i][1] << 16 | (uint64_t)dist[i][2] << 32 | (uint64_t)dist[i][3] << 48;
+            if (tid < PH_TILE) sW[tid] = b0 + tid < M ? (weights ? weights[b0 + tid] : 1u) : 0u;
+            __syncthreads();
+            ulonglong2 dv[2];
+            dv[0] = *(const ulonglong2*)&sD[r * PR_DPITCH + q * 16];
+            dv[1] = *(const ulonglong2*)&sD[r * PR_DPITCH + q * 16 + 8];
+            unsigned long long t0 = 0, t1 = 0, t5 = 0;                 // of the 16 pairs: below 2^36, 2^52, 2^52
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const unsigned long long word = j & 4 ? dv[j >> 3].y : dv[j >> 3].x;
+                const unsigned long long d = (word >> (16 * (j & 3))) & 0xffffu, dd = d * d;
+                const unsigned long long w = a0 + r == b0 + q * 16 + j ? 0ull : (unsigned long long)sW[q * 16 + j];       // (the diagonal pair)
+                const unsigned long long p2 = w * dd;
+                const int fold = nbits - 2 * (int)d;
+                t0 += w;
+                t1 += w * d;
+                t5 += w * (unsigned long long)(fold < 0 ? -fold : fold);
+                add128(lo[2], hi[2], p2, 0);
+                add128(lo[3], hi[3], p2 * d, __umul64hi(p2, d));
+                add128(lo[4], hi[4], p2 * dd, __umul64hi(p2, dd));
+            }
+            lo[0] += t0;                                               // (below 2^63 over all rows b: no carry)
+            add128(lo[1], hi[1], t1, 0);
+            add128(lo[5], hi[5], t5, 0);
+        }
+        // the 4 threads of a row: lanes 4 r' .. 4 r' + 3 of a wave
+#pragma unroll
+        for (int m = 1; m < 4; m *= 2)
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const unsigned long long vlo = __shfl_xor(lo[k], m), vhi = __shfl_xor(hi[k], m);
+                add128(lo[k], hi[k], vlo, vhi);
+            }
+        if (q == 0 && a0 + r < M) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) slabs[(s * M + a0 + r) * 6 + k] = make_ulonglong2(lo[k], hi[k]);
+        }
+    }
+}
+
+// out[e] = entry e = 6 a + k summed over the S slabs, with carry; every entry is written
+__global__ __launch_bounds__(256) void pair_rowsums_reduce_kernel(const unsigned long long* __restrict__ slabs, int64_t nslab, int64_t nent,
+                                                                  unsigned long long* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= nent) return;
+    ((ulonglong2*)out)[e] = slab_sum(slabs, nslab, nent, e);
+}
+
 }  // namespace
 
 }  // namespace tn
@@ -787,6 +923,35 @@ int tn_spin_moments(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr,
                                                          slabs, p.ntiles, p.nchunks, p.nwg, nrows, out, ldo));
         TN_CHECK_LAUNCH("spin_moments_reduce_kernel");
     }
+    return 0;
+}
+
+int64_t tn_pair_rowsums_ws_bytes(int64_t M, int64_t nbits, int lanes16) {
+    (void)lanes16;
+    if (!pair_rowsums_shape_ok(M, nbits)) return 0;
+    return pair_rowsums_plan(M).ws_bytes;
+}
+
+int tn_pair_rowsums(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, int lanes16, uint64_t* out, void* ws,
+                    int64_t ws_bytes, void* stream) {
+    if (int rc = check_pair_count(__func__, M)) return rc;
+    if (nbits < 1 || nbits > PR_MAX_NBITS) {
+        set_error("tn_pair_rowsums: nbits = %lld outside 1 .. %lld (w d^2 must stay below 2^64 and a row's sum of w d^4 below 2^127)", (long long)nbits,
+                  (long long)PR_MAX_NBITS);
+        return -1;
+    }
+    const int64_t nwords = pair_hist_nwords(nbits, lanes16);
+    if (int rc = check_operands(__func__, rows && (out || M == 0) && ws, ldr, nwords, "ldr shorter than a row")) return rc;
+    const PairRowsumsPlan p = pair_rowsums_plan(M);
+    if (int rc = check_workspace(__func__, ws_bytes, p.ws_bytes)) return rc;
+    if (M == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    launch_persistent(lanes16 ? &pair_rowsums_kernel<true> : &pair_rowsums_kernel<false>, st, p.nwg, 0, rows, M, nwords, ldr, last_word_mask(nbits, lanes16),
+                      weights, (int)nbits, p.nblk, p.S, (ulonglong2*)ws);
+    TN_CHECK_LAUNCH("pair_rowsums_kernel");
+    TN_PROF_LAUNCH(st, PROF_MISC, hipLaunchKernelGGL(pair_rowsums_reduce_kernel, dim3((unsigned)cdiv(M * 6, 256)), dim3(256), 0, st,
+                                                     (const unsigned long long*)ws, p.S, M * 6, (unsigned long long*)out));
+    TN_CHECK_LAUNCH("pair_rowsums_reduce_kernel");
     return 0;
 }
 

@@ -1048,6 +1048,23 @@ def pair_hist(rows, nbits, weights=None, lanes16=False):
     return out
 
 
+def pair_rowsums(rows, nbits, weights=None, lanes16=False):
+    """Per-row sums of the pairwise distances of packed rows (tn_pair_rowsums): rows, nbits, weights and lanes16 as pair_hist.
+    Returns the (M, 6, 2) int64 device tensor of the limbs (lo, hi) of, for every row a and over every other row b with
+    d = dist(a, b): out[a][0] = sum w_b, out[a][k] = sum w_b d^k (k = 1 .. 4), out[a][5] = sum w_b |nbits - 2 d|: exact integers
+    (read them as unsigned)."""
+    M, ld = _packed_rows(rows)
+    nbits = int(nbits)
+    nwords = -(-nbits // (4 if lanes16 else 64))
+    if rows.shape[1] < nwords:
+        raise ValueError('rows hold %d words, %d bits take %d' % (rows.shape[1], nbits, nwords))
+    d_w = _row_weights(weights, M)
+    l16 = int(bool(lanes16))
+    p_rows, out, ws, wsb = _stat_buffers('tn_pair_rowsums_ws_bytes', rows, M, (M, 6, 2), nbits, l16)
+    check(lib().tn_pair_rowsums(p_rows, M, nbits, max(ld, nwords), d_w, l16, out.data_ptr(), ws, wsb, _stream()))
+    return out
+
+
 def pair_moments(rows, G, wpg, weights=None, wmax=None, lanes16=False):
     """Second moments of the grouped pairwise distances of packed rows (tn_pair_moments): rows (M, ld) int64 / uint64 device tensor
     whose first G * wpg words are G groups of wpg words each, zero-padded by the caller (overlap.pack_groups); weights None (all 1)

@@ -1,10 +1,12 @@
 """Replica-overlap distributions of a set of configurations (host side of tnac4o.calculate_overlap_distribution) and
 their line-resolved second moments (tnac4o.calculate_overlap_correlations), and the correlations of every pair of spins
-over the configurations (tnac4o.calculate_sample_correlations).
+over the configurations (tnac4o.calculate_sample_correlations), and the jackknife errors of the overlap moments
+(tnac4o.calculate_overlap_errors).
 
 Plain numpy, importable without a GPU; the only device work is the pair histogram tn_pair_hist (ops.pair_hist), which the driver
 overlap_distribution calls once, the pair moments tn_pair_moments (ops.pair_moments), which overlap_correlations calls once per axis,
-and the spin moments tn_spin_moments (ops.spin_moments), which sample_correlations calls once.  Row layouts of the library: a row of
+the spin moments tn_spin_moments (ops.spin_moments), which sample_correlations calls once, and the per-row sums tn_pair_rowsums
+(ops.pair_rowsums), which overlap_errors calls once.  Row layouts of the library: a row of
 n bits is ceil(n / 64) uint64 words, bit i in word i // 64 at position i % 64; a row of n 16-bit lanes is ceil(n / 4) words, lane i
 in word i // 4 at bits 16 (i % 4) .. 16 (i % 4) + 15."""
 import numpy as np
@@ -81,20 +83,25 @@ def condense(rows, w):
     the SAME row: they have distance 0 and belong to bin 0.  float64 throughout.  The pair histogram of all M rows equals the one of
     the K distinct rows with weights W plus D0 in bin 0; at low temperature, where one row carries most of the weight, this keeps
     those pairs off a single word of the device histogram."""
+    return condense_with_inverse(rows, w)[:3]
+
+
+def condense_with_inverse(rows, w):
+    """condense, and the class of every sample: (urows, W, D0, inv) with inv (M,) int64, rows[s] == urows[inv[s]]."""
     rows = np.ascontiguousarray(rows, dtype=np.uint64)
     w = np.asarray(w, dtype=np.float64)
     if rows.ndim != 2 or w.shape != (rows.shape[0],):
         raise ValueError('rows (M, nwords) and w (M,) expected')
     if rows.shape[0] == 0:
-        return rows, w, 0.0
+        return rows, w, 0.0, np.zeros(0, dtype=np.int64)
     if rows.shape[1] == 0:
         urows, inv = rows[:1], np.zeros(rows.shape[0], dtype=np.int64)
     else:
         urows, inv = np.unique(rows, axis=0, return_inverse=True)
-    inv = np.asarray(inv).reshape(-1)
+    inv = np.asarray(inv).reshape(-1).astype(np.int64, copy=False)
     W = np.bincount(inv, weights=w, minlength=urows.shape[0])
     S = np.bincount(inv, weights=w * w, minlength=urows.shape[0])
-    return urows, W, float(np.sum(W * W - S) / 2.0)
+    return urows, W, float(np.sum(W * W - S) / 2.0), inv
 
 
 def quantise(W, wmax=WMAX):
@@ -132,6 +139,15 @@ def prepare(rows, w, wmax=WMAX):
     urows, W, D0 = condense(rows, w)
     wq, keep, scale = quantise(W, wmax)
     return np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep]), scale, D0
+
+
+def prepare_with_inverse(rows, w, wmax=WMAX):
+    """prepare, and where every sample went: (urows, wq, scale, D0, inv) with inv (M,) int64 = the index of sample s's row among the
+    kept distinct rows, -1 when the quantisation dropped it."""
+    urows, W, D0, inv = condense_with_inverse(rows, w)
+    wq, keep, scale = quantise(W, wmax)
+    index = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
+    return np.ascontiguousarray(urows[keep]), np.ascontiguousarray(wq[keep]), scale, D0, index[inv] if inv.size else inv
 
 
 def upload(urows, wq):
@@ -259,6 +275,160 @@ def overlap_distribution(solver, kind=None, weights='uniform'):
     solver.overlap_ess = effective_sample_size(w)
     solver.overlap_pairs = rows.shape[0] * (rows.shape[0] - 1) // 2
     return P
+
+
+# ---------------------------------------------------------------------------------------------- jackknife errors
+MAX_ROWSUM_NBITS = 65535         # largest row tn_pair_rowsums takes: w d^2 below 2^64, a row's sum of w d^4 below 2^127 (include/tnpeps.h)
+_SLOT_POWER = (0, 1, 1, 2, 4)    # the slots of a row's moments: k = 0, 1, A (|q|), 2, 4 and the power of n that an equal row contributes
+
+
+def rowsums_to_int(limbs):
+    """(K, 6, 2) limbs of tn_pair_rowsums (lo, hi; any integer dtype, read as unsigned 64-bit) -> K lists of six Python ints."""
+    h = np.asarray(limbs)
+    if h.ndim != 3 or h.shape[1:] != (6, 2):
+        raise ValueError('limbs (K, 6, 2) expected')
+    flat = limbs_to_int(h.reshape(-1, 2))
+    return [flat[6 * a:6 * a + 6] for a in range(h.shape[0])]
+
+
+def _row_moments(R, n, kind):
+    """For every row a the integers sum_{b != a} wq_b (n - c d_ab)^k in the slots k = 0, 1, A, 2, 4, from R_a[0 .. 5] by the binomial
+    expansion in Python integers (slot A: R_a[5] = sum wq_b |n - 2 d| for 'spin' and 'link'; for 'cell' |q| = q, the slot of k = 1)."""
+    c = 1 if kind == 'cell' else 2
+    out = []
+    for R0, R1, R2, R3, R4, R5 in ([int(v) for v in row] for row in R):
+        I1 = n * R0 - c * R1
+        I2 = n * n * R0 - 2 * n * c * R1 + c * c * R2
+        I4 = n ** 4 * R0 - 4 * n ** 3 * c * R1 + 6 * n * n * c * c * R2 - 4 * n * c ** 3 * R3 + c ** 4 * R4
+        out.append((R0, I1, I1 if kind == 'cell' else R5, I2, I4))
+    return out
+
+
+def _theta(Q, n, spin):
+    """The estimates from the five pair sums Q (slots 0, 1, A, 2, 4; any common factor cancels): dict over the keys of overlap_moments;
+    nan throughout when no pair carries weight."""
+    keys = ('q', 'abs_q', 'q2', 'q4', 'binder') + (('chi_sg',) if spin else ())
+    if not Q[0] > 0:
+        return dict.fromkeys(keys, float('nan'))
+    q2, q4 = Q[3] / (n * n * Q[0]), Q[4] / (n ** 4 * Q[0])
+    t = {'q': Q[1] / (n * Q[0]), 'abs_q': Q[2] / (n * Q[0]), 'q2': q2, 'q4': q4, 'binder': 0.5 * (3.0 - q4 / (q2 * q2)) if q2 > 0 else float('nan')}
+    if spin:
+        t['chi_sg'] = n * q2
+    return t
+
+
+def jackknife(R, wq, scale, inv, w, n, kind):
+    """Delete-one jackknife of the overlap moments of M weighted samples (calculate_overlap_errors of tnac4o).
+    R: K rows of six integers, the sums of tn_pair_rowsums over the K kept distinct rows (rowsums_to_int); wq (K,), scale: their
+    quantised weights (prepare); inv (M,): the kept row of sample s, -1 when the quantisation dropped it; w (M,): the raw weights;
+    n: bits (cells) per row; kind: 'spin', 'link' or 'cell'.
+    With c = 2 ('cell': 1) and What_b = wq_b / scale: r_a[k] = sum_{b != a} What_b (n - c d_ab)^k for k = 0, 1, 2, 4 and
+    r_a[A] = sum What_b |n - 2 d_ab| ('cell': r_a[1]); W_c = the summed raw weight of the samples that carry row c;
+    Q_k = 1/2 sum_s w_s (r_c(s)[k] + (W_c(s) - w_s) n^k), the second term for the other samples with the same row (A: n^1).
+    q = Q_1 / (n Q_0), abs_q = Q_A / (n Q_0), q2 = Q_2 / (n^2 Q_0), q4 = Q_4 / (n^4 Q_0), binder = (3 - q4 / q2^2) / 2, chi_sg = n q2
+    ('spin' only).  Without sample s: Q_k - w_s (r_c(s)[k] + (W_c(s) - w_s) n^k), and theta^(-s) from the same formulas; a sample of a
+    dropped row leaves theta as it is.  Only samples with w_s > 0 count, M' of them (fewer than three: ValueError).  With tbar the
+    mean of theta^(-s): error = sqrt((M' - 1) / M' sum_s (theta^(-s) - tbar)^2), bias_corrected = M' theta - (M' - 1) tbar.
+    The binomial sums are always formed in Python integers; with scale 1 and integer raw weights everything up to the final
+    divisions is (then theta^(-s) is computed once per distinct (row, weight): K values under uniform weights); otherwise the
+    integers are divided by scale and the rest is float64, the sums over the samples without rounding (math.fsum).  Rounded
+    weights: in the first term w_s stands for w_s What_c / W_c, the sample's share of the ROUNDED weight of its row (a factor within
+    2^-33 max W / W_c of 1), so that Q_k is the pair sum of `distribution` -- hist / scale^2 + D0 -- to rounding and the estimate
+    is that of calculate_overlap_distribution; the second term keeps the raw weights, as D0 does.
+    Returns {'estimate', 'error', 'bias_corrected', 'leave_one_out'}, each a dict over the keys of overlap_moments (leave_one_out:
+    arrays (M,), nan where w_s = 0), and 'state_q', 'state_q2' (M,): the mean of q and q^2 of state s with all OTHER samples,
+    (r[1] + (W_c - w_s) n) / (n (r[0] + W_c - w_s)) and likewise with r[2] and n^2 (nan for a dropped row or without partners)."""
+    import math
+    from collections import Counter
+    if kind not in KINDS:
+        raise ValueError("kind must be 'spin', 'link' or 'cell'")
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    inv = np.asarray(inv, dtype=np.int64).reshape(-1)
+    wq = np.asarray(wq).reshape(-1)
+    n, M, K = int(n), w.size, wq.size
+    if inv.shape != (M,) or len(R) != K or n < 1 or inv.size and (inv.min() < -1 or inv.max() >= K):
+        raise ValueError('R and wq of the K kept rows, inv and w of the M samples expected')
+    counted = w > 0
+    Mp = int(np.count_nonzero(counted))
+    if Mp < 3:
+        raise ValueError('the jackknife needs at least three samples with a positive weight')
+    spin = kind == 'spin'
+    I = _row_moments(R, n, kind)
+    powers = [n ** p for p in _SLOT_POWER]
+    exact = float(scale) == 1.0 and bool(np.all(w == np.rint(w)))
+    if exact:
+        r, Wc, ws, g, total = I, [int(x) for x in wq], [int(x) for x in w], [1] * K, sum
+    else:
+        r = [tuple(float(v) / float(scale) for v in row) for row in I]
+        Wc = np.bincount(inv[inv >= 0], weights=w[inv >= 0], minlength=K).tolist()
+        ws = w.tolist()
+        g = [float(q) / float(scale) / W if W > 0 else 0.0 for q, W in zip(wq.tolist(), Wc)]        # What_c / W_c
+        total = math.fsum
+    cls = inv.tolist()
+    # what a sample contributes to 2 Q, once per distinct (row, weight)
+    share = {}
+    for key in set(zip(cls, ws)):
+        c, x = key
+        if c >= 0:
+            share[key] = tuple(x * g[c] * r[c][k] + x * (Wc[c] - x) * powers[k] for k in range(5))
+    count = Counter(zip(cls, ws))
+    Q2 = [total(count[key] * t[k] for key, t in share.items()) for k in range(5)]
+    theta = _theta(Q2, n, spin)
+    if theta['q'] != theta['q']:
+        raise ValueError('no pair of distinct samples carries weight')
+    keys = list(theta)
+    loo_of, state_of = {}, {}
+    for key, t in share.items():
+        c, x = key
+        loo_of[key] = _theta([Q2[k] - 2 * t[k] for k in range(5)], n, spin) if x > 0 else None
+        den = r[c][0] + Wc[c] - x
+        state_of[key] = ((r[c][1] + (Wc[c] - x) * n) / (n * den), (r[c][3] + (Wc[c] - x) * n * n) / (n * n * den)) if den > 0 else (float('nan'),) * 2
+    loo = {k: np.full(M, np.nan) for k in keys}
+    state_q, state_q2 = np.full(M, np.nan), np.full(M, np.nan)
+    for s, key in enumerate(zip(cls, ws)):
+        if key in share:
+            state_q[s], state_q2[s] = state_of[key]
+        if key[1] > 0:
+            t = loo_of[key] if key in share else theta
+            for k in keys:
+                loo[k][s] = t[k]
+    est, err, corr = {}, {}, {}
+    for k in keys:
+        v = loo[k][counted]
+        tbar = float(np.mean(v))
+        est[k] = float(theta[k])
+        err[k] = float(np.sqrt((Mp - 1.0) / Mp * np.sum((v - tbar) ** 2)))
+        corr[k] = Mp * est[k] - (Mp - 1.0) * tbar
+    return {'estimate': est, 'error': err, 'bias_corrected': corr, 'leave_one_out': loo, 'state_q': state_q, 'state_q2': state_q2}
+
+
+def overlap_errors(solver, kind=None, weights='uniform'):
+    """calculate_overlap_errors of tnac4o (documented there)."""
+    kind, w = check_arguments(solver, kind, weights)
+    if np.count_nonzero(w > 0) < 3:
+        raise ValueError('calculate_overlap_errors needs at least three stored states with a positive weight')
+    rows, n, lanes16 = rows_of(solver, kind)
+    if n < 1:
+        raise ValueError("kind '%s': the model has nothing to compare" % kind)
+    if n > MAX_ROWSUM_NBITS:
+        raise NotImplementedError("kind '%s' compares %d %s per state; tn_pair_rowsums takes at most %d (its sums of w d^4 must stay below "
+                                  '2^127); there is no host fallback' % (kind, n, 'cells' if lanes16 else 'bits', MAX_ROWSUM_NBITS))
+    urows, wq, scale, _, inv = prepare_with_inverse(rows, w)
+    if urows.shape[0] >= 2:
+        from . import ops
+        d_rows, d_w = upload(urows, wq)
+        limbs = ops.pair_rowsums(d_rows, n, d_w, lanes16).cpu().numpy()
+    else:                                            # one distinct row: no pair of distinct rows, every sum is zero
+        limbs = np.zeros((urows.shape[0], 6, 2), dtype=np.int64)
+    jk = jackknife(rowsums_to_int(limbs), wq, scale, inv, w, n, kind)
+    solver.overlap_errors = jk['error']
+    solver.overlap_error_estimates = jk['estimate']
+    solver.overlap_bias_corrected = jk['bias_corrected']
+    solver.overlap_state_q = jk['state_q']
+    solver.overlap_state_q2 = jk['state_q2']
+    solver.overlap_error_kind = kind
+    solver.overlap_ess = effective_sample_size(w)
+    return jk['error']
 
 
 # ---------------------------------------------------------------------------------------------- line-resolved overlaps (DESIGN §16)

@@ -1718,6 +1718,30 @@ class tnac4o:
         from . import overlap
         return overlap.overlap_distribution(self, kind, weights)
 
+    def calculate_overlap_errors(self, kind=None, weights='uniform'):
+        """Error bars of the overlap moments of calculate_overlap_distribution -- <q>, <|q|>, <q^2>, <q^4>, the Binder ratio and, for
+        'spin', chi_sg -- by the delete-one jackknife over the M rows of `states`.  kind and weights as
+        calculate_overlap_distribution.  Equal rows are condensed; one call of tn_pair_rowsums gives, for every distinct row, the
+        exact integer sums over all other rows of w_b d^k (k = 0 .. 4) and w_b |n - 2 d|; from them the host forms the estimate
+        without each sample in turn (tnac4o_amd/overlap.py: jackknife).  With theta^(-s) the estimate without
+        sample s, tbar their mean and M' the samples with a positive weight: error = sqrt((M' - 1) / M' sum_s (theta^(-s) - tbar)^2).
+        Returns and stores overlap_errors, a dict over the keys of overlap_moments; stores overlap_error_estimates (the estimates
+        themselves: those of calculate_overlap_distribution up to rounding), overlap_bias_corrected = M' theta - (M' - 1) tbar,
+        overlap_state_q and overlap_state_q2 (M,) = the mean of q and of q^2 of state s with all OTHER samples (which states are
+        typical, which are outliers; nan for a state whose weight was rounded away), overlap_error_kind and overlap_ess.  Writes
+        none of the attributes of calculate_overlap_distribution.  Under uniform weights everything up to the final divisions
+        is exact; other weights are rounded to 32 bits of the largest.
+        INDEPENDENT samples only: the jackknife assumes that the rows of `states` are independent draws -- sample_boltzmann, or
+        gibbs_sampling draws.  States moved by the Monte Carlo calls (relax_samples, relax_lines, exchange_clusters,
+        temper_samples, anneal_population) are correlated, and the errors are then too small.
+        Degenerate statistic: where <s_i> = 0 for every spin (high temperature without fields) the pair statistic is degenerate
+        and the jackknife overestimates its variance, by about a factor of 2 (iid bits with p = 1/2, M = 128, n = 64: 1.9 to 2.4
+        in a host experiment).
+        Fewer than three states with a positive weight and bad arguments are a ValueError, more than 65535 bits (cells) per
+        state a NotImplementedError naming the limit, all raised before any device work; there is no host fallback."""
+        from . import overlap
+        return overlap.overlap_errors(self, kind, weights)
+
     def calculate_overlap_correlations(self, axis='both', kind=None, weights='uniform'):
         """Overlap correlations between the lattice lines, from all pairs of distinct rows of `states` (whatever wrote them), and the
         second-moment correlation length of the overlap.  The line overlap q_g of a replica pair is the overlap restricted to model
