@@ -902,6 +902,37 @@ int64_t tn_pair_rowsums_ws_bytes(int64_t M, int64_t nbits, int lanes16);
 int tn_pair_rowsums(const uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const uint32_t* weights, int lanes16, uint64_t* out, void* ws,
                     int64_t ws_bytes, void* stream);
 
+/* ---- K19: one measurement of the overlap histograms of a tempering ladder (no counterpart in the reference: the measure= of
+ * tnac4o.temper_samples) -----------------------------------------------------------------------------------------------------------------
+ * tn_ladder_measure: ADDS one measurement to accumulators on the device.  states (DEVICE, M x Nx*Ny int16), slot (DEVICE, R x T int32,
+ * R = M / T), cells (HOST) and bitcell (DEVICE, nbits x 2 int32) are those of tn_temper (K12) and are only read: the rows at temperature t
+ * are slot[c][t], c = 0 .. R-1.  Every row is converted to nbits packed spin bits by tn_temper's own kernel (row bit = 1 - state bit, a
+ * state outside its cell reads as 0, an entry of bitcell out of range leaves the bit 0).  For every t and every counted chain pair
+ * ca < cb, with d = popcount(row_a XOR row_b):  spin_hist[t (nbits + 1) + d] += 1  (DEVICE, T x (nbits + 1) uint64).  With links (DEVICE,
+ * nlinks x 2 int32 row positions) and link_hist (DEVICE, T x (nlinks + 1) uint64) the link row of a configuration has bit l = row bit
+ * links[l][0] XOR row bit links[l][1] -- 0 when either entry lies outside [0, nbits) --, and with d_l the distance of two link rows
+ * link_hist[t (nlinks + 1) + d_l] += 1 over the same pairs; link_hist NULL or nlinks = 0: no link overlap.
+ * split = 0: every pair ca < cb is counted.  0 < split <= R: only the pairs with ca < split <= cb (two sets of chains, overlaps between
+ * the sets); split = R counts nothing.  A slot entry outside [0, M) takes all pairs of that chain at that temperature out of the count.
+ * energy (DEVICE, M doubles: tn_temper's energy_out) and esums (DEVICE, T x 3 doubles), both or neither used: one thread per
+ * temperature forms s1 = sum E[slot[c][t]] and s2 = sum E^2 over c = 0 .. R-1 in ascending c (fp64, no contraction; a slot entry out
+ * of range is skipped), then esums[3t] += 1, esums[3t+1] += s1, esums[3t+2] += s2.
+ * Valid degenerate forms: R = 1, split = R and M = 0 count no pair; link_hist = NULL; energy or esums = NULL.  Only spin_hist, link_hist
+ * and esums are written, inside their extents.  The counts are an integer function of the inputs: bit-identical for every grid and
+ * every split of the pairs over workgroups (uint32 histograms in LDS with integer atomics, one slab per workgroup in ws, a reduce kernel
+ * that adds the slabs into the 64-bit accumulators; TN_LADDER_WGS = the workgroups that share the pairs of one temperature, default
+ * max(1, 1024 / T), never more than there are 16 x 16 tiles of pairs).  No floating-point atomics, no barrier across workgroups, no host
+ * synchronisation.  ws: tn_ladder_measure_ws_bytes (which reads TN_LADDER_WGS as the call does; 0 for a shape the call refuses): the table
+ * of the cells, the packed rows and link rows, the slabs.  Asynchronous on `stream`.
+ * Limits: 0 <= M < 2^31, M a multiple of T >= 1, R <= 65536 (R (R - 1) / 2 < 2^32: no bin of a workgroup can wrap); 1 <= nbits <= 38815
+ * and 0 <= nlinks <= 38815 (the histogram at 4 bytes per bin and 8576 bytes of staging must fit the 160 KiB of LDS); 0 <= split <= R;
+ * cells as tn_cell_sweep's.  Errors: -1 argument (the message names the limit), -3 workspace too small; both before any launch, nothing
+ * is written. */
+int64_t tn_ladder_measure_ws_bytes(int64_t Nx, int64_t Ny, int64_t M, int64_t T, int64_t nbits, int64_t nlinks);
+int tn_ladder_measure(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int64_t T, const int16_t* states, const int32_t* slot,
+                      int64_t nbits, const int32_t* bitcell, const int32_t* links, int64_t nlinks, int64_t split, const double* energy,
+                      uint64_t* spin_hist, uint64_t* link_hist, double* esums, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

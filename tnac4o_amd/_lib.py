@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libtnpeps.so')
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['api.hip', 'gemm_f64.hip', 'rank_update.hip', 'factor_products.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip', 'sampler.hip', 'overlap.hip', 'relax.hip', 'exchange.hip', 'temper.hip', 'anneal.hip', 'rng.hip', 'droplets.hip', 'linkage.hip', 'lines.hip']
+SOURCES = ['api.hip', 'gemm_f64.hip', 'rank_update.hip', 'factor_products.hip', 'small.hip', 'qr.hip', 'svd.hip', 'absorb.hip', 'misc.hip', 'beam.hip', 'prof.hip', 'cholqr.hip', 'smallqr.hip', 'fused.hip', 'peps.hip', 'env.hip', 'batch.hip', 'site.hip', 'chain.hip', 'beamsearch.hip', 'marginal.hip', 'sampler.hip', 'overlap.hip', 'relax.hip', 'exchange.hip', 'temper.hip', 'anneal.hip', 'rng.hip', 'droplets.hip', 'linkage.hip', 'lines.hip', 'ladder.hip']
 
 _i64, _f64, _int, _ptr = C.c_int64, C.c_double, C.c_int, C.c_void_p
 
@@ -125,6 +125,8 @@ SIGNATURES = {
     'tn_state_linkage': (_int, [_ptr, _i64, _i64, _i64, _int, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr]),
     'tn_line_sweep_ws_bytes': (_i64, [_i64, _i64, _i64]),
     'tn_line_sweep': (_int, [_i64, _i64, _ptr, _i64, _ptr, _int, _int, _f64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr]),
+    'tn_ladder_measure_ws_bytes': (_i64, [_i64] * 6),
+    'tn_ladder_measure': (_int, [_i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr]),
     'tn_profile_enable': (None, [C.c_uint]),
     'tn_profile_reset': (None, []),
     'tn_profile_sample': (None, [C.c_uint]),
@@ -225,7 +227,7 @@ SHORT_CALLS = ('tn_gemm', 'tn_gemm_ws_bytes', 'tn_qr_ws_bytes', 'tn_svd_ws_bytes
                'tn_mpo_from_factor_ops', 'tn_env3_stack', 'tn_env3_stack_ws_bytes', 'tn_stack_cell_law', 'tn_stack_cell_law_ws_bytes',
                'tn_last_error')
 _lib = None
-ABI_VERSION = 26       # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
+ABI_VERSION = 27      # bumped whenever a signature of include/tnpeps.h changes; must equal tn_version()
 
 
 def lib():

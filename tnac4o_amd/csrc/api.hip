@@ -23,7 +23,7 @@ using namespace tn;
 
 extern "C" {
 
-int tn_version(void) { return 26; }
+int tn_version(void) { return 27; }
 
 #ifndef TN_SRC_HASH
 #define TN_SRC_HASH "unknown"

@@ -48,6 +48,11 @@ int64_t cluster_exchange_max_nbits();
 int cluster_exchange_launch(hipStream_t st, uint64_t* rows, int64_t M, int64_t nbits, int64_t ldr, const int32_t* rowptr, const int32_t* cols,
                             int64_t nnz, const int32_t* pairs, int64_t P, const double* uniforms, int32_t* size_out, int32_t* diff_out);
 
+// temper.hip: states -> packed spin bits of tn_temper (rows: M x ceil(nbits / 64) words, every word written; M x words / 256 below 2^31 is
+// the caller's duty), the one source of the conversion for tn_ladder_measure (ladder.hip) too
+int temper_to_bits_launch(hipStream_t st, const SweepCell* cells, const int16_t* states, int64_t ncell, int64_t M, int64_t nbits, const int32_t* bitcell,
+                          uint64_t* rows);
+
 // the product of non-negative factors fits an index: no overflow and below 2^60
 inline bool mul_fits(std::initializer_list<int64_t> f) {
     int64_t p = 1;

@@ -158,6 +158,16 @@ TemperWs temper_layout(void* ws, int64_t Nx, int64_t Ny, int64_t M, int64_t T, i
 
 }  // namespace
 
+// sweep.h: the launch of temper_to_bits_kernel, for tn_temper and tn_ladder_measure (ladder.hip)
+int temper_to_bits_launch(hipStream_t st, const SweepCell* cells, const int16_t* states, int64_t ncell, int64_t M, int64_t nbits, const int32_t* bitcell,
+                          uint64_t* rows) {
+    const int64_t nwords = cdiv(nbits, 64);
+    hipLaunchKernelGGL(temper_to_bits_kernel, dim3((unsigned)cdiv(M * nwords, 256)), dim3(256), 0, st, cells, states, ncell, M, (int)nbits, (int)nwords,
+                       bitcell, rows);
+    TN_CHECK_LAUNCH("temper_to_bits_kernel");
+    return 0;
+}
+
 }  // namespace tn
 
 using namespace tn;
@@ -245,9 +255,7 @@ int tn_temper(int64_t Nx, int64_t Ny, const tn_beam_cell* cells, int64_t M, int6
         for (int64_t j = 0; j < sweeps; ++j)
             BS(sweep_once(st, plan, w.cells, states, 0, 0.0, rb, usweep + (r * sweeps + j) * ncell * ldu, ldu, nullptr));
         if (cluster) {
-            hipLaunchKernelGGL(temper_to_bits_kernel, dim3((unsigned)cdiv(M * nwords, 256)), dim3(256), 0, st, w.cells, states, ncell, M, (int)nbits,
-                               (int)nwords, bitcell, w.rows);
-            TN_CHECK_LAUNCH("temper_to_bits_kernel");
+            BS(temper_to_bits_launch(st, w.cells, states, ncell, M, nbits, bitcell, w.rows));
             hipLaunchKernelGGL(temper_pairs_kernel, dim3((unsigned)cdiv(np, 256)), dim3(256), 0, st, slot, R, T, cluster_from, Tc, cpairs + r * Pc * 2, Pc,
                                w.pairs);
             TN_CHECK_LAUNCH("temper_pairs_kernel");

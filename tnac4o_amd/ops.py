@@ -1214,6 +1214,47 @@ def temper(cells, Nx, Ny, betas, states, tidx, slot, round0, rounds, sweeps, usw
     return out
 
 
+def ladder_measure(cells, Nx, Ny, states, slot, nbits, bitcell, spin_hist, links=None, link_hist=None, split=0, energy=None, esums=None):
+    """One measurement of the overlap histograms of a tempering ladder, ADDED to the accumulators (tn_ladder_measure; include/tnpeps.h,
+    K19).  cells, states (M, Nx*Ny) int16, slot (R, T) int32 and bitcell (nbits, 2) int32 as ops.temper takes them (read only);
+    spin_hist (T, nbits + 1) int64, links (nlinks, 2) int32 row positions with link_hist (T, nlinks + 1) int64 (both or neither),
+    energy (M,) float64 with esums (T, 3) float64 (both or neither): contiguous device tensors -- views into larger accumulators are
+    fine.  split: 0 counts every chain pair ca < cb, 0 < split <= R only those with ca < split <= cb.  Returns nothing."""
+    if not states.is_cuda:
+        raise RuntimeError('tnac4o_amd operates on GPU tensors only (got a %s tensor); there is no CPU path' % states.device)
+    if states.dim() != 2 or states.dtype != torch.int16 or not states.is_contiguous() or states.shape[1] != Nx * Ny:
+        raise TypeError('states: a contiguous (M, Nx*Ny) int16 device tensor')
+    if slot.dim() != 2:
+        raise TypeError('slot: an (R, T) tensor')
+    M, T, nbits = int(states.shape[0]), int(slot.shape[1]), int(nbits)
+    p_slot, p_bc = _i32_operand(slot, 'slot', M), _i32_operand(bitcell, 'bitcell', 2 * max(nbits, 0))
+
+    def acc(t, name, dtype, shape):
+        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise TypeError('%s: a contiguous %s device tensor of %s' % (name, shape, dtype))
+        return t.data_ptr()
+
+    p_sh = acc(spin_hist, 'spin_hist', torch.int64, (T, nbits + 1))
+    nlinks, p_links, p_lh = 0, None, None
+    if (links is None) != (link_hist is None):
+        raise TypeError('links and link_hist go together')
+    if links is not None:
+        if links.dim() != 2 or links.shape[1] != 2:
+            raise TypeError('links: an (nlinks, 2) tensor')
+        nlinks = int(links.shape[0])
+        p_links = _i32_operand(links, 'links')
+        p_lh = acc(link_hist, 'link_hist', torch.int64, (T, nlinks + 1))
+    p_e, p_es = None, None
+    if (energy is None) != (esums is None):
+        raise TypeError('energy and esums go together')
+    if energy is not None:
+        p_e, p_es = acc(energy, 'energy', torch.float64, (M,)) if M else p_slot, acc(esums, 'esums', torch.float64, (T, 3))
+    wsb = int(lib().tn_ladder_measure_ws_bytes(Nx, Ny, M, T, nbits, nlinks))
+    ws = workspace(max(wsb, 16), 1)
+    check(lib().tn_ladder_measure(Nx, Ny, C.cast(cells, C.c_void_p), M, T, states.data_ptr() if M else p_slot, p_slot, nbits, p_bc, p_links, nlinks,
+                                  int(split), p_e, p_sh, p_lh, p_es, ws.data_ptr(), wsb, _stream()))
+
+
 def anneal(cells, Nx, Ny, betas, states, family, sweeps, usweep=None, ures=None, record=False):
     """The steps betas[0] -> betas[1] -> ... of population annealing, IN PLACE in states and family (tn_anneal; include/tnpeps.h, K13).
     cells: the ctypes tn_beam_cell array of the lattice (relax.EnergyCells(...).cells); betas: K host floats, betas[0] >= 0 and strictly

@@ -192,11 +192,14 @@ def reorder_trace(energy_trace, tidx_trace, T):
     return out
 
 
-def temper_native(solver, states_rot, a, record, tables=None):
+def temper_native(solver, states_rot, a, record, tables=None, meas=None):
     """The device loop: states, tables and graph go up once, the rounds run in blocks of rounds_per_call calls of tn_temper with round0
     advanced, everything comes back once.  states_rot: (M, Ny*Nx) in the lattice order of the current rotation; a: what
-    check_arguments returned; tables: (nbits, cellbits, bitcell, rowptr, cols) numpy, or None without cluster moves.  Returns a dict of
-    numpy arrays: states, energy, tidx, accepted, attempted, and with record energy_trace, tidx_trace, sizes, differing."""
+    check_arguments returned; tables: (nbits, cellbits, bitcell, rowptr, cols) numpy, or None without cluster moves.  meas: None, or
+    what ladder.check_arguments returned with nbits, bitcell and links (numpy, or None) added: the blocks are cut so that one ends behind
+    every measurement round, and tn_ladder_measure follows it on the stream with that block's energies, adding to the accumulators of
+    the measurement's time bin.  Returns a dict of numpy arrays: states, energy, tidx, accepted, attempted, with record energy_trace,
+    tidx_trace, sizes, differing, and with meas spin_hist (B, T, nbits + 1), link_hist (B, T, nlinks + 1) or None, esums (B, T, 3)."""
     import torch
     from . import ops
     from .relax import EnergyCells
@@ -218,6 +221,15 @@ def temper_native(solver, states_rot, a, record, tables=None):
         fixed = M * Nx * Ny * 2 + int(ops.lib().tn_temper_ws_bytes(Nx, Ny, M, T, 0 if tables is None else tables[0], a['pairs'].shape[1]))
         per = plan_rounds(rounds, round_bytes(a['shapes'], M, record), max(torch.cuda.mem_get_info(dev)[0] // 2 - fixed, 0))
     given = a['uniforms']
+    due = {}
+    if meas is not None:
+        B = meas['B']
+        due = {int(r) + 1: int(b) for r, b in zip(meas['after'], meas['bins'])}               # block end -> time bin
+        m_bitcell = torch.as_tensor(np.ascontiguousarray(meas['bitcell'], dtype=np.int32)).to(dev)
+        m_links = None if meas['links'] is None else torch.as_tensor(np.ascontiguousarray(meas['links'], dtype=np.int32)).to(dev)
+        d_sh = torch.zeros((B, T, meas['nbits'] + 1), dtype=torch.int64, device=dev)
+        d_lh = None if m_links is None else torch.zeros((B, T, m_links.shape[0] + 1), dtype=torch.int64, device=dev)
+        d_es = torch.zeros((B, T, 3), dtype=torch.float64, device=dev)
 
     def block(u, lo, hi):
         u = u[lo:hi]
@@ -225,8 +237,9 @@ def temper_native(solver, states_rot, a, record, tables=None):
 
     outs = []
     energy = None
-    for lo in range(0, max(rounds, 1), per):
-        hi = min(lo + per, rounds)
+    from .ladder import block_ends
+    lo = 0
+    for hi in block_ends(rounds, per, None if meas is None else meas['after']):
         if a.get('seed') is not None:
             d_u = seeded_block(a['seed'], a['shapes'], lo, hi, dev)
         else:
@@ -237,33 +250,51 @@ def temper_native(solver, states_rot, a, record, tables=None):
                          cluster_from=a['cluster_from'], cpairs=None if d_pairs is None else d_pairs[lo:hi].contiguous(), ucl=d_u['cluster'],
                          uswap=d_u['swap'], accepted=d_acc if T > 1 else None, attempted=d_att if T > 1 else None, record=record)
         energy = out['energy']
-        outs.append(out)
-        del d_u                                             # (released in stream order: the next block's numbers may take their place)
+        if record:
+            outs.append(out)
+        del d_u                                            # (released in stream order: the next block's numbers may take their place)
+        if hi in due:
+            b = due[hi]
+            ops.ladder_measure(table.cells, Nx, Ny, d_st, d_slot, meas['nbits'], m_bitcell, d_sh[b], m_links, None if d_lh is None else d_lh[b],
+                               meas['split'], energy, d_es[b])
+        lo = hi
     res = dict(states=d_st.cpu().numpy().astype(np.int64), energy=energy.cpu().numpy(), tidx=d_tidx.cpu().numpy().astype(np.int64),
                accepted=d_acc.cpu().numpy().astype(np.int64), attempted=d_att.cpu().numpy().astype(np.int64))
     if record:
         for k in ('energy_trace', 'tidx_trace', 'sizes', 'differing'):
             res[k] = None if outs[0][k] is None else np.concatenate([o[k].cpu().numpy() for o in outs], axis=0)
+    if meas is not None:
+        res.update(spin_hist=d_sh.cpu().numpy(), link_hist=None if d_lh is None else d_lh.cpu().numpy(), esums=d_es.cpu().numpy())
     del table
     return res
 
 
 def temper_samples(solver, betas, rounds=10, sweeps=1, cluster_moves=True, cluster_beta_min=None, pairs=None, uniforms=None, record=False,
-                   keep=None, rounds_per_call=None, seed=None):
+                   keep=None, rounds_per_call=None, seed=None, measure=None, measure_from=0, measure_bins=16, measure_pairs='all',
+                   measure_links=True):
     """temper_samples of tnac4o (documented there)."""
     a = check_arguments(solver, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, keep, rounds_per_call, seed)
+    meas = None
+    if measure is not None:
+        from . import ladder
+        meas = ladder.check_arguments(solver, a, measure, measure_from, measure_bins, measure_pairs, measure_links)
     tables = None
     if a['cluster']:
         tables = bit_tables(solver) + coupling_csr(solver)
+    if meas is not None:
+        nbits, _, bitcell = tables[:3] if tables is not None else bit_tables(solver)
+        meas.update(nbits=nbits, bitcell=bitcell, links=ladder.link_table(solver) if meas['links'] else None)
     st = a['states']
     rot = np.empty_like(st)
     rot[:, solver.order] = st                                # the inverse of _store_result's states[:, order]
-    res = temper_native(solver, rot, a, bool(record), tables)
+    res = temper_native(solver, rot, a, bool(record), tables, meas)
     T, R = a['T'], a['R']
     states, energy, tidx = res['states'][:, solver.order], res['energy'], res['tidx']
     solver.temper_betas = a['betas']
     solver.temper_index, solver.temper_beta = tidx, a['betas'][tidx]
     solver.temper_swap_accepted, solver.temper_swap_attempted = res['accepted'], res['attempted']
+    if meas is not None:
+        ladder.store(solver, res['spin_hist'], res['link_hist'], res['esums'], meas['n_meas'], R, a['betas'])
     if record:
         solver.temper_energy_trace = reorder_trace(res['energy_trace'], res['tidx_trace'], T)
         Tc, Pc = a['shapes']['cluster'][1:]

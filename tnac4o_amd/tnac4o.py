@@ -1279,7 +1279,8 @@ class tnac4o:
         return linkage.state_linkage(self, threshold, kind, symmetric, states)
 
     def temper_samples(self, betas, rounds=10, sweeps=1, cluster_moves=True, cluster_beta_min=None, pairs=None, uniforms=None, record=False,
-                       keep=None, rounds_per_call=None, seed=None):
+                       keep=None, rounds_per_call=None, seed=None, measure=None, measure_from=0, measure_bins=16, measure_pairs='all',
+                       measure_links=True):
         """Parallel tempering with isoenergetic cluster moves (PT+ICM: Zhu, Ochoa, Katzgraber) over the stored configurations, whole
         rounds on the device in one library call (tn_temper, tnac4o_amd/temper.py).  Runs NO contraction and needs no
         boundary MPS; the solver's own beta plays no part.
@@ -1312,10 +1313,31 @@ class tnac4o:
         probability, sample_log2Z, log2Z_lower and log2Z_estimate are set to None, as relax_samples does.
         keep: None leaves a MIXED population in states / energy -- rows at all T temperatures, told apart by temper_index, which the
         calculate_overlap_* calls would pool; keep=t leaves only the R rows that end at temperature index t (chains ascending) in
-        states and energy, so that those calls see one temperature (temper_index and temper_beta still describe all M rows)."""
+        states and energy, so that those calls see one temperature (temper_index and temper_beta still describe all M rows).
+        measure: None (nothing below happens or is stored), or a positive integer: overlap histograms at EVERY temperature, accumulated
+        on the device between the blocks of rounds (tn_ladder_measure, tnac4o_amd/ladder.py; Ising only, R >= 2, at most
+        38815 active spins and 38815 couplings, else NotImplementedError).  A measurement follows global round r, after its swaps,
+        iff r >= measure_from and (r - measure_from + 1) % measure == 0: n_meas = (rounds - measure_from) // measure of them (none, a
+        non-positive measure or a measure_from outside [0, rounds]: ValueError); measurement i goes to time bin i B // n_meas with
+        B = min(measure_bins, n_meas).  The library calls are cut at the measurement rounds; states, energy, temper_index and the
+        counters are the bits of the same call without measure (with uniforms=None the global generator's stream follows the cut, as
+        it follows rounds_per_call).  A measurement counts, for every temperature t and every chain pair, the Hamming distance d of
+        the two rows at t over the active spins (q = 1 - 2 d / n) and, with measure_links, over the couplings of overlap.link_pairs
+        (q_l = 1 - 2 d_l / n_l).  measure_pairs='all': every pair of chains; 'halves': only pairs with one chain below R // 2 and one
+        at or above it -- the two-sets convention of PT+ICM; with cluster moves the given pairs= must then stay inside the halves
+        (ladder.pairs_in_halves draws such pairings), else ValueError.
+        Stores temper_measurements = n_meas; temper_overlap_hist (B, T, n + 1) and temper_link_hist (B, T, n_l + 1) int64 pair counts
+        per time bin, temper_overlap_values / temper_link_values, temper_overlap_P / temper_link_P (T, n + 1) / (T, n_l + 1) summed
+        over the bins and normalised (the three link results are None with measure_links=False); temper_overlap_moments, a dict of
+        (T,) arrays q, abs_q, q2, q4, binder, chi_sg (conventions of overlap_moments) and ql = the mean link overlap;
+        temper_overlap_errors, the same keys from a delete-one-bin jackknife over the B time bins (NaN when B < 2);
+        temper_energy_sums (B, T, 3) = measurements, sum E, sum E^2 over the R rows at each temperature, temper_energy_mean (T,),
+        temper_heat_capacity (T,) = beta^2 (<E^2> - <E>^2) / n and temper_energy_mean_error, temper_heat_capacity_error from the same
+        jackknife.  The jackknife assumes bins longer than the autocorrelation time; with 'all' under cluster moves the pairs of
+        chains are not independent, which it does not see."""
         from . import temper
         return temper.temper_samples(self, betas, rounds, sweeps, cluster_moves, cluster_beta_min, pairs, uniforms, record, keep, rounds_per_call,
-                                     seed)
+                                     seed, measure, measure_from, measure_bins, measure_pairs, measure_links)
 
     def anneal_population(self, betas, sweeps=1, M=None, uniforms=None, record=False, log2Z0=None, steps_per_call=None, seed=None):
         """Population annealing (Hukushima, Iba; Machta; Wang, Machta, Katzgraber): a population of M configurations is taken along the
